@@ -8,8 +8,12 @@ LFB row table (reference rule, on device) -> TMRNet forward (rows read from the 
 This is the per-step work of train_only_non-local_pretrained.py:698-725 (BASELINE.json configs[1],
 configs[2] at N=8).  Synthetic data/weights per SURVEY.md §8d (seeds 1-5, torch.manual_seed(0)).
 
-Prints ONE JSON line (rank 0).  Multi-GPU: launched by torch.distributed.run, one rank per GPU,
-each rank trains its own B clips (weak scaling), gradients summed across ranks.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the
+line; --full adds the live conv roofline (one more, profiled, step), the committed PMC traffic
+figures and the CPU baseline (those keys are null in a plain line).  --dump-outputs DIR writes the
+last timed step's loss, logits and samples of gradients / updated parameters.  Multi-GPU: launched
+by torch.distributed.run, one rank per GPU, each rank trains its own B clips (weak scaling),
+gradients summed across ranks.
 """
 import argparse
 import json
@@ -42,9 +46,18 @@ def parse():
     ap.add_argument("--clips", type=int, default=64, help="clips per rank (reference batch)")
     ap.add_argument("--seq", type=int, default=10)
     ap.add_argument("--lfb", type=int, default=40)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--conv-table", action="store_true", help="per-launch conv table on stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the live conv roofline (one profiled "
+                         "step), read the committed PMC traffic records and time the CPU "
+                         "baseline; a plain run only sets up, warms up, times --steps steps and "
+                         "prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, logits, fixed seeded "
+                         "samples of the gradients and of the updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline")
+    ap.add_argument("--conv-table", action="store_true",
+                    help="with --full: per-launch conv table on stderr")
     ap.add_argument("--cpu-clips", type=int, default=4)
     ap.add_argument("--cpu-steps", type=int, default=5)
     ap.add_argument("--cpu-warmup", type=int, default=2)
@@ -179,7 +192,7 @@ def main():
         if reducer is not None:
             reducer.all_reduce_sum()
         opt.step()
-        return loss
+        return loss, out
 
     for i in range(args.warmup):
         step(i)
@@ -196,7 +209,7 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.warmup, args.warmup + args.steps):
-        loss = step(i)
+        loss, out = step(i)
         marks[i - args.warmup + 1].record()
     torch.cuda.synchronize()
     if dist is not None:
@@ -213,17 +226,20 @@ def main():
     fps = frames_total / elapsed
     ms = elapsed / args.steps * 1e3
     loss_v = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        # before anything below runs another step: the state is the last timed step's
+        dump_outputs(args.dump_outputs, loss, out, model)
 
     # ---- live roofline of the dominant kernel family (implicit-GEMM conv) ----
     roof = None
     # the committed PMC passes profile the default geometry (64 clips x 10 frames, L=40)
     traffic = (load_traffic(args.model, args.precision, args.seq, args.lfb)
-               if args.clips == 64 else None)
+               if args.full and args.clips == 64 else None)
     stale = bool(traffic and traffic.get("stale"))
     if stale:
         traffic_src = traffic
         traffic = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         ops.PROF = []
         torch.cuda.synchronize()
         i = args.warmup + args.steps
@@ -298,7 +314,7 @@ def main():
         dist.destroy_process_group()
         dist = None
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     if rank == 0:
@@ -328,6 +344,35 @@ def main():
             "cpu_baseline": cpu,
         }
         print(json.dumps(line), flush=True)
+
+
+DUMP_SAMPLE = 65536   # elements kept per parameter tensor (14-19 MB per sampled array)
+
+
+def dump_outputs(path, loss, logits, model):
+    """--dump-outputs: what a caller of the timed step holds after the last timed step, as
+    float32 .npy files under `path` (rank 0's share at N > 1): loss (the CE sum), logits (B x 7),
+    and -- the step's effect on the model -- grads and params, each the concatenation over
+    model.named_parameters() of the tensor flattened (up to DUMP_SAMPLE elements) or of
+    DUMP_SAMPLE of its elements at sorted indices drawn once from numpy's default_rng(0), so two
+    builds sample the same elements.  A parameter without a gradient contributes zeros."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(0)
+    grads, params = [], []
+    for _, p in model.named_parameters():
+        flat = p.detach().reshape(-1)
+        g = p.grad.detach().reshape(-1) if p.grad is not None else torch.zeros_like(flat)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(rng.choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            idx = torch.from_numpy(idx).to(flat.device)
+            flat, g = flat[idx], g[idx]
+        params.append(flat.float().cpu())
+        grads.append(g.float().cpu())
+    arrays = {"loss": loss.detach().float().reshape(1).cpu(),
+              "logits": logits.detach().float().cpu(),
+              "grads": torch.cat(grads), "params": torch.cat(params)}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.numpy().astype(np.float32, copy=False))
 
 
 def rank_diagnostics(dist, world, dev, elapsed, marks, reducer, c0, steps):
