@@ -112,7 +112,10 @@ int tmr_conv2d_fwd(const tmr_conv_desc* d, const float* x, const float* w_krsc,
  * Bottleneck units: LFB construction, Training TMRNet/train_only_non-local_pretrained.py:570-590,
  * and the eval scripts): y = [relu](fmaf(conv(x, w_krsc), scale[k], shift[k]) + residual),
  * the same arithmetic as tmr_conv2d_fwd followed by tmr_bn_apply, without the y round trip.
- * scale/shift from tmr_bn_eval_params; residual (NHWC like y) may be NULL, must not alias y. */
+ * scale/shift from tmr_bn_eval_params; residual (NHWC like y) may be NULL, must not alias y.
+ * TMR_IO_Y_BF16 (with TMR_IO_X_BF16 | TMR_IO_W_BF16, TMR_MATH_BF16; no groups): y and residual
+ * are bf16 tensors -- the same arithmetic in fp32 on the widened residual, rounded once (RNE) at
+ * the store; scale/shift stay fp32.  The bf16-activation inference contract. */
 int tmr_conv2d_fwd_fused(const tmr_conv_desc* d, const float* x, const float* w_krsc,
                          const float* scale, const float* shift, const float* residual, float* y,
                          int relu, hipStream_t stream);

@@ -546,7 +546,7 @@ constexpr int occ16() {
 
 // the body of one workgroup: output tile `bid` (m-major over the n-tiles), reduction split `split`
 template <int MODE, int BM, int BN, int WM, int WN, int TAPV, int PIPE, int F32, int PRO, int NST,
-          int EPF = 0>
+          int EPF = 0, int INF16 = 0>
 __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, const int split) {
   constexpr uint32_t ES = F32 ? 4u : 2u;   // element bytes
   constexpr int EPC = 16 / ES;             // elements per 16-B chunk
@@ -1103,8 +1103,8 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
       return;
     }
   }
-  epilogue_batched<MODE, BM, BN, WM, WN, TM, TN>(a, acc, reinterpret_cast<float*>(smem), m0, n0,
-                                                 split);
+  epilogue_batched<MODE, BM, BN, WM, WN, TM, TN, INF16>(a, acc, reinterpret_cast<float*>(smem), m0,
+                                                        n0, split);
 }
 
 template <int MODE, int BM, int BN, int WM, int WN, int TAPV, int PIPE = 1, int F32 = 0, int PRO = 0,
@@ -1187,6 +1187,10 @@ namespace tmrg {
 template <int MODE, int BM, int BN, int WM, int WN, int F32, int PRO = 0>
 int launch16_cfg(const GemmArgs& a, bool tapv, dim3 grid, hipStream_t st) {
   const dim3 blk(64 * WM * WN);
+  // the bf16-activation inference epilogue (bf16 residual / y): its own kernels (gemm16_select.h)
+  if constexpr (MODE == MODE_FWD && F32 == 0 && PRO == 0) {
+    if (a.c16 && a.scale) return launch16_inf16<BM, BN, WM, WN>(a, tapv, grid, st);
+  }
   // one-k-tile bf16 FWD launches on the 4-wave 128x128 / 256x64 tiles: the one-stage form
   // (bit-identical to the two-stage form, which it replaced in round 4).  56x56 64->64: 0.427 ->
   // 0.378 ms; the DGRAD view measured slower in it (its 233-VGPR LDS-staged epilogue caps the

@@ -194,4 +194,19 @@ extern template int launch_gemm16<MODE_DGRAD, 1>(const GemmArgs&, int, hipStream
 extern template int launch_gemm16<MODE_WGRAD, 0>(const GemmArgs&, int, hipStream_t);
 extern template int launch_gemm16<MODE_WGRAD, 1>(const GemmArgs&, int, hipStream_t);
 
+// the bf16-activation inference forwards (tmr_conv2d_fwd_fused with TMR_IO_Y_BF16: bf16 residual
+// and y, epilogue_batched's INF16 form) of one tile config, in the launch form (one-stage, TAPV)
+// the same tile's other bf16 forwards take -- their accumulators are bit-identical.  Kernels of
+// their own (gemm16_fwd_inf16.hip): the train step's instantiations are not touched.
+template <int BM, int BN, int WM, int WN>
+int launch16_inf16(const GemmArgs& a, bool tapv, dim3 grid, hipStream_t st);
+extern template int launch16_inf16<256, 128, 4, 2>(const GemmArgs&, bool, dim3, hipStream_t);
+extern template int launch16_inf16<128, 128, 2, 2>(const GemmArgs&, bool, dim3, hipStream_t);
+extern template int launch16_inf16<256, 64, 4, 1>(const GemmArgs&, bool, dim3, hipStream_t);
+extern template int launch16_inf16<64, 256, 1, 4>(const GemmArgs&, bool, dim3, hipStream_t);
+extern template int launch16_inf16<128, 128, 4, 2>(const GemmArgs&, bool, dim3, hipStream_t);
+extern template int launch16_inf16<64, 64, 2, 2>(const GemmArgs&, bool, dim3, hipStream_t);
+extern template int launch16_inf16<256, 256, 2, 4>(const GemmArgs&, bool, dim3, hipStream_t);
+extern template int launch16_inf16<256, 256, 4, 4>(const GemmArgs&, bool, dim3, hipStream_t);
+
 }  // namespace tmrg

@@ -289,6 +289,7 @@ TMR_API int tmr_conv2d_fwd_fused(const tmr_conv_desc* d, const float* x, const f
   TMR_CHECK_ARG(scale && shift, "tmr_conv2d_fwd_fused: null BatchNorm scale/shift");
   TMR_CHECK_ARG(!residual || residual != y, "tmr_conv2d_fwd_fused: residual must not alias y");
   if (ngroups(d) > 1) {
+    TMR_CHECK_ARG(!(d->io & TMR_IO_Y_BF16), "tmr_conv2d_fwd_fused: a grouped conv writes fp32 (no TMR_IO_Y_BF16)");
     tmr_conv_desc g;
     if (group_split(d, g)) return 1;
     for (int i = 0; i < d->groups; ++i) {
@@ -306,12 +307,22 @@ TMR_API int tmr_conv2d_fwd_fused(const tmr_conv_desc* d, const float* x, const f
     const tmr_conv_desc c = chunk_desc(d, d->n - f0 < fc ? d->n - f0 : fc);
     GemmArgs a;
     bool al;
-    int rc = conv_fwd_args(&c, adv(x, f0 * x_frame(d), esz_x(d)), w_krsc, shift, y + f0 * y_frame(d), 0.f, a, al);
+    int rc = conv_fwd_args(&c, adv(x, f0 * x_frame(d), esz_x(d)), w_krsc, shift, adv(y, f0 * y_frame(d), esz_y(d)), 0.f, a, al);
     if (rc) return rc;
-    TMR_CHECK_ARG(!a.c16, "tmr_conv2d_fwd_fused: the inference epilogue writes fp32 (no TMR_IO_Y_BF16)");
     a.scale = scale;
-    a.res = residual ? residual + f0 * y_frame(d) : nullptr;
+    a.res = adv(residual, f0 * y_frame(d), esz_y(d));
     a.relu = relu;
+    if (a.c16) {
+      // bf16 activations (TMR_IO_Y_BF16): y and the residual are bf16, moved as dwords of two
+      // columns; the LDS-DMA engine's forwards carry this epilogue (gemm16_fwd_inf16.hip)
+      TMR_CHECK_ARG(use16(a, MODE_FWD),
+                    "tmr_conv2d_fwd_fused: a bf16 output (TMR_IO_Y_BF16) needs bf16 x and w "
+                    "(TMR_IO_X_BF16 | TMR_IO_W_BF16), channels and row strides multiples of 8");
+      TMR_CHECK_ARG(a.N % 2 == 0 && a.ldc % 2 == 0 && (((uintptr_t)a.C | (uintptr_t)a.res) & 3) == 0,
+                    "tmr_conv2d_fwd_fused: a bf16 output needs even channels / y_ld and 4-B "
+                    "aligned y and residual");
+      a.Cbytes = clamp_bytes_e(span((long)c.n * c.ho * c.wo, a.ldc, c.k), 2);
+    }
     rc = launch_gemm<MODE_FWD>(a, al, 1, stream);
     if (rc) return rc;
   }

@@ -219,7 +219,11 @@ __device__ __forceinline__ void tap_split(const GemmArgs& a, int tap, int& ri, i
 // Epilogue, batched form: branch-free buffer accesses over C's extent, each chunk of ER rows
 // issuing all of its loads before consuming any (latency-bound short-reduction GEMMs).  Used by
 // gemm_kernel's 64x64 tiles and by every tile of the LDS-DMA engine.
-template <int MODE, int BM, int BN, int WM, int WN, int TM, int TN>
+// INF16 (compile time; the bf16-activation inference forwards, gemm16_fwd_inf16.hip): the FWD
+// inference epilogue with a bf16 residual and a bf16 y -- fmaf(acc, scale, shift), + residual,
+// ReLU as the fp32 form, then one RNE rounding at the store; the residual is read as the packed
+// bf16 pairs of the store form in use.
+template <int MODE, int BM, int BN, int WM, int WN, int TM, int TN, int INF16 = 0>
 __device__ __forceinline__ void epilogue_batched(const GemmArgs& a, floatx16 (&acc)[TM][TN],
                                                  float* smem, int m0, int n0, int split) {
   const int tid = threadIdx.x;
@@ -289,7 +293,7 @@ __device__ __forceinline__ void epilogue_batched(const GemmArgs& a, floatx16 (&a
     const uint32_t w = odd ? ((mine << 16) | got) : ((got << 16) | mine);
     __builtin_amdgcn_raw_buffer_store_b32(w, rC, poff(off_r, off_r1), 0, 0);
   };
-  if (c16) {   // the stored (rounded) values are the ones the BN statistics describe
+  if (!INF16 && c16) {   // the stored (rounded) values are the ones the BN statistics describe
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -490,6 +494,87 @@ __device__ __forceinline__ void epilogue_batched(const GemmArgs& a, floatx16 (&a
   // the same row, so the 32 lanes of a half-wave write one row's 64 columns = 128 contiguous bytes
   // (the pair form below, kept for tiles with an odd TN, writes 64-B halves of two rows).  Same
   // values, same bytes.  a.c16 == 2 selects it (every bf16-output forward, gemm_conv.hip).
+  // the fp32 inference epilogue's arithmetic on one element (rv: its residual, 0 without one)
+  auto inf_val = [&](float accv, int j, float rv) -> float {
+    float v = fmaf(accv, scj[j], bvals[j]);
+    v = fmaf(a.beta, 0.f, v);
+    v += rv;
+    if (a.relu) v = fmaxf(v, 0.f);
+    return v;
+  };
+  if constexpr (INF16 != 0) {
+    constexpr int JP = TN / 2 > 0 ? TN / 2 : 1;
+    if (c16w) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int r0 = 0; r0 < 16; r0 += ER) {
+          uint32_t so[ER][JP], rw[ER][JP];
+#pragma unroll
+          for (int r = 0; r < ER; ++r) {
+            const uint32_t ro = row_off(i, r0 + r);
+#pragma unroll
+            for (int jp = 0; jp < TN / 2; ++jp) {
+              const int scol = odd ? col0 - 1 + 32 * (2 * jp + 1) : col0 + 64 * jp;
+              so[r][jp] = (ro >= OOB || scol >= a.N) ? OOB : (ro >> 1) + (uint32_t)scol * 2u;
+              // the residual dword of the pair this lane stores: (scol, scol + 1) of this row
+              rw[r][jp] = has_res ? __builtin_amdgcn_raw_buffer_load_b32(rR, so[r][jp], 0, 0) : 0u;
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < ER; ++r)
+#pragma unroll
+            for (int jp = 0; jp < TN / 2; ++jp) {
+              // even lane holds (block 2jp: cols 2k, 2k+1), odd lane (block 2jp+1: cols 2k, 2k+1);
+              // each lane's own column of both blocks: one half of its dword, one of its neighbour's
+              const uint32_t nw = swap1(rw[r][jp]);
+              const float r0v = odd ? __uint_as_float(nw & 0xffff0000u) : __uint_as_float(rw[r][jp] << 16);
+              const float r1v = odd ? __uint_as_float(rw[r][jp] & 0xffff0000u) : __uint_as_float(nw << 16);
+              const float v0 = inf_val(acc[i][2 * jp][r0 + r], 2 * jp, r0v);
+              const float v1 = inf_val(acc[i][2 * jp + 1][r0 + r], 2 * jp + 1, r1v);
+              const float mine = odd ? v1 : v0;
+              const float send = odd ? v0 : v1;
+              const uint32_t got = swap1((uint32_t)bf16_bits(send));
+              const uint32_t mb = (uint32_t)bf16_bits(mine);
+              const uint32_t w = odd ? ((mb << 16) | got) : ((got << 16) | mb);
+              __builtin_amdgcn_raw_buffer_store_b32(w, rC, so[r][jp], 0, 0);
+            }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      return;
+    }
+    // pair form (odd TN): the even lane moves the pair of row r, the odd lane that of row r + 1
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int r0 = 0; r0 < 16; r0 += ER) {
+        uint32_t off[ER][TN], rw[ER / 2][TN];
+#pragma unroll
+        for (int r = 0; r < ER; ++r) {
+          const uint32_t ro = row_off(i, r0 + r);
+#pragma unroll
+          for (int j = 0; j < TN; ++j) off[r][j] = eoff(ro, j);
+        }
+#pragma unroll
+        for (int rp = 0; rp < ER / 2; ++rp)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            rw[rp][j] = has_res ? __builtin_amdgcn_raw_buffer_load_b32(
+                                      rR, poff(off[2 * rp][j], off[2 * rp + 1][j]), 0, 0)
+                                : 0u;
+#pragma unroll
+        for (int rp = 0; rp < ER / 2; ++rp)
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            float ra, rb;
+            unpair(rw[rp][j], ra, rb);
+            st_pair(inf_val(acc[i][j][r0 + 2 * rp], j, ra), inf_val(acc[i][j][r0 + 2 * rp + 1], j, rb),
+                    off[2 * rp][j], off[2 * rp + 1][j]);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    return;
+  }
   if (c16w) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)

@@ -11,6 +11,11 @@ Reference: ``code/eval/python/test_singlenet_phase_non-local_pretrained_2fc_copy
   *probabilities* (Appendix A of SURVEY.md; weighted when class weights are given), correct
   counts against ``labels[T-1::T]``.  Everything stays on the device until ``result()`` (one
   host transfer per evaluation instead of one ``.item()`` per batch).
+* ``SplitEvaluator`` / ``evaluate_split`` -- a whole split in one pass: the same outputs as the
+  loop above, but every frame is encoded once (gate table + batched recurrence, as
+  ``lfb_build.LFBBuilder``) instead of once per overlapping clip; also the per-epoch validation
+  pass of ``Training TMRNet/train_only_non-local_pretrained.py:786-833``, whose CE-sum on the
+  *logits* (:816) is returned next to the test script's CE-sum on the probabilities.
 * ``save_predictions`` -- the two pickles of :510-521 (``<name>_test_<acc*1e4>_crop_<c>.pkl`` and
   ``..._score.pkl``).
 * ``export_phase`` -- ``export_phase_copy.py``: per video, T-1 leading zeros then the clip
@@ -27,6 +32,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .lfb_build import LFBBuilder, clip_plan, inference_mode, check_activations, shard_range
 
 PHASES = ("Preparation", "CalotTriangleDissection", "ClippingCutting", "GallbladderDissection",
           "GallbladderPackaging", "CleaningCoagulation", "GallbladderRetraction")
@@ -89,6 +95,130 @@ class PhaseEvaluator:
         corrects = int((preds == labels).sum())
         return {"preds": preds, "scores": scores, "labels": labels, "loss_sum": loss_sum,
                 "average_loss": loss_sum / n, "corrects": corrects, "accuracy": corrects / n}
+
+
+def clip_label_index(seq_len, video_lengths):
+    """Global frame index whose label scores each valid clip, in valid-start order: the clip
+    starting at frame s is scored against labels[s + T - 1] (labels[(T-1)::T] over the
+    SeqSampler's clip-major index list, :455)."""
+    valid, _, _ = clip_plan(seq_len, video_lengths)
+    return valid + (seq_len - 1)
+
+
+def _finish(res):
+    n = res["preds"].size
+    res["average_loss"] = res["loss_sum"] / n if n else 0.0
+    res["accuracy"] = res["corrects"] / n if n else 0.0
+    return res
+
+
+def merge_results(results):
+    """The result of a split from its shards' results (SplitEvaluator.run with rank / world), in
+    rank order: per-clip arrays concatenated, losses and counts summed.  Pure numpy: how the
+    shards' dicts reach one process is the caller's."""
+    results = list(results)
+    if not results:
+        raise ValueError("merge_results: no shard results")
+    out = {k: np.concatenate([np.asarray(r[k]) for r in results])
+           for k in ("preds", "scores", "labels", "probs", "logits")}
+    for k in ("loss_sum", "logit_loss_sum"):
+        out[k] = float(sum(float(r[k]) for r in results))
+    for k in ("corrects", "frames_encoded", "clips"):
+        out[k] = int(sum(int(r[k]) for r in results))
+    return _finish(out)
+
+
+class SplitEvaluator:
+    """Scores every valid clip of a split, encoding each frame once.
+
+    model: a ``resnet_lstm`` (any backbone / TimeConv variant with activations="fp32"); bank: the
+    split's ``LongFeatureBank``; weight: optional class weights of the criterion; activations:
+    "fp32", or "bf16" for the bf16-activation eval trunk (ResNet-50, precision "bf16").
+    """
+
+    def __init__(self, model, bank, weight=None, activations="fp32", frames_per_launch=640,
+                 clips_per_launch=8192):
+        check_activations(model, activations)
+        self.model = model
+        self.bank = bank
+        self.weight = weight
+        self.activations = activations
+        self.builder = LFBBuilder(model, frames_per_launch, clips_per_launch)
+
+    def run(self, frames, video_lengths, labels, rank=0, world=1):
+        """frames: uint8 (N, H, W, 3) or a ``loader(first, count)`` (as LFBBuilder takes);
+        labels: per-frame labels in global frame order.  rank / world: this call scores a
+        contiguous share of the clips (their frames, halo included, are encoded here); no
+        collective inside -- merge the shards' dicts with ``merge_results``.
+
+        Returns the keys of ``PhaseEvaluator.result()`` in valid-start order (what
+        ``export_phase`` expects) plus probs and logits (clips, K), logit_loss_sum (the training
+        script's validation loss), frames_encoded and clips."""
+        model, bank = self.model, self.bank
+        T = model.seq_len
+        valid, used, grow = clip_plan(T, video_lengths)
+        n_frames = int(np.sum(np.asarray(video_lengths, dtype=np.int64)))
+        labels = torch.as_tensor(labels).reshape(-1).to(torch.int64)
+        if labels.numel() < n_frames:
+            raise ValueError("labels cover %d frames, the videos have %d" % (labels.numel(), n_frames))
+        bvalid = bank.valid.cpu().numpy()
+        if bvalid.shape != valid.shape or not np.array_equal(bvalid, valid):
+            raise ValueError("the bank's valid starts (%d) are not those of these videos at T=%d (%d)"
+                             % (bvalid.size, T, valid.size))
+        dev = self.builder._device()
+        K = model.fc_c.out_features
+        lo, hi = shard_range(valid.size, rank, world)
+        res = {"preds": np.zeros(0, np.int64), "scores": np.zeros(0, np.float32),
+               "labels": np.zeros(0, np.int64), "probs": np.zeros((0, K), np.float32),
+               "logits": np.zeros((0, K), np.float32),
+               "loss_sum": 0.0, "logit_loss_sum": 0.0, "corrects": 0, "frames_encoded": 0,
+               "clips": 0}
+        if hi <= lo:
+            return _finish(res)
+        with torch.no_grad(), inference_mode(model, self.activations):
+            H = model.lstm.hidden_size
+            g_lo, g_hi = int(grow[lo]), int(grow[hi - 1]) + T
+            gates = torch.empty((g_hi - g_lo, 4 * H), device=dev)
+            self.builder.encode(frames, used[g_lo:g_hi], gates)
+            query = torch.empty((hi - lo, H), device=dev)
+            self.builder.recur(gates, grow[lo:hi] - g_lo, query)
+            del gates
+            starts = torch.from_numpy(valid[lo:hi]).to(dev)
+            lab = labels.to(dev)[starts + (T - 1)].contiguous()
+            weight = self.weight.to(dev).contiguous() if self.weight is not None else None
+            C = self.builder.clips_per_launch
+            if hasattr(model, "time_conv"):   # TimeConv reads a dense (nb, L, 512) Lt: <= 1 GiB
+                C = max(1, min(C, (1 << 28) // (bank.lfb_length * H)))
+            preds, scores, probs, lgts, loss, lloss = [], [], [], [], [], []
+            for c0 in range(0, hi - lo, C):
+                nb = min(C, hi - lo - c0)
+                logits = model.clip_head(query[c0:c0 + nb].view(nb, 1, H),
+                                         bank.view(starts[c0:c0 + nb])).contiguous()
+                pr, pmax, pd = ops.softmax_max(logits)
+                lb = lab[c0:c0 + nb]
+                loss.append(ops.ce_sum(pr, lb, weight, want_grad=False)[0].reshape(1))
+                lloss.append(ops.ce_sum(logits, lb, weight, want_grad=False)[0].reshape(1))
+                preds.append(pd); scores.append(pmax); probs.append(pr); lgts.append(logits)
+            res["preds"] = torch.cat(preds).cpu().numpy()
+            res["scores"] = torch.cat(scores).cpu().numpy()
+            res["probs"] = torch.cat(probs).cpu().numpy()
+            res["logits"] = torch.cat(lgts).cpu().numpy()
+            res["labels"] = lab.cpu().numpy()
+            res["loss_sum"] = float(sum(float(v) for v in torch.cat(loss).cpu().numpy()))
+            res["logit_loss_sum"] = float(sum(float(v) for v in torch.cat(lloss).cpu().numpy()))
+        res["corrects"] = int((res["preds"] == res["labels"]).sum())
+        res["frames_encoded"] = g_hi - g_lo
+        res["clips"] = hi - lo
+        return _finish(res)
+
+
+def evaluate_split(model, bank, frames, video_lengths, labels, weight=None, activations="fp32",
+                   rank=0, world=1, frames_per_launch=640, clips_per_launch=8192):
+    """Functional form of SplitEvaluator: res = evaluate_split(model, bank, frames, lengths,
+    labels)."""
+    ev = SplitEvaluator(model, bank, weight=weight, activations=activations,
+                        frames_per_launch=frames_per_launch, clips_per_launch=clips_per_launch)
+    return ev.run(frames, video_lengths, labels, rank=rank, world=world)
 
 
 def prediction_names(model_pure_name, accuracy, crop):

@@ -28,6 +28,7 @@ concatenation), and only the final bank crosses PCIe if the caller asks for it.
 ``save_lfb``/``load_lfb`` keep the reference's on-disk format (a pickled float64 ndarray) next
 to ``.npy``; ``load_lfb`` unpickles only numpy array payloads (restricted unpickler).
 """
+import contextlib
 import io
 import pickle
 
@@ -86,18 +87,59 @@ def _runs(idx):
     return [(int(idx[a]), int(b - a)) for a, b in zip(starts, ends)]
 
 
+def check_activations(model, activations):
+    """Validate the `activations` argument of the per-frame inference paths (LFBBuilder,
+    evaluate.SplitEvaluator): "fp32", or "bf16" -- the bf16-activation eval trunk
+    (ResNet50Share.infer_act16), which exists for a ResNet-50 trunk of precision "bf16"."""
+    if activations not in ("fp32", "bf16"):
+        raise ValueError("activations must be 'fp32' or 'bf16', got %r" % (activations,))
+    if activations == "fp32":
+        return
+    from . import trunk
+    share = model.share
+    if not isinstance(share, trunk.ResNet50Share):
+        raise ValueError("activations='bf16' exists for the ResNet-50 trunk only (%s evaluates "
+                         "with fp32 activations)" % type(share).__name__)
+    if share.precision != "bf16" or not trunk._full16(share.precision):
+        raise ValueError("activations='bf16' needs a model of precision='bf16' with bf16-stored "
+                         "conv operands (got precision=%r)" % (share.precision,))
+
+
+@contextlib.contextmanager
+def inference_mode(model, activations="fp32"):
+    """The model in eval mode, its trunk storing activations as asked; the training flag and the
+    trunk switch are restored on exit, also when the body raises."""
+    check_activations(model, activations)
+    share = model.share
+    was_training = model.training
+    had = getattr(share, "infer_act16", None)
+    model.eval()
+    if had is not None:
+        share.infer_act16 = activations == "bf16"
+    try:
+        yield
+    finally:
+        if had is not None:
+            share.infer_act16 = had
+        model.train(was_training)
+
+
 class LFBBuilder:
     """Builds the (N_valid, 512) bank of a ``resnet_lstm_LFB`` model on its device.
 
     frames: a uint8 (N_frames, Hin, Win, 3) tensor (device or host memory) holding every frame of
     the split in the reference's global frame order, or a callable ``loader(first, count)``
     returning such a tensor for frames [first, first + count) (e.g. a decoder).
+    activations: "fp32", or "bf16" for the bf16-activation eval trunk (check_activations).
     """
 
-    def __init__(self, model_lfb, frames_per_launch=640, clips_per_launch=8192):
+    def __init__(self, model_lfb, frames_per_launch=640, clips_per_launch=8192,
+                 activations="fp32"):
+        check_activations(model_lfb, activations)
         self.model = model_lfb
         self.frames_per_launch = int(frames_per_launch)
         self.clips_per_launch = int(clips_per_launch)
+        self.activations = activations
 
     def _device(self):
         return next(self.model.parameters()).device
@@ -162,9 +204,7 @@ class LFBBuilder:
         """
         model = self.model
         T = model.seq_len
-        was_training = model.training
-        model.eval()
-        try:
+        with inference_mode(model, self.activations):
             valid, used, grow = clip_plan(T, video_lengths)
             dev = self._device()
             H = model.lstm.hidden_size
@@ -182,8 +222,6 @@ class LFBBuilder:
             if world == 1:
                 return part, valid
             return _all_gather_rows(part, valid.size, world), valid
-        finally:
-            model.train(was_training)
 
 
 def _all_gather_rows(part, n, world):

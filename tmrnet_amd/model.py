@@ -145,6 +145,11 @@ class resnet_lstm(nn.Module):  # noqa: N801  (reference class name)
         feat = _frames_to_features(self.share, x)
         self.lstm.flatten_parameters()
         y_seq, _ = self.lstm(feat.view(-1, T, 2048))   # y.view(-1,512)[T-1::T] inside ClipHeadFn
+        return self.clip_head(y_seq, long_feature)
+
+    def clip_head(self, y_seq, long_feature):
+        """The clip branch after the LSTM (ClipHeadFn) on y_seq (B, T', 512), whose last step is
+        the query; evaluate.SplitEvaluator passes the queries alone, (B, 1, 512)."""
         Lt = long_feature
         if hasattr(self, "time_conv"):
             if isinstance(Lt, LFBRows):

@@ -221,24 +221,34 @@ def conv_fwd(x, w_krsc, stride, pad, bias=None, out=None, beta=0.0, c_real=None,
 
 
 def conv_fwd_fused(x, w_krsc, stride, pad, scale, shift, residual=None, relu=True, c_real=None,
-                   pad_w=None, math="fp32"):
+                   pad_w=None, math="fp32", y16=False):
     """Inference conv + BN(running stats) [+ residual] [+ ReLU] in one launch:
-    [relu](conv(x, w_krsc) * scale + shift + residual) -> (N,Ho,Wo,K)."""
+    [relu](conv(x, w_krsc) * scale + shift + residual) -> (N,Ho,Wo,K).
+    y16: bf16 activations (TMR_IO_Y_BF16) -- bf16 x, w and residual in, the result rounded once
+    (RNE) to a bf16 output."""
+    if y16:   # (checked before any library call)
+        if x.dtype != BF16 or w_krsc.dtype != BF16 or math != "bf16":
+            raise RuntimeError("conv_fwd_fused: y16 needs bf16 x and w and math='bf16'")
+        if residual is not None and residual.dtype != BF16:
+            raise RuntimeError("conv_fwd_fused: a bf16 output (y16) takes a bf16 residual, got %s"
+                               % residual.dtype)
     _req_op(x, "x"); _req_op(w_krsc, "w"); _req(scale, "scale"); _req(shift, "shift")
     n, h, w, c = x.shape
     k, r, s, c2 = w_krsc.shape
     assert c == c2, (x.shape, w_krsc.shape)
-    d = conv_desc(n, h, w, c, k, r, s, stride, pad, pad_w, math=math, io=_io(x, w_krsc))
-    out = _empty((n, d.ho, d.wo, k), x)
+    d = conv_desc(n, h, w, c, k, r, s, stride, pad, pad_w, math=math,
+                  io=_io(x, w_krsc) | (IO_Y if y16 else 0))
+    out = _empty((n, d.ho, d.wo, k), x, dtype=BF16 if y16 else f32)
     if residual is not None:
-        _req(residual, "residual")
+        _req(residual, "residual", out.dtype)
         if residual.shape != out.shape:
             raise RuntimeError("conv_fwd_fused: residual %s != output %s"
                                % (tuple(residual.shape), tuple(out.shape)))
     ysz = n * d.ho * d.wo * k
     with _prof("conv_fwd" + _SUFFIX[math], 2.0 * ysz * r * s * (c_real or c),
                (n, h, w, c, k, r, stride),
-               4 * (n * h * w * c + k * r * s * c + ysz * (2 if residual is not None else 1))):
+               (2 if y16 else 4)
+               * (n * h * w * c + k * r * s * c + ysz * (2 if residual is not None else 1))):
         call("tmr_conv2d_fwd_fused", ctypes.byref(d), x, w_krsc, scale, shift, residual, out,
              int(relu), stream_ptr())
     return out

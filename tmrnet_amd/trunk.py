@@ -213,8 +213,15 @@ def _act16(math):
     return _full16(math) and ACT16
 
 
+def _infer16(share):
+    """The bf16-activation inference trunk applies: eval mode, every conv operand bf16 in HBM
+    (_full16) and the opt-in switch ResNet50Share.infer_act16."""
+    return bool(not share.training and _full16(share.precision)
+                and getattr(share, "infer_act16", False))
+
+
 def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None, math="fp32",
-             defer=False, branch=None, nbt=None, dual=False, groups=1):
+             defer=False, branch=None, nbt=None, dual=False, groups=1, y16=False):
     """conv (NHWC implicit GEMM) -> BN -> (+residual) -> (ReLU); returns z.
 
     Train mode only: ``defer`` returns (y, scale, shift) instead of applying the BN -- the
@@ -223,7 +230,8 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
     (y, scale, shift) used as the residual; ``x`` may itself be a deferred (y, scale, shift) of a
     ReLU unit, read through the conv's X-operand prologue.  ``dual`` (block outputs under
     _full16): returns (z fp32, z bf16 copy).  ``groups``: a grouped conv
-    (train mode; ResNeSt's radix-2 3x3, tmr_conv_desc.groups)."""
+    (train mode; ResNeSt's radix-2 3x3, tmr_conv_desc.groups).  ``y16`` (eval mode, bf16
+    activations: ResNet50Share.infer_act16): x and residual bf16, z rounded once to bf16."""
     xpro = None
     if isinstance(x, tuple):
         x, xpro = x[0], (x[1], x[2])
@@ -257,7 +265,7 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
         scale, shift = ops.bn_eval_params(bn.weight.detach(), bn.bias.detach(), bn.running_mean,
                                           bn.running_var, bn.eps)
         return ops.conv_fwd_fused(x, wk, stride, pad, scale, shift, residual, relu, c_real=c,
-                                  math=math)
+                                  math=math, y16=y16)
     # fp32 block outputs on the LDS-DMA path also record their ReLU mask as bits: the dgrad that
     # produces their gradient reads 1 bit instead of z's 4 bytes (mask 3)
     zbits = None
@@ -414,7 +422,7 @@ class TrunkFn(torch.autograd.Function):
     def forward(ctx, x4, share, keep, *params):
         # every conv weight layout of the step in one launch (ops.layout_session)
         with ops.layout_session(share, ("resnet50", share.training, bool(keep),
-                                 share.precision)):
+                                 share.precision, _infer16(share))):
             return TrunkFn._forward(ctx, x4, share, keep, params)
 
     @staticmethod
@@ -427,6 +435,10 @@ class TrunkFn(torch.autograd.Function):
         mt = share.precision
         a16 = training and _act16(mt)            # every activation bf16: no fp32 copies
         f16 = training and _full16(mt) and not a16
+        # eval mode, opt-in (share.infer_act16): every stored activation bf16, rounded once after
+        # BN (+residual) (+ReLU) by the conv's epilogue; the block output is the next block's
+        # operand and identity
+        i16 = _infer16(share)
         if training:
             # bf16 activations: the stem reads an NHWC8 bf16 copy of its input (8-channel
             # pieces: the LDS-DMA engine; exact, the bf16 math rounds x anyway)
@@ -437,6 +449,15 @@ class TrunkFn(torch.autograd.Function):
                                     defer=True, nbt=nbt)
             p, am = ops.maxpool_fwd_bn(y0, sc0, sh0, bf16=f16)
             stem_hw = (y0.shape[1], y0.shape[2])
+        elif i16:
+            # bf16-activation inference: the stem reads the NHWC8 bf16 copy of its input on the
+            # LDS-DMA engine; its bf16 output is already >= 0, so the bf16 maxpool with an
+            # identity BatchNorm is exact
+            z = _conv_bn(ops.nhwc4_to_bf16x8(x4), conv1, bn1, 2, 3, True, training, math=mt,
+                         y16=True)
+            p, am = ops.maxpool_fwd_bn(z, torch.ones_like(bn1.running_mean),
+                                       torch.zeros_like(bn1.running_mean))
+            stem_hw = (z.shape[1], z.shape[2])
         else:
             z = _conv_bn(x4, conv1, bn1, 2, 3, True, training, recs=recs, math=mt, nbt=nbt)
             p, am = ops.maxpool_fwd(z)
@@ -451,14 +472,15 @@ class TrunkFn(torch.autograd.Function):
                 fold = training and FOLD_BN
                 fd16 = a16 and FOLD16
                 z1 = _conv_bn(hx, blk.conv1, blk.bn1, 1, 0, True, training, recs=brec, math=mt,
-                              nbt=nbt,
+                              nbt=nbt, y16=i16,
                               defer=fold or (fd16 and not _direct3_input(blk, hx.shape[2])))
                 z2 = _conv_bn(z1, blk.conv2, blk.bn2, blk.stride, 1, True, training, recs=brec,
-                              math=mt, nbt=nbt, defer=fold or fd16)
+                              math=mt, nbt=nbt, defer=fold or fd16, y16=i16)
                 if blk.downsample is not None:
                     # train: the branch's BN is applied inside the BN3 pass (bn_apply2)
                     idn = _conv_bn(hx, blk.downsample[0], blk.downsample[1], blk.stride, 0, False,
-                                   training, recs=brec, math=mt, defer=training, nbt=nbt)
+                                   training, recs=brec, math=mt, defer=training, nbt=nbt,
+                                   y16=i16)
                 else:
                     if h is None:
                         raise RuntimeError("identity residual of the stem output (no downsample)")
@@ -468,7 +490,7 @@ class TrunkFn(torch.autograd.Function):
                                  recs=brec, math=mt, nbt=nbt, dual=f16)
                 else:
                     h = _conv_bn(z2, blk.conv3, blk.bn3, 1, 0, True, training, residual=idn,
-                                 recs=brec, math=mt, nbt=nbt, dual=f16)
+                                 recs=brec, math=mt, nbt=nbt, dual=f16, y16=i16)
                 h, hx = h if f16 else (h, h)
                 blocks.append((blk, brec))
         feat = ops.avgpool_fwd(h)
@@ -560,6 +582,9 @@ class ResNet50Share(nn.Sequential):
     def __init__(self, indexed=False, precision="fp32"):
         super().__init__()
         self.precision = precision   # conv operand precision: "fp32" | "bf16" (ops.MATH)
+        # eval mode under precision "bf16", opt-in: bf16 activations (TrunkFn._forward i16; the
+        # default keeps every eval path's fp32 activations and bits)
+        self.infer_act16 = False
         mods = (nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False), nn.BatchNorm2d(64),
                 nn.ReLU(inplace=True), nn.MaxPool2d(3, stride=2, padding=1),
                 _make_layer(64, 64, 3, 1), _make_layer(256, 128, 4, 2),
