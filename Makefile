@@ -12,7 +12,7 @@ else
 BUILD := build
 LIB := tmrnet_amd/libtmr.so
 endif
-SRC := $(wildcard tmrnet_amd/csrc/*.hip) tmrnet_amd/csrc/api.cpp
+SRC := $(wildcard tmrnet_amd/csrc/*.hip) tmrnet_amd/csrc/api.cpp tmrnet_amd/csrc/jpeg_host.cpp
 OBJ := $(patsubst tmrnet_amd/csrc/%,$(BUILD)/%.o,$(SRC))
 CFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -Itmrnet_amd/csrc -munsafe-fp-atomics \
           -DTMR_PROLOGUES=$(PROLOGUES) $(EXTRA)
@@ -29,6 +29,11 @@ $(BUILD)/%.hip.o: tmrnet_amd/csrc/%.hip
 $(BUILD)/%.cpp.o: tmrnet_amd/csrc/%.cpp
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(CFLAGS) -MMD -MP -c $< -o $@
+
+# the JPEG entropy decoder is host code only: plain C++, no device pass
+$(BUILD)/jpeg_host.cpp.o: tmrnet_amd/csrc/jpeg_host.cpp
+	@mkdir -p $(BUILD)
+	$(HIPCC) -x c++ -O3 -std=c++17 -fPIC -Iinclude -MMD -MP -c $< -o $@
 
 -include $(OBJ:.o=.d)
 

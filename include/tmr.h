@@ -20,7 +20,11 @@
 #ifndef TMR_H_
 #define TMR_H_
 
+#ifdef TMR_HOST_ONLY /* a unit with no HIP in it (jpeg_host.cpp): the stream is an opaque handle */
+typedef struct ihipStream_t* hipStream_t;
+#else
 #include <hip/hip_runtime.h>
+#endif
 #include <stddef.h>
 #include <stdint.h>
 
@@ -419,6 +423,42 @@ int tmr_resize_u8(const uint8_t* in, int n, int h, int w, uint8_t* tmp, size_t t
                   uint8_t* out, int oh, int ow, const int32_t* bounds_h, const int32_t* k_h,
                   int ksize_h, const int32_t* bounds_v, const int32_t* k_v, int ksize_v, int y0,
                   int y1, hipStream_t stream);
+
+/* ---------------- input pipeline: baseline JPEG decode (jpeg_host.cpp, jpeg.hip) -------- */
+/* pil_loader (:96-99) of a baseline JPEG file, bit-exact to Pillow / libjpeg-turbo's default
+ * decode (islow IDCT, fancy upsampling), split at the entropy decoder.
+ * Host, no GPU (jpeg_host.cpp): the marker parse and the Huffman decode into DCT coefficients.
+ * In scope: SOF0, 8 bit, one scan of all components; one component, or three YCbCr components
+ * sampled 1x1/1x1/1x1 or 2x2/1x1/1x1; 8-bit DQT, DHT, DRI/RSTn; APPn/COM skipped.  Status: 0 ok,
+ * 1 malformed or truncated, 2 well formed but out of scope (decode it with PIL), 3 bad arguments;
+ * the reason is in tmr_last_error().  Every read is checked against len; both entry points are
+ * re-entrant.
+ * Coefficients: int16, natural (de-zigzagged) order, 64 per block; component 0's blocks, then
+ * 1's, then 2's, each in block-raster order over its MCU-padded grid blocks_h[c] x blocks_w[c];
+ * every coefficient is written. */
+#define TMR_JPEG_GRAY 0 /* one component */
+#define TMR_JPEG_444 1  /* YCbCr, chroma at full size */
+#define TMR_JPEG_420 2  /* YCbCr, chroma halved both ways */
+typedef struct tmr_jpeg_info {
+  int32_t width, height;
+  int32_t ncomp;    /* 1 or 3 */
+  int32_t sampling; /* TMR_JPEG_* */
+  int32_t blocks_w[3], blocks_h[3];
+  uint16_t qt[3][64]; /* per component, natural order */
+  uint64_t coef_bytes;
+} tmr_jpeg_info;
+/* Headers up to the scan; also 1 when no marker ends the scan data within len. */
+int tmr_jpeg_probe(const uint8_t* data, size_t len, tmr_jpeg_info* info);
+int tmr_jpeg_entropy_decode(const uint8_t* data, size_t len, tmr_jpeg_info* info, int16_t* coef,
+                            size_t coef_bytes);
+/* Device (jpeg.hip): f frames of one size and sampling class, coef = f x coef_bytes as above,
+ * qt = (f, 3, 64) uint16 -- dequantisation, 8x8 IDCT into uint8 planes in ws, chroma upsampling
+ * and YCbCr -> RGB into out, (out_frames, h, w, 3) uint8 = the input of tmr_resize_u8.  Frame i
+ * is written to out frame out_index[i] (null: i); an index outside [0, out_frames) is skipped. */
+size_t tmr_jpeg_ws_bytes(int f, int h, int w, int sampling);
+int tmr_jpeg_reconstruct(const int16_t* coef, const uint16_t* qt, int f, int h, int w,
+                         int sampling, uint8_t* ws, size_t ws_bytes, uint8_t* out,
+                         const int32_t* out_index, int out_frames, hipStream_t stream);
 
 /* ---------------- pooling (pool_layout.hip) --------------------------------------- */
 /* MaxPool2d(3,2,1) of share.maxpool (train_only_non-local_pretrained.py:207), NHWC */

@@ -1,10 +1,23 @@
-"""Throughput of the frames-from-files stage: tmrnet_amd.frames.load_frames =
-the reference's pil_loader (train_only_non-local_pretrained.py:96-99) in a host thread pool ->
-pinned batch -> HBM -> tmr_resize_u8 (Resize((250, 250)), :336), next to the train step's
-consumption rate.
+"""Throughput of the frames-from-files stage: files -> decoded -> HBM ->
+tmr_resize_u8 (Resize((250, 250)), train_only_non-local_pretrained.py:336), next to the train
+step's consumption rate.
 
-Threads (decode_frames) and worker processes (DecodePool).  Synthetic JPEGs (smooth colour field + noise, quality 95, written to a temp dir) at Cholec80's
-native 854x480 and at a pre-resized 250x250.  Prints one JSON line per (size, workers)."""
+Variants, each at every --workers count:
+  threads    decode_frames: pil_loader (:96-99) in a thread pool into a pinned batch
+  processes  DecodePool: pil_loader in worker processes into a pinned shared-memory batch
+  device     tmrnet_amd.jpeg.DeviceJpegDecoder: entropy decode in threads, the rest in jpeg.hip
+`processes` and `device` submit batch i + 1 before they take batch i (their submit / result
+pairs), `threads` has no such pair and runs batch after batch.
+
+Protocol (DESIGN.md §18's): one warm-up of every variant, then --rounds rounds in which the
+variants run alternately, all in this process tree; per variant the median frames/s to the resized
+device batch and spread = (max - min) / median.  `device` also reports its host pass alone
+(entropy decode into pinned memory, no copy, no kernels) and the time of the reconstruction
+kernels per frame from device events.  The last line compares `device` with `processes` at the
+largest worker count of the same run.
+
+Synthetic JPEGs (smooth colour field + noise, quality 95, written to a temp dir) at Cholec80's
+native 854x480 and at a pre-resized 250x250.  One JSON line per (size, variant, workers)."""
 import argparse
 import json
 import os
@@ -33,50 +46,120 @@ def write_jpegs(d, n, w, h, seed=0):
     return paths
 
 
+class Variant:
+    """One (mode, workers): run(paths, batches) -> the last resized device batch (or host batch
+    without a GPU)."""
+
+    def __init__(self, mode, nw, dev):
+        from tmrnet_amd import frames
+        self.mode, self.nw, self.dev, self.frames = mode, nw, dev, frames
+        self.pool = self.dec = None
+        if mode == "processes":
+            self.pool = frames.DecodePool(workers=nw)
+        elif mode == "device":
+            from tmrnet_amd.jpeg import DeviceJpegDecoder
+            self.dec = DeviceJpegDecoder(workers=nw, device=dev)
+
+    def _finish(self, dev_batch):
+        if tuple(dev_batch.shape[1:3]) == tuple(self.frames.RESIZE):
+            return dev_batch
+        return self.frames.resize_frames(dev_batch)
+
+    def run(self, paths, batches):
+        if self.mode == "threads":
+            for _ in range(batches):
+                out = self.frames.load_frames(paths, device=self.dev, workers=self.nw)
+            return out
+        src = self.pool if self.mode == "processes" else self.dec
+        job = src.submit(paths)
+        for b in range(batches):
+            nxt = src.submit(paths) if b + 1 < batches else None
+            out = self._finish(job.to(self.dev) if self.mode == "processes" else job.result())
+            job = nxt
+        return out
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.close()
+        if self.dec is not None:
+            self.dec.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=640, help="one C2 step's frames per batch")
     ap.add_argument("--batches", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--workers", default="8,16")
     ap.add_argument("--sizes", default="854x480,250x250")
-    ap.add_argument("--modes", default="threads,processes",
-                    help="threads = decode_frames' thread pool; processes = DecodePool workers")
+    ap.add_argument("--modes", default="threads,processes,device")
     args = ap.parse_args()
     import torch
-    from tmrnet_amd import frames
-    dev = torch.device("cuda:0") if torch.cuda.is_available() else None
+    if not torch.cuda.is_available():
+        raise SystemExit("decode_bench: the resized batch lives on the device; no GPU is visible")
+    dev = torch.device("cuda:0")
+    workers = [int(v) for v in args.workers.split(",")]
     for size in args.sizes.split(","):
         w, h = (int(v) for v in size.split("x"))
         with tempfile.TemporaryDirectory() as d:
             paths = write_jpegs(d, args.frames, w, h)
             mb = sum(os.path.getsize(p) for p in paths) / 1e6
-            for mode in args.modes.split(","):
-                for nw in (int(v) for v in args.workers.split(",")):
-                    pool = frames.DecodePool(workers=nw) if mode == "processes" else None
-                    dec = ((lambda ps: pool.decode(ps)) if pool is not None else
-                           (lambda ps: frames.decode_frames(ps, workers=nw)))
-                    dec(paths[:64])   # warm the page cache / the pool's workers
-                    t0 = time.perf_counter()
-                    for _ in range(args.batches):
-                        host = dec(paths)
-                    t_dec = (time.perf_counter() - t0) / args.batches
-                    rec = {"stage": "frames-from-files", "mode": mode, "size": size, "workers": nw,
-                           "frames": args.frames, "jpeg_mb": round(mb, 1),
-                           "decode_frames_per_s": round(args.frames / t_dec, 1)}
-                    if dev is not None:
-                        frames.load_frames(paths[:64], device=dev, workers=nw, pool=pool)
-                        torch.cuda.synchronize()
+            variants = [Variant(m, nw, dev) for m in args.modes.split(",") for nw in workers]
+            try:
+                for v in variants:          # warm: page cache, worker processes, pinned buffers
+                    v.run(paths, 1)
+                torch.cuda.synchronize()
+                rates = {id(v): [] for v in variants}
+                for _ in range(args.rounds):
+                    for v in variants:
                         t0 = time.perf_counter()
-                        for _ in range(args.batches):
-                            out = frames.load_frames(paths, device=dev, workers=nw, pool=pool)
+                        out = v.run(paths, args.batches)
                         torch.cuda.synchronize()
-                        t_all = (time.perf_counter() - t0) / args.batches
+                        dt = time.perf_counter() - t0
                         assert tuple(out.shape) == (args.frames, 250, 250, 3)
-                        rec["load_frames_per_s"] = round(args.frames / t_all, 1)
-                    if pool is not None:
-                        pool.close()
-                    rec["host_cpus"] = len(os.sched_getaffinity(0))
+                        rates[id(v)].append(args.frames * args.batches / dt)
+                summary = {}
+                for v in variants:
+                    r = sorted(rates[id(v)])
+                    med = float(np.median(r))
+                    rec = {"stage": "frames-from-files", "mode": v.mode, "size": size,
+                           "workers": v.nw, "frames": args.frames, "batches": args.batches,
+                           "rounds": args.rounds, "jpeg_mb": round(mb, 1),
+                           "frames_per_s": round(med, 1), "min": round(r[0], 1), "max": round(r[-1], 1),
+                           "spread_pct": round(100 * (r[-1] - r[0]) / med, 2),
+                           "host_cpus": len(os.sched_getaffinity(0))}
+                    if v.dec is not None:
+                        hp = []
+                        for _ in range(args.rounds):
+                            t0 = time.perf_counter()
+                            nbytes = v.dec.host_pass(paths)
+                            hp.append(args.frames / (time.perf_counter() - t0))
+                        rec["host_pass_frames_per_s"] = round(float(np.median(hp)), 1)
+                        rec["upload_bytes_per_frame"] = nbytes // args.frames
+                        v.dec.kernel_events = []
+                        for _ in range(args.rounds):
+                            v.dec.decode(paths)
+                        torch.cuda.synchronize()
+                        ms = [a.elapsed_time(b) for a, b in v.dec.kernel_events]
+                        v.dec.kernel_events = None
+                        rec["kernels_us_per_frame"] = round(1e3 * float(np.median(ms)) / args.frames, 3)
+                        rec["device_frames"] = v.dec.stats["device"]
+                        rec["fallback_frames"] = v.dec.stats["fallback"]
+                    summary[(v.mode, v.nw)] = rec
                     print(json.dumps(rec), flush=True)
+                top = max(workers)
+                a, b = summary.get(("device", top)), summary.get(("processes", top))
+                if a and b:
+                    gain = 100 * (a["frames_per_s"] / b["frames_per_s"] - 1)
+                    noise = max(a["spread_pct"], b["spread_pct"])
+                    print(json.dumps({"stage": "frames-from-files", "size": size, "workers": top,
+                                      "device_over_processes_pct": round(gain, 2),
+                                      "larger_spread_pct": noise,
+                                      "verdict": "gain" if gain > noise else
+                                                 ("loss" if -gain > noise else "no difference")}), flush=True)
+            finally:
+                for v in variants:
+                    v.close()
 
 
 if __name__ == "__main__":

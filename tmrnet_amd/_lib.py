@@ -43,6 +43,17 @@ class NLBlockPtrs(ctypes.Structure):
     """tmr_nlblock_weights / tmr_nlblock_grads: ten device pointers in NLBlock parameter order."""
     _fields_ = [(n, ctypes.c_void_p) for n in _NL_FIELDS]
 
+
+class JpegInfo(ctypes.Structure):
+    """tmr_jpeg_info: what the headers of a baseline JPEG say (tmr_jpeg_probe)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32),
+                ("sampling", ctypes.c_int32), ("blocks_w", ctypes.c_int32 * 3),
+                ("blocks_h", ctypes.c_int32 * 3), ("qt", (ctypes.c_uint16 * 64) * 3),
+                ("coef_bytes", ctypes.c_uint64)]
+
+
+JP = ctypes.POINTER(JpegInfo)
+
 # name -> argtypes (restype is int unless listed in _RESTYPES)
 SIGNATURES = {
     "tmr_abi_version": [],
@@ -91,6 +102,10 @@ SIGNATURES = {
     "tmr_resize_coeffs": [I, I, P, P, I],
     "tmr_resize_tmp_bytes": [I, I, I, I, I],
     "tmr_resize_u8": [P, I, I, I, P, SZ, P, I, I, P, P, I, P, P, I, I, I, P],
+    "tmr_jpeg_probe": [P, SZ, JP],
+    "tmr_jpeg_entropy_decode": [P, SZ, JP, P, SZ],
+    "tmr_jpeg_ws_bytes": [I, I, I, I],
+    "tmr_jpeg_reconstruct": [P, P, I, I, I, I, P, SZ, P, P, I, P],
     "tmr_gemm_nt": [I, I, I, P, I, P, I, P, P, I, F, P],
     "tmr_gemm_nn": [I, I, I, P, I, P, I, P, I, F, P],
     "tmr_gemm_tn": [I, I, I, P, I, P, I, P, I, F, P],
@@ -193,6 +208,7 @@ _RESTYPES = {
     "tmr_conv2d_wgrad_ws_bytes": SZ,
     "tmr_dgrad_ws_launches": L,
     "tmr_resize_tmp_bytes": SZ,
+    "tmr_jpeg_ws_bytes": SZ,
     "tmr_bn_ws_bytes": SZ,
     "tmr_bn_parts_ws_bytes": SZ,
     "tmr_bn_bwd_parts_ds_ws_bytes": SZ,

@@ -5,12 +5,15 @@ opens each frame file with PIL and converts it to RGB; the DataLoader workers th
 ``transforms.Resize((250, 250))`` (:336) before the per-clip crop / jitter / flip / rotation
 (tmrnet_amd.augment, on the device).  Here:
 
-* decode stays on the host, with the reference's own loader (PIL; libjpeg-turbo for JPEG) -- this
-  image has no GPU JPEG decoder -- either in a thread pool straight into a pinned uint8 batch, or
-  (``DecodePool``) in worker processes that write a shared-memory batch registered as pinned host
-  memory: the thread pool stops scaling at ~2.1k frames/s of 854x480 JPEGs (the GIL-held parts of
-  ``convert`` / ``asarray``; ``profiles/r3/bench_r5a/decode.jsonl``), the reference's own answer
-  is DataLoader worker processes (:682-688);
+* by default decode stays on the host, with the reference's own loader (PIL; libjpeg-turbo for
+  JPEG), either in a thread pool straight into a pinned uint8 batch, or (``DecodePool``) in worker
+  processes that write a shared-memory batch registered as pinned host memory: the thread pool
+  stops scaling at ~2.1k frames/s of 854x480 JPEGs (the GIL-held parts of ``convert`` /
+  ``asarray``; ``profiles/r3/bench_r5a/decode.jsonl``), the reference's own answer is DataLoader
+  worker processes (:682-688);
+* opt-in, ``load_frames(paths, decoder=DeviceJpegDecoder())`` (tmrnet_amd.jpeg) keeps only the
+  entropy decode of baseline JPEGs on the host and reconstructs the pixels on the device
+  (jpeg.hip), bit-identical to ``pil_loader``; other files fall back to ``pil_loader``;
 * the batch is copied to HBM and resized there by ``tmr_resize_u8`` (resize.hip), bit-exact to
   Pillow's ``Image.resize((250, 250), BILINEAR)``: the per-axis fixed-point tables are computed
   once per input size on the host (``tmr_resize_coeffs``, Pillow's double arithmetic) and kept
@@ -264,10 +267,14 @@ def _buf_addr(shm):
     return ctypes.addressof(ctypes.c_char.from_buffer(shm.buf))
 
 
-def load_frames(paths, device="cuda", size=RESIZE, workers=8, pool=None):
+def load_frames(paths, device="cuda", size=RESIZE, workers=8, pool=None, decoder=None):
     """Files -> decoded (host, PIL; threads, or the processes of `pool`, a DecodePool) -> HBM ->
-    resized on the device: (F, 250, 250, 3) uint8."""
-    if pool is not None:
+    resized on the device: (F, 250, 250, 3) uint8.  With `decoder`, a
+    tmrnet_amd.jpeg.DeviceJpegDecoder, the frames are decoded on the decoder's device instead
+    (same bytes; `device`, `workers` and `pool` are then unused)."""
+    if decoder is not None:
+        dev = decoder.decode(paths)
+    elif pool is not None:
         job = pool.submit(paths)
         dev = job.to(device)          # the pool tracks this copy before reusing the slot
     else:
