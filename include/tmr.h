@@ -72,7 +72,7 @@ typedef struct tmr_conv_desc {
                              layout per group block: KRSC (k, r, s, c/G), the transposed copy
                              (G, c/G, r, s, k/G), OIHW gradients (k, c_real, r, s) with c_real the real
                              input channels per group.  BatchNorm partials (stats / parts) keep rows
-                             over all channels.  No operand prologues, no ReLU-mask bits. */
+                             over all channels.  No ReLU-mask bits. */
 } tmr_conv_desc;
 #define TMR_MATH_F32 0
 #define TMR_MATH_BF16 1

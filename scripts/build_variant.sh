@@ -7,7 +7,7 @@ NAME=$1; FLAGS=$2; shift 2
 UNITS=${*:-"gemm16_dgrad_bf16 gemm16_dgrad_f32 gemm16_dpar_bf16 gemm16_dpar_f32"}
 D=build_var/$NAME
 mkdir -p $D
-CF="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude -Itmrnet_amd/csrc -munsafe-fp-atomics -DTMR_PROLOGUES=0"
+CF="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude -Itmrnet_amd/csrc -munsafe-fp-atomics"
 pids=()
 for u in $UNITS; do
   /opt/rocm/bin/hipcc $CF $FLAGS -c tmrnet_amd/csrc/$u.hip -o $D/$u.hip.o -Rpass-analysis=kernel-resource-usage \

@@ -41,10 +41,6 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--stats", action="store_true",
                     help="forward with the fused BatchNorm-statistics epilogue (as the train step)")
-    ap.add_argument("--pro", action="store_true",
-                    help="operand prologues as the folded train step uses them: BN+ReLU on the X "
-                         "operand (fwd, wgrad) and the BN backward on dY (dgrad, wgrad), every "
-                         "conv but the stem")
     ap.add_argument("--math", choices=["fp32", "bf16"], default="fp32",
                     help="conv operand precision (bf16 = the C4/C5 configs)")
     ap.add_argument("--io16", action="store_true",
@@ -99,10 +95,6 @@ def main():
                 wdg = wk
         elif args.wt32 and cin != 3:
             wdg, wt = ops.weight_to_crsk(torch.randn(cout, cs, r, r, device=dev), bf16=False), True
-        xpro = dpro = None
-        if args.pro and cin != 3:
-            xpro = (torch.rand(cs, device=dev) + 0.5, torch.randn(cs, device=dev) * 0.1)
-            dpro = (torch.randn_like(y), torch.randn(3, cout, device=dev))
         dx = torch.empty(n, h, w, cs, device=dev)
         if args.bnbwd and cin != 3:
             yb, zb = torch.randn_like(dx), torch.rand_like(dx) - 0.3
@@ -111,18 +103,18 @@ def main():
             if kind == "dgrad" and cin == 3:
                 continue
             mt = args.math
-            fn = {"fwd": (lambda: ops.conv_fwd_bnstats(x, wk, st, pad, c_real=cin, xpro=xpro,
-                                                       math=mt, y16=args.y16))
-                  if (args.stats or xpro is not None or args.y16)
+            fn = {"fwd": (lambda: ops.conv_fwd_bnstats(x, wk, st, pad, c_real=cin, math=mt,
+                                                       y16=args.y16))
+                  if (args.stats or args.y16)
                   else (lambda: ops.conv_fwd(x, wk, st, pad, out=y, math=mt)),
                   "dgrad": (lambda: ops.conv_dgrad_bnbwd(dy, wdg, (h, w), st, pad, yb, meanb, 1,
                                                          z=zb, out=dx, beta=args.dgrad_beta,
                                                          math=mt, wt=wt))
                   if args.bnbwd else
                   (lambda: ops.conv_dgrad(dy, wdg, (h, w), st, pad, out=dx,
-                                          beta=args.dgrad_beta, dpro=dpro, math=mt, wt=wt)),
-                  "wgrad": lambda: ops.conv_wgrad(x, dy, r, r, st, pad, c_real=cin, xpro=xpro,
-                                                  dpro=dpro, math=mt)}[kind]
+                                          beta=args.dgrad_beta, math=mt, wt=wt)),
+                  "wgrad": lambda: ops.conv_wgrad(x, dy, r, r, st, pad, c_real=cin,
+                                                  math=mt)}[kind]
             fn()
             torch.cuda.synchronize()
             e0 = torch.cuda.Event(enable_timing=True)

@@ -33,18 +33,6 @@ def test_library_exports_every_declared_symbol(built):
 def test_python_binding_covers_header(built):
     from tmrnet_amd import _lib
     assert sorted(_lib.SIGNATURES) == header_symbols()
-    assert sorted(_lib.PROLOGUE_SIGNATURES) == header_symbols("tmr_prologue.h")
-
-
-def test_retired_prologues_absent_from_default_library(built):
-    """The operand prologues (include/tmr_prologue.h, measured slower) are an A/B build only:
-    the product library exports none of their entry points and the binding reports them absent."""
-    from tmrnet_amd import _lib
-    out = subprocess.check_output(["nm", "-D", "--defined-only", built]).decode()
-    exported = set(l.split()[-1] for l in out.splitlines() if " T " in l)
-    assert not set(header_symbols("tmr_prologue.h")) & exported
-    if os.path.abspath(_lib.LIB_PATH) == os.path.abspath(built):
-        assert not _lib.has_prologues()
 
 
 def test_library_loads_and_reports_version(built):

@@ -609,124 +609,6 @@ def test_stem_bwd_maxpool_fused(dev):
     assert rel_err(dg, dg_ref) < 1e-5 and rel_err(db, db_ref) < 1e-5
 
 
-@pytest.mark.parametrize("engine", ["lds_dma", "register_staged"])
-def test_bn_fold_bit_identical(dev, engine):
-    """Train step with the BatchNorm folded into the conv loaders (tmr_conv_prologue: BN+ReLU of
-    units 1-2 on the X operand, the BN backward on every dY operand) against the explicit passes
-    (tmr_bn_apply / tmr_bn_bwd_parts / tmr_bn_bwd): same operand values by construction, same
-    GEMM arithmetic -> logits, every gradient and the running statistics bit-identical.  Both
-    sides on the fp32 LDS-DMA engine (prologues applied in LDS, gemm16_kernel PRO), or both on
-    the register-staged engine (TMR_GEMM32=0, read per launch).  The prologues are a retired A/B
-    experiment: this runs against the A/B build (make PROLOGUES=1; TMR_LIB_PATH=
-    tmrnet_amd/libtmr_pro.so) and is skipped on the product library."""
-    import os
-    import tmrnet_amd
-    from tmrnet_amd import trunk, _lib
-    if not _lib.has_prologues():
-        pytest.skip("operand prologues: A/B build only (make PROLOGUES=1, TMR_LIB_PATH)")
-    B, T, L = 2, 5, 7
-    g = torch.Generator().manual_seed(3)
-    frames = torch.randint(0, 256, (B * T, 250, 250, 3), generator=g, dtype=torch.uint8).to(dev)
-    off = torch.randint(0, 27, (B, 2), generator=g, dtype=torch.int32).to(dev)
-    lt = (torch.rand(B, L, 512, generator=g) * 2 - 1).to(dev)
-    labels = torch.randint(0, 7, (B,), generator=g).to(dev)
-    res = {}
-    saved = trunk.FOLD_BN
-    saved_dma, saved_env = trunk.DMA32, os.environ.get("TMR_GEMM32")
-    if engine == "register_staged":
-        trunk.DMA32 = False
-        os.environ["TMR_GEMM32"] = "0"
-    try:
-        for fold in (True, False):
-            trunk.FOLD_BN = fold
-            torch.manual_seed(0)
-            m = tmrnet_amd.resnet_lstm(seq_len=T).to(dev).train()
-            m.nl_block.forced_mask = torch.ones(B, 512, device=dev)
-            m.forced_head_mask = torch.ones(B, 512, device=dev)
-            x4 = ops.crop_normalize(frames, off, T)
-            out = m(x4, lt)
-            tmrnet_amd.CrossEntropyLoss(size_average=False)(out, labels).backward()
-            torch.cuda.synchronize()
-            res[fold] = (out.detach().clone(), {n: p.grad.clone() for n, p in m.named_parameters()},
-                         {n: b.clone() for n, b in m.named_buffers()})
-    finally:
-        trunk.FOLD_BN = saved
-        trunk.DMA32 = saved_dma
-        if saved_env is None:
-            os.environ.pop("TMR_GEMM32", None)
-        else:
-            os.environ["TMR_GEMM32"] = saved_env
-    assert torch.equal(res[True][0], res[False][0])
-    for n in res[True][1]:
-        assert torch.equal(res[True][1][n], res[False][1][n]), n
-    for n in res[True][2]:
-        assert torch.equal(res[True][2][n], res[False][2][n]), n
-
-
-@pytest.mark.parametrize("folds", [("FOLD16",), ("FOLD16DY",), ("FOLD16", "FOLD16DY")])
-def test_bn_fold16_bit_identical(dev, folds):
-    """The bf16 forms (round 5): under the bf16-activation step (FOLD16) the relu(bn1) /
-    relu(bn2) outputs are never written -- conv2 / conv3 read the bf16 pre-BN y through the bf16
-    X-operand prologue of the LDS-DMA engine, forward and wgrad views -- and (FOLD16DY) no
-    BatchNorm backward writes dy -- every conv whose BN output gradient g is bf16 reads g and y
-    through the bf16 dY-operand prologue, dgrad (fused BN-backward epilogues, the accumulating
-    conv1 dgrads included) and wgrad views -- against the explicit bn_apply8_a16 /
-    bn_bwd_apply8_a16 passes: the same rounded operand values by construction, so logits, every
-    gradient and the running statistics bit-identical.  A/B build only (make PROLOGUES=1;
-    TMR_LIB_PATH=tmrnet_amd/libtmr_pro.so), skipped on the product library."""
-    import tmrnet_amd
-    from tmrnet_amd import trunk, _lib
-    if not _lib.has_prologues():
-        pytest.skip("operand prologues: A/B build only (make PROLOGUES=1, TMR_LIB_PATH)")
-    B, T, L = 2, 5, 7
-    g = torch.Generator().manual_seed(4)
-    frames = torch.randint(0, 256, (B * T, 250, 250, 3), generator=g, dtype=torch.uint8).to(dev)
-    off = torch.randint(0, 27, (B, 2), generator=g, dtype=torch.int32).to(dev)
-    lt = (torch.rand(B, L, 512, generator=g) * 2 - 1).to(dev)
-    labels = torch.randint(0, 7, (B,), generator=g).to(dev)
-    res = {}
-    saved = {f: getattr(trunk, f) for f in folds}
-    # the dY prologue really runs: count the coefficient-only BN backwards it takes
-    ncoef = [0]
-    wrapped = {n: getattr(ops, n) for n in ("bn_bwd_coefs", "bn_bwd_coefs_g16")}
-
-    def counting(fn):
-        def f(*a, **k):
-            ncoef[0] += 1
-            return fn(*a, **k)
-        return f
-    try:
-        for n, fn in wrapped.items():
-            setattr(ops, n, counting(fn))
-        for fold in (True, False):
-            for f in folds:
-                setattr(trunk, f, fold)
-            ncoef[0] = 0
-            torch.manual_seed(0)
-            m = tmrnet_amd.resnet_lstm(seq_len=T, precision="bf16").to(dev).train()
-            m.nl_block.forced_mask = torch.ones(B, 512, device=dev)
-            m.forced_head_mask = torch.ones(B, 512, device=dev)
-            x4 = ops.crop_normalize(frames, off, T)
-            out = m(x4, lt)
-            tmrnet_amd.CrossEntropyLoss(size_average=False)(out, labels).backward()
-            torch.cuda.synchronize()
-            res[fold] = (out.detach().clone(), {n: p.grad.clone() for n, p in m.named_parameters()},
-                         {n: b.clone() for n, b in m.named_buffers()})
-            # ResNet-50: bn1 x 16, bn2 x 13 (layer1's conv2 runs direct), bn3 x 15 (not the last
-            # block's: its gradient is fp32), downsample x 4
-            assert ncoef[0] == (48 if fold and "FOLD16DY" in folds else 0), ncoef[0]
-    finally:
-        for f, v in saved.items():
-            setattr(trunk, f, v)
-        for n, fn in wrapped.items():
-            setattr(ops, n, fn)
-    assert torch.equal(res[True][0], res[False][0])
-    for n in res[True][1]:
-        assert torch.equal(res[True][1][n], res[False][1][n]), n
-    for n in res[True][2]:
-        assert torch.equal(res[True][2][n], res[False][2][n]), n
-
-
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("rows,c", [(3 * 56 * 56, 256), (1001, 8), (77, 2048)])
 def test_bn_bwd_parts_ds_op(dev, dtype, rows, c):

@@ -29,13 +29,6 @@ class ConvDesc(ctypes.Structure):
 DP = ctypes.POINTER(ConvDesc)
 
 
-class ConvPrologue(ctypes.Structure):
-    """tmr_conv_prologue: BN(+ReLU) of the X operand / BN backward of the dY operand on load."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("x_scale", "x_shift", "dy_y", "dy_coef")]
-
-
-PP = ctypes.POINTER(ConvPrologue)
-
 _NL_FIELDS = ("w1", "b1", "w2", "b2", "w3", "b3", "ln_w", "ln_b", "w4", "b4")
 
 
@@ -190,18 +183,6 @@ SIGNATURES = {
     "tmr_lstm_cell_fwd": [P, I, P, P, P, I, P, P, I, I, P],
     "tmr_lstm_cell_bwd": [P, I, P, P, P, P, P, P, I, P, I, I, P],
 }
-# include/tmr_prologue.h: the retired operand-prologue experiment, bound only when the loaded
-# library is the A/B build (`make PROLOGUES=1` -> libtmr_pro.so)
-PROLOGUE_SIGNATURES = {
-    "tmr_conv2d_fwd_bnstats_pro": [DP, P, P, P, P, SZ, PP, P],
-    "tmr_conv2d_dgrad_pro": [DP, P, P, P, F, PP, P],
-    "tmr_conv2d_dgrad_bnbwd_pro": [DP, P, P, P, F, P, P, P, P, P, I, P, SZ, PP, P],
-    "tmr_conv2d_wgrad_pro": [DP, P, P, P, I, F, P, SZ, PP, P],
-    "tmr_bn_bwd_coefs": [P, I, P, P, P, P, P, P, I, I, P, SZ, P],
-    "tmr_bn_bwd_coefs_dense": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, P, SZ, P],
-    "tmr_conv2d_dgrad_bnbwd_acc_pro": [DP, P, P, P, F, P, I, P, P, P, P, P, I, P, SZ, PP, P],
-    "tmr_bn_bwd_coefs_g16": [P, P, P, P, P, P, P, P, I, I, P, SZ, P],
-}
 _RESTYPES = {
     "tmr_last_error": ctypes.c_char_p,
     "tmr_clear_error": None,
@@ -238,18 +219,8 @@ def lib():
             fn = getattr(h, name)
             fn.argtypes = args
             fn.restype = _RESTYPES.get(name, ctypes.c_int)
-        for name, args in PROLOGUE_SIGNATURES.items():
-            if hasattr(h, name):
-                fn = getattr(h, name)
-                fn.argtypes = args
-                fn.restype = ctypes.c_int
         _lib = h
     return _lib
-
-
-def has_prologues():
-    """True when the loaded library is the operand-prologue A/B build (include/tmr_prologue.h)."""
-    return all(hasattr(lib(), n) for n in PROLOGUE_SIGNATURES)
 
 
 def exported_symbols():

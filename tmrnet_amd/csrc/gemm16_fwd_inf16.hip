@@ -10,10 +10,10 @@ __global__ __launch_bounds__(64 * WM * WN, (occ16<BM, BN, WM, WN, NST>()))
 void gemm16_inf16_kernel(const GemmArgs a) {
   int bid, split;
   xcd_work(bid, split);   // XCD-aware tile order (gemm_kernel.h)
-  gemm16_body<MODE_FWD, BM, BN, WM, WN, TAPV, 1, 0, 0, NST, 0, 1>(a, bid, split);
+  gemm16_body<MODE_FWD, BM, BN, WM, WN, TAPV, 1, 0, NST, 0, 1>(a, bid, split);
 }
 
-// The launch forms are launch16_cfg's for a bf16 forward without prologue, in the same order: the
+// The launch forms are launch16_cfg's for a bf16 forward, in the same order: the
 // one-stage form of the 4-wave 128x128 / 256x64 tiles and of 256x256 (as 256x128, 8 waves) for one
 // k-tile, the TAPV form for k-tiles spanning taps, else the two-stage form.
 template <int BM, int BN, int WM, int WN>

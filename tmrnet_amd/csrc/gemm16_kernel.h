@@ -524,16 +524,6 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // k = 8s + 2t + hh, one ds_read_b32 each; odd k-rows have their chunks XOR 8 (columns ^ 32), so
 // the two lane halves (rows k, k + 1) read disjoint bank halves.
 //
-// PRO (fp32 form only; GemmArgs::pro): operand prologues -- the BatchNorm that produced an
-// operand applied in LDS, so its output is never written to HBM.  Bit 1, the X operand (FWD A,
-// WGRAD B): x' = relu(fmaf(x, scale[c], shift[c])) (bn_apply_k's arithmetic), 0 where the
-// gather is out of range (the zero padding belongs to the post-ReLU tensor).  Bit 2, the dY
-// operand (DGRAD A, WGRAD A): dy' = fmaf(A[c], g, fmaf(B[c], y, C[c])) (bn_bwd_apply's), with y
-// brought into an LDS scratch image by a second LDS-DMA at g's offsets, 0 out of range.  Each
-// lane transforms the 16-B pieces it issued, after its own LDS-DMA has landed (vmcnt) and
-// before the barrier that publishes the k-tile, so no extra barrier; the coefficient tables
-// are staged in LDS once per workgroup.
-//
 // NST = 1 (FWD launches of one k-tile, K <= BK: the second stage would never be used): one LDS
 // stage -- 32-40 KB instead of 64-80 KB, so three 4-wave workgroups fit a CU instead of one or
 // two: the short-reduction launches are bound by their epilogue's stores, and more workgroups
@@ -545,8 +535,8 @@ constexpr int occ16() {
 }
 
 // the body of one workgroup: output tile `bid` (m-major over the n-tiles), reduction split `split`
-template <int MODE, int BM, int BN, int WM, int WN, int TAPV, int PIPE, int F32, int PRO, int NST,
-          int EPF = 0, int INF16 = 0>
+template <int MODE, int BM, int BN, int WM, int WN, int TAPV, int PIPE, int F32, int NST, int EPF = 0,
+          int INF16 = 0>
 __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, const int split) {
   constexpr uint32_t ES = F32 ? 4u : 2u;   // element bytes
   constexpr int EPC = 16 / ES;             // elements per 16-B chunk
@@ -564,8 +554,7 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
   constexpr int CPRA = BM * (int)ES / 16, CPRB = BN * (int)ES / 16;
   using Frag = typename std::conditional<F32 != 0, f32x4_t, bf16x8>::type;
   constexpr int EPI = WM * BN * 2 * 4;
-  static_assert(NST == 2 || (NST == 1 && MODE != MODE_WGRAD && (PRO & 2) == 0),
-                "one-stage form: FWD / DGRAD, no dY prologue");
+  static_assert(NST == 2 || (NST == 1 && MODE != MODE_WGRAD), "one-stage form: FWD / DGRAD");
   // the DGRAD view's LDS-staged BN-backward epilogue stages the whole tile at once where it fits
   // 70 KB (every dgrad tile but 256x256: a few KB over the two k-tile stages), so the
   // accumulators are dead before its global loads start; else whole wave row-blocks per chunk
@@ -574,17 +563,7 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
   constexpr int SMEM1 = STAGE > EPI ? (STAGE > LDSNEED ? STAGE : LDSNEED) : (EPI > LDSNEED ? EPI : LDSNEED);
   constexpr int SMEM2 = 2 * STAGE > EPI ? 2 * STAGE : EPI;
   constexpr int SMEM = NST == 1 ? SMEM1 : (SMEM2 > LDSNEED ? SMEM2 : LDSNEED);
-  static_assert(!(PRO & 1) || MODE != MODE_DGRAD, "X prologue: FWD / WGRAD views");
-  static_assert(!(PRO & 2) || MODE != MODE_FWD, "dY prologue: DGRAD / WGRAD views");
-  // prologue regions after the stages / epilogue buffer: dY's y image (one stage: each lane reads
-  // back only the pieces it issued), dY coefficients A|B|C, X scale|shift
-  constexpr int YIMG = (PRO & 2) ? ABYTES : 0;
-  constexpr int DCOEF = (PRO & 2) ? 3 * PRO_DMAX * 4 : 0;
-  constexpr int XCOEF = (PRO & 1) ? 2 * PRO_XMAX * 4 : 0;
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM + YIMG + DCOEF + XCOEF];
-  unsigned char* const ysm = smem + SMEM;
-  float* const dcoef = reinterpret_cast<float*>(smem + SMEM + YIMG);
-  float* const xcoef = reinterpret_cast<float*>(smem + SMEM + YIMG + DCOEF);
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -683,12 +662,6 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
     }
   }
 
-  // prologue pieces of the k-tile in flight: in range, first channel of the 4 (A: X or dY,
-  // B: WGRAD's X); set by stage(), consumed by transform() of the same tile
-  bool pokA[PRO ? NIA : 1], pokB[PRO ? NIB : 1];
-  int pcA[PRO ? NIA : 1];
-  const __amdgpu_buffer_rsrc_t rY = make_rsrc((PRO & 2) ? a.pd_y : a.A, a.Abytes);
-
   // ---------------- stage one k-tile into LDS buffer `buf` ----------------
   auto stage = [&](int kt, int buf) {
     const int kb = kbeg + kt * BK;
@@ -722,11 +695,6 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
                         (unsigned)xs < (unsigned)a.Ws;
         const uint32_t off = apix[q] + (uint32_t)((dy * a.Ws + dx) * a.lds + c) * ES;
         glds16(rA, As + 1024 * (wave + NW * q), ok ? off : OOB);
-        if constexpr (PRO != 0) {
-          pokA[q] = ok;
-          pcA[q] = c;
-          if constexpr ((PRO & 2) != 0) glds16(rY, ysm + 1024 * (wave + NW * q), ok ? off : OOB);
-        }
       }
       if constexpr (MODE == MODE_FWD) {
         // B[j][k] = W[co][tap][c]: k-contiguous rows of the KRSC weights
@@ -772,11 +740,6 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
         const bool ok = acok[q] && m < kend;
         const uint32_t off = (uint32_t)m * (uint32_t)a.ldb * ES + aco[q];
         glds16(rA, As + 1024 * (wave + NW * q), ok ? off : OOB);
-        if constexpr ((PRO & 2) != 0) {
-          pokA[q] = ok;
-          pcA[q] = (int)(aco[q] / ES);
-          glds16(rY, ysm + 1024 * (wave + NW * q), ok ? off : OOB);
-        }
       }
       // WGRAD B[k=m][j=(tap,c)] = X[src(m, tap)][c]
 #pragma unroll
@@ -792,113 +755,6 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
                         (unsigned)xs < (unsigned)a.Ws;
         const uint32_t off = (uint32_t)(((int)n * a.Hs + ys) * a.Ws + xs) * (uint32_t)a.lds * ES + bco[q];
         glds16(rB, Bs + 1024 * (wave + NW * q), ok ? off : OOB);
-        if constexpr ((PRO & 1) != 0) pokB[q] = ok;
-      }
-    }
-  };
-
-  // ---------------- operand prologues on this lane's landed pieces of buffer `buf` ----------------
-  auto transform = [&](int buf) {
-    unsigned char* As = smem + buf * STAGE;
-    unsigned char* Bs = As + ABYTES;
-    if constexpr ((PRO & 2) != 0 && F32 == 0) {   // dY = A operand (DGRAD, WGRAD), bf16 pieces
-      // 8 channels c .. c + 7 of the masked gradient g and of y, both stored bf16:
-      // fmaf(A, g, fmaf(B, y, C)) rounded RNE -- bn_bwd_apply8_a16's arithmetic, so the operand
-      // equals the dy that pass would have stored
-#pragma unroll
-      for (int q = 0; q < NIA; ++q) {
-        uint4* p = reinterpret_cast<uint4*>(As + 1024 * (wave + NW * q) + 16 * lane);
-        const uint4 gw = *p;
-        const uint4 yw = *reinterpret_cast<const uint4*>(ysm + 1024 * (wave + NW * q) + 16 * lane);
-        const uint32_t gu[4] = {gw.x, gw.y, gw.z, gw.w}, yu[4] = {yw.x, yw.y, yw.z, yw.w};
-        const int c = pcA[q];
-        uint32_t w[4];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const float4 A4 = *reinterpret_cast<const float4*>(dcoef + c + 4 * h);
-          const float4 B4 = *reinterpret_cast<const float4*>(dcoef + PRO_DMAX + c + 4 * h);
-          const float4 C4 = *reinterpret_cast<const float4*>(dcoef + 2 * PRO_DMAX + c + 4 * h);
-          const float o0 = fmaf(A4.x, __uint_as_float(gu[2 * h] << 16),
-                                fmaf(B4.x, __uint_as_float(yu[2 * h] << 16), C4.x));
-          const float o1 = fmaf(A4.y, __uint_as_float(gu[2 * h] & 0xffff0000u),
-                                fmaf(B4.y, __uint_as_float(yu[2 * h] & 0xffff0000u), C4.y));
-          const float o2 = fmaf(A4.z, __uint_as_float(gu[2 * h + 1] << 16),
-                                fmaf(B4.z, __uint_as_float(yu[2 * h + 1] << 16), C4.z));
-          const float o3 = fmaf(A4.w, __uint_as_float(gu[2 * h + 1] & 0xffff0000u),
-                                fmaf(B4.w, __uint_as_float(yu[2 * h + 1] & 0xffff0000u), C4.w));
-          typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-          const bf16x2_t lo = {(__bf16)o0, (__bf16)o1}, hi = {(__bf16)o2, (__bf16)o3};
-          w[2 * h] = __builtin_bit_cast(uint32_t, lo);
-          w[2 * h + 1] = __builtin_bit_cast(uint32_t, hi);
-        }
-        *p = pokA[q] ? make_uint4(w[0], w[1], w[2], w[3]) : make_uint4(0u, 0u, 0u, 0u);
-      }
-    } else if constexpr ((PRO & 2) != 0) {   // dY = A operand (DGRAD, WGRAD), fp32
-#pragma unroll
-      for (int q = 0; q < NIA; ++q) {
-        float4* p = reinterpret_cast<float4*>(As + 1024 * (wave + NW * q) + 16 * lane);
-        const float4 g = *p;
-        const float4 yv = *reinterpret_cast<const float4*>(ysm + 1024 * (wave + NW * q) + 16 * lane);
-        const int c = pcA[q];
-        const float4 A4 = *reinterpret_cast<const float4*>(dcoef + c);
-        const float4 B4 = *reinterpret_cast<const float4*>(dcoef + PRO_DMAX + c);
-        const float4 C4 = *reinterpret_cast<const float4*>(dcoef + 2 * PRO_DMAX + c);
-        float4 o;
-        o.x = fmaf(A4.x, g.x, fmaf(B4.x, yv.x, C4.x));
-        o.y = fmaf(A4.y, g.y, fmaf(B4.y, yv.y, C4.y));
-        o.z = fmaf(A4.z, g.z, fmaf(B4.z, yv.z, C4.z));
-        o.w = fmaf(A4.w, g.w, fmaf(B4.w, yv.w, C4.w));
-        *p = pokA[q] ? o : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
-    if constexpr ((PRO & 1) != 0) {   // X = A operand (FWD) or B operand (WGRAD)
-      constexpr int NX = MODE == MODE_FWD ? NIA : NIB;
-#pragma unroll
-      for (int q = 0; q < NX; ++q) {
-        unsigned char* img = MODE == MODE_FWD ? As : Bs;
-        int c;
-        bool ok;
-        if constexpr (MODE == MODE_FWD) {
-          c = pcA[q];
-          ok = pokA[q];
-        } else {
-          c = (int)(bco[q] / ES);
-          ok = pokB[q];
-        }
-        if constexpr (F32) {
-          float4* p = reinterpret_cast<float4*>(img + 1024 * (wave + NW * q) + 16 * lane);
-          const float4 v = *p;
-          const float4 sc = *reinterpret_cast<const float4*>(xcoef + c);
-          const float4 sh = *reinterpret_cast<const float4*>(xcoef + PRO_XMAX + c);
-          float4 o;
-          o.x = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f);
-          o.y = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
-          o.z = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f);
-          o.w = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
-          *p = ok ? o : make_float4(0.f, 0.f, 0.f, 0.f);
-        } else {
-          // bf16 piece: 8 channels c .. c + 7 of the stored pre-BN y; relu(fmaf(y, sc, sh))
-          // rounded RNE -- bn_apply8_a16_k's arithmetic, so the operand equals the z it would
-          // have stored
-          uint4* p = reinterpret_cast<uint4*>(img + 1024 * (wave + NW * q) + 16 * lane);
-          const uint4 v = *p;
-          const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-          uint32_t w[4];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const float4 sc = *reinterpret_cast<const float4*>(xcoef + c + 4 * h);
-            const float4 sh = *reinterpret_cast<const float4*>(xcoef + PRO_XMAX + c + 4 * h);
-            const float o0 = fmaxf(fmaf(__uint_as_float(u[2 * h] << 16), sc.x, sh.x), 0.f);
-            const float o1 = fmaxf(fmaf(__uint_as_float(u[2 * h] & 0xffff0000u), sc.y, sh.y), 0.f);
-            const float o2 = fmaxf(fmaf(__uint_as_float(u[2 * h + 1] << 16), sc.z, sh.z), 0.f);
-            const float o3 = fmaxf(fmaf(__uint_as_float(u[2 * h + 1] & 0xffff0000u), sc.w, sh.w), 0.f);
-            typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-            const bf16x2_t lo = {(__bf16)o0, (__bf16)o1}, hi = {(__bf16)o2, (__bf16)o3};
-            w[2 * h] = __builtin_bit_cast(uint32_t, lo);
-            w[2 * h + 1] = __builtin_bit_cast(uint32_t, hi);
-          }
-          *p = ok ? make_uint4(w[0], w[1], w[2], w[3]) : make_uint4(0u, 0u, 0u, 0u);
-        }
       }
     }
   };
@@ -1023,25 +879,6 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
     }
   };
 
-  if constexpr (PRO != 0) {
-    // coefficient tables -> LDS (published by the barrier below, before any transform)
-    if constexpr ((PRO & 2) != 0) {
-      const int cd = MODE == MODE_WGRAD ? a.ldb : a.lds;
-      for (int i = tid; i < cd; i += 64 * NW) {
-        dcoef[i] = a.pd_a[i];
-        dcoef[PRO_DMAX + i] = a.pd_b[i];
-        dcoef[2 * PRO_DMAX + i] = a.pd_c[i];
-      }
-    }
-    if constexpr ((PRO & 1) != 0) {
-      for (int i = tid; i < a.lds; i += 64 * NW) {
-        xcoef[i] = a.px_scale[i];
-        xcoef[PRO_XMAX + i] = a.px_shift[i];
-      }
-    }
-    __syncthreads();
-  }
-
   // ---------------- main loop: two LDS stages ----------------
   // Iteration kt: wait for this wave's pieces of tile kt, barrier (every wave's pieces landed;
   // every wave finished reading the other buffer in iteration kt-1), issue tile kt+1 into the
@@ -1050,7 +887,6 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
     stage(0, 0);
     for (int kt = 0; kt < ntiles; ++kt) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if constexpr (PRO != 0) transform(kt & 1);
       __syncthreads();
       if (kt + 1 < ntiles) stage(kt + 1, (kt + 1) & 1);
       compute(kt & 1);
@@ -1062,7 +898,6 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
       if (kt > 0) __syncthreads();   // every wave's reads of tile kt - 1 done
       stage(kt, 0);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if constexpr (PRO != 0) transform(0);
       __syncthreads();
       compute(0);
     }
@@ -1073,7 +908,6 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
     stage(0, 0);
     for (int kt = 0; kt < ntiles; ++kt) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if constexpr (PRO != 0) transform(kt & 1);
       __syncthreads();
       const int buf = kt & 1;
       Frag a0[TM], b0[TN], a1[TM], b1[TN];
@@ -1107,13 +941,13 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
                                                         n0, split);
 }
 
-template <int MODE, int BM, int BN, int WM, int WN, int TAPV, int PIPE = 1, int F32 = 0, int PRO = 0,
-          int NST = 2, int EPF = 0>
+template <int MODE, int BM, int BN, int WM, int WN, int TAPV, int PIPE = 1, int F32 = 0, int NST = 2,
+          int EPF = 0>
 __global__ __launch_bounds__(64 * WM * WN, (occ16<BM, BN, WM, WN, NST>()))
 void gemm16_kernel(const GemmArgs a) {
   int bid, split;
   xcd_work(bid, split);   // XCD-aware tile order (gemm_kernel.h)
-  gemm16_body<MODE, BM, BN, WM, WN, TAPV, PIPE, F32, PRO, NST, EPF>(a, bid, split);
+  gemm16_body<MODE, BM, BN, WM, WN, TAPV, PIPE, F32, NST, EPF>(a, bid, split);
 }
 
 // Tile w of a GemmPar launch -> (class, tile of that class).  The classes' tiles go out in
@@ -1177,18 +1011,18 @@ void gemm16_par_kernel(const GemmPar p) {
   a.dHW = FastDiv{own(c.dHW.d), own(c.dHW.m), own(c.dHW.s)};
   a.dW = FastDiv{own(c.dW.d), own(c.dW.m), own(c.dW.s)};
   a.bn_part = own(c.bn_part);
-  gemm16_body<MODE_DGRAD, BM, BN, WM, WN, 0, 1, F32, 0, 2, EPF>(a, t, 0);
+  gemm16_body<MODE_DGRAD, BM, BN, WM, WN, 0, 1, F32, 2, EPF>(a, t, 0);
 }
 
 }  // namespace tmrg
 #include "gemm16_ws.h"
 namespace tmrg {
 
-template <int MODE, int BM, int BN, int WM, int WN, int F32, int PRO = 0>
+template <int MODE, int BM, int BN, int WM, int WN, int F32>
 int launch16_cfg(const GemmArgs& a, bool tapv, dim3 grid, hipStream_t st) {
   const dim3 blk(64 * WM * WN);
   // the bf16-activation inference epilogue (bf16 residual / y): its own kernels (gemm16_select.h)
-  if constexpr (MODE == MODE_FWD && F32 == 0 && PRO == 0) {
+  if constexpr (MODE == MODE_FWD && F32 == 0) {
     if (a.c16 && a.scale) return launch16_inf16<BM, BN, WM, WN>(a, tapv, grid, st);
   }
   // one-k-tile bf16 FWD launches on the 4-wave 128x128 / 256x64 tiles: the one-stage form
@@ -1199,10 +1033,10 @@ int launch16_cfg(const GemmArgs& a, bool tapv, dim3 grid, hipStream_t st) {
   // through the one stage, measured no faster: C2 forward family 47.1 -> 46.9 / 47.2 / 47.7 ms,
   // profiles/r5/nst1_f32/; not taken)
   constexpr int kmax = 64;
-  if constexpr (MODE == MODE_FWD && (PRO & 2) == 0 && F32 == 0 && WM * WN == 4 &&
+  if constexpr (MODE == MODE_FWD && F32 == 0 && WM * WN == 4 &&
                 ((BM == 128 && BN == 128) || (BM == 256 && BN == 64))) {
     if (!tapv && a.K > 0 && a.K <= kmax) {
-      hipLaunchKernelGGL((gemm16_kernel<MODE, BM, BN, WM, WN, 0, 1, F32, PRO, 1>), grid, blk, 0, st, a);
+      hipLaunchKernelGGL((gemm16_kernel<MODE, BM, BN, WM, WN, 0, 1, F32, 1>), grid, blk, 0, st, a);
       TMR_CHECK_LAUNCH("gemm16_kernel (one stage)");
       return 0;
     }
@@ -1212,32 +1046,30 @@ int launch16_cfg(const GemmArgs& a, bool tapv, dim3 grid, hipStream_t st) {
   // (one 16-wave 256x256 workgroup fills the register file), so one's epilogue stores overlap
   // the other's loads.  Same BM (the statistics' part rows), same per-wave tiles: bit-identical to
   // the 256x256 launch it replaced.
-  if constexpr (MODE == MODE_FWD && (PRO & 2) == 0 && F32 == 0 && BM == 256 && BN == 256) {
+  if constexpr (MODE == MODE_FWD && F32 == 0 && BM == 256 && BN == 256) {
     if (!tapv && a.K > 0 && a.K <= kmax) {
       const dim3 g2((unsigned)(cdiv(a.M, 256) * cdiv(a.N, 128)), grid.y, 1);
-      hipLaunchKernelGGL((gemm16_kernel<MODE, 256, 128, 4, 2, 0, 1, F32, PRO, 1>), g2, dim3(512), 0, st, a);
+      hipLaunchKernelGGL((gemm16_kernel<MODE, 256, 128, 4, 2, 0, 1, F32, 1>), g2, dim3(512), 0, st, a);
       TMR_CHECK_LAUNCH("gemm16_kernel (one stage, 256x128)");
       return 0;
     }
   }
   // the fused BN-backward dgrads of the 4-wave tiles in their compile-time epilogue form
   // (EpiForm: bf16 step EPF 1, fp32 step EPF 2)
-  constexpr bool FORMS = MODE == MODE_DGRAD && PRO == 0 && TMR_EPI_FORMS &&
+  constexpr bool FORMS = MODE == MODE_DGRAD && TMR_EPI_FORMS &&
                          (WM * WN == 4 || (WM * WN == 8 && TMR_EPI_LATE_F > 0));
   if constexpr (FORMS) {
     const int f = a.bn_part != nullptr ? epi_form(a) : 0;
     if (f == (F32 ? 2 : 1)) {
       if (tapv)
-        hipLaunchKernelGGL((gemm16_kernel<MODE, BM, BN, WM, WN, 1, 1, F32, 0, 2, F32 ? 2 : 1>), grid, blk, 0, st, a);
+        hipLaunchKernelGGL((gemm16_kernel<MODE, BM, BN, WM, WN, 1, 1, F32, 2, F32 ? 2 : 1>), grid, blk, 0, st, a);
       else
-        hipLaunchKernelGGL((gemm16_kernel<MODE, BM, BN, WM, WN, 0, 1, F32, 0, 2, F32 ? 2 : 1>), grid, blk, 0, st, a);
+        hipLaunchKernelGGL((gemm16_kernel<MODE, BM, BN, WM, WN, 0, 1, F32, 2, F32 ? 2 : 1>), grid, blk, 0, st, a);
       TMR_CHECK_LAUNCH("gemm16_kernel (dgrad epilogue form)");
       return 0;
     }
   }
-  if constexpr (PRO != 0) {   // one tap per k-tile (pro32_ok)
-    hipLaunchKernelGGL((gemm16_kernel<MODE, BM, BN, WM, WN, 0, 1, F32, PRO>), grid, blk, 0, st, a);
-  } else if (tapv) {
+  if (tapv) {
     hipLaunchKernelGGL((gemm16_kernel<MODE, BM, BN, WM, WN, 1, 1, F32>), grid, blk, 0, st, a);
   } else {
     hipLaunchKernelGGL((gemm16_kernel<MODE, BM, BN, WM, WN, 0, 1, F32>), grid, blk, 0, st, a);
@@ -1246,22 +1078,20 @@ int launch16_cfg(const GemmArgs& a, bool tapv, dim3 grid, hipStream_t st) {
   return 0;
 }
 
-template <int MODE, int F32, int PRO>
+template <int MODE, int F32>
 int launch16_switch(const GemmArgs& a, int cfg, bool tapv, dim3 grid, hipStream_t st) {
   switch (cfg) {
-    case 1: return launch16_cfg<MODE, 256, 128, 4, 2, F32, PRO>(a, tapv, grid, st);
-    case 2: return launch16_cfg<MODE, 128, 128, 2, 2, F32, PRO>(a, tapv, grid, st);
-    case 3: return launch16_cfg<MODE, 256, 64, 4, 1, F32, PRO>(a, tapv, grid, st);
-    case 4: return launch16_cfg<MODE, 64, 256, 1, 4, F32, PRO>(a, tapv, grid, st);
-    case 7: return launch16_cfg<MODE, 128, 128, 4, 2, F32, PRO>(a, tapv, grid, st);
-    case 5: return launch16_cfg<MODE, 64, 64, 2, 2, F32, PRO>(a, tapv, grid, st);
+    case 1: return launch16_cfg<MODE, 256, 128, 4, 2, F32>(a, tapv, grid, st);
+    case 2: return launch16_cfg<MODE, 128, 128, 2, 2, F32>(a, tapv, grid, st);
+    case 3: return launch16_cfg<MODE, 256, 64, 4, 1, F32>(a, tapv, grid, st);
+    case 4: return launch16_cfg<MODE, 64, 256, 1, 4, F32>(a, tapv, grid, st);
+    case 7: return launch16_cfg<MODE, 128, 128, 4, 2, F32>(a, tapv, grid, st);
+    case 5: return launch16_cfg<MODE, 64, 64, 2, 2, F32>(a, tapv, grid, st);
+    case 0: return launch16_cfg<MODE, 256, 256, 2, 4, F32>(a, tapv, grid, st);
+    case 6: return launch16_cfg<MODE, 256, 256, 4, 4, F32>(a, tapv, grid, st);
     default: break;
   }
-  if constexpr ((PRO & 2) == 0) {   // 256x256: no room for the dY prologue's LDS (pick_cfg16)
-    if (cfg == 0) return launch16_cfg<MODE, 256, 256, 2, 4, F32, PRO>(a, tapv, grid, st);
-    if (cfg == 6) return launch16_cfg<MODE, 256, 256, 4, 4, F32, PRO>(a, tapv, grid, st);
-  }
-  TMR_CHECK_ARG(false, "gemm16: no tile config %d for prologue %d", cfg, PRO);
+  TMR_CHECK_ARG(false, "gemm16: no tile config %d", cfg);
   return 1;
 }
 
@@ -1278,11 +1108,6 @@ int check16(const GemmArgs& a, int cfg) {
                                              : a.ldb % 4 == 0)),
                 "gemm (fp32 LDS-DMA path): 4-channel pieces, 16-B row strides (view %d)", MODE);
   const Cfg16 c = kCfgs16[cfg];
-  // the BN-partial rows of a fused dgrad were counted with the prologue-free tile rows
-  TMR_CHECK_ARG(MODE != MODE_DGRAD || !a.bn_part || c.bm == kCfgs16[pick_cfg16(a.M, a.N, a.K, MODE, f32)].bm,
-                "gemm (LDS-DMA path): the dY prologue changed a fused dgrad's tile rows");
-  TMR_CHECK_ARG(!a.pro || (f32 ? pro32_ok(a, MODE) : pro16_ok(a, MODE)),
-                "gemm (LDS-DMA path): operand prologue %d not supported here (view %d)", a.pro, MODE);
   // ReLU-mask bits are read by the LDS-staged BN-backward epilogue only (every dgrad tile but
   // 256x256, whose wave row-blocks do not fit the staging buffer)
   TMR_CHECK_ARG(a.bn_part == nullptr || a.bn_mask != 3 ||
@@ -1305,7 +1130,7 @@ int check16(const GemmArgs& a, int cfg) {
 template <int MODE, int F32>
 int launch_gemm16_t(const GemmArgs& a, int splits, hipStream_t st) {
   constexpr bool f32 = F32 != 0;
-  const int cfg = pick_cfg16(a.M, a.N, a.K, MODE, f32, a.pro);
+  const int cfg = pick_cfg16(a.M, a.N, a.K, MODE, f32);
   const Cfg16 c = kCfgs16[cfg];
   if (const int rc = check16<MODE, F32>(a, cfg)) return rc;
   dim3 grid(cdiv(a.M, c.bm) * cdiv(a.N, c.bn), splits, 1);
@@ -1319,19 +1144,7 @@ int launch_gemm16_t(const GemmArgs& a, int splits, hipStream_t st) {
     const int rc = launch_dgrad_ws<F32>(a, cfg, st);
     if (rc >= 0) return rc;
   }
-#if TMR_PROLOGUES
-  // prologue variants (A/B build; fp32 and bf16): FWD X, DGRAD dY, WGRAD dY / dY + X / X
-  if (a.pro) {
-    if constexpr (MODE == MODE_FWD) return launch16_switch<MODE, F32, 1>(a, cfg, tapv, grid, st);
-    if constexpr (MODE == MODE_DGRAD) return launch16_switch<MODE, F32, 2>(a, cfg, tapv, grid, st);
-    if constexpr (MODE == MODE_WGRAD) {
-      if (a.pro == 2) return launch16_switch<MODE, F32, 2>(a, cfg, tapv, grid, st);
-      if (a.pro == 3) return launch16_switch<MODE, F32, 3>(a, cfg, tapv, grid, st);
-      return launch16_switch<MODE, F32, 1>(a, cfg, tapv, grid, st);
-    }
-  }
-#endif
-  return launch16_switch<MODE, F32, 0>(a, cfg, tapv, grid, st);
+  return launch16_switch<MODE, F32>(a, cfg, tapv, grid, st);
 }
 
 template <int MODE, int F32>
@@ -1340,20 +1153,19 @@ int launch_gemm16(const GemmArgs& a, int splits, hipStream_t st) {
 }
 
 // The stride-parity classes of one strided dgrad in one launch (gemm16_par_kernel): every class
-// on the tile config its own launch would use, one tap per k-tile (no TAPV form), no operand
-// prologue.  Returns -1 (nothing launched) when the classes do not qualify: the caller launches
+// on the tile config its own launch would use, one tap per k-tile (no TAPV form).  Returns -1 (nothing launched) when the classes do not qualify: the caller launches
 // them one by one.  Each tile computes exactly what its class's own launch computes.
 template <int F32>
 int launch_gemm16_par(const GemmArgs* as, int n, hipStream_t st) {
   constexpr bool f32 = F32 != 0;
   static_assert(sizeof(GemmPar) <= 4096, "kernel argument size");
   if (n < 2 || n > PAR_MAX) return -1;
-  const int cfg = pick_cfg16(as[0].M, as[0].N, as[0].K, MODE_DGRAD, f32, as[0].pro);
+  const int cfg = pick_cfg16(as[0].M, as[0].N, as[0].K, MODE_DGRAD, f32);
   const int bk = f32 ? 32 : 64;
   for (int i = 0; i < n; ++i) {
     const GemmArgs& a = as[i];
-    if (a.pro || (a.prec == TMR_MATH_F32) != f32 || !use16(a, MODE_DGRAD)) return -1;
-    if (pick_cfg16(a.M, a.N, a.K, MODE_DGRAD, f32, 0) != cfg) return -1;
+    if ((a.prec == TMR_MATH_F32) != f32 || !use16(a, MODE_DGRAD)) return -1;
+    if (pick_cfg16(a.M, a.N, a.K, MODE_DGRAD, f32) != cfg) return -1;
     if (a.ntaps > 1 && ((1 << a.log2C) % bk) != 0) return -1;   // the TAPV form
   }
   switch (cfg) {

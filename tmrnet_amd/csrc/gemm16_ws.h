@@ -440,7 +440,7 @@ __global__ __launch_bounds__(512) void dgrad_ws_kernel(const GemmArgs a) {
 template <int F32>
 int launch_dgrad_ws(const GemmArgs& a, int cfg, hipStream_t st) {
   static const int on = env_int("TMR_DGRAD_WS", TMR_DGRAD_WS);   // A/B of the kernel
-  if (!on || a.io_tiles || a.bn_part == nullptr || a.pro) return -1;
+  if (!on || a.io_tiles || a.bn_part == nullptr) return -1;
   if (kCfgs16[cfg].bm != 128) return -1;
   if (a.ntaps != 1 || a.osy != 1 || a.osx != 1 || a.oyc != 0 || a.oxc != 0 || a.oy0 != 0 ||
       a.ox0 != 0 || a.wr0 != 0 || a.ws0 != 0 || a.sy != 1 || a.sx != 1 ||

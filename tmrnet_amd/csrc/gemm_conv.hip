@@ -5,22 +5,6 @@
 
 using namespace tmrg;
 
-// the prologue forms behind the plain entry points (pro = nullptr); exported as the
-// include/tmr_prologue.h entry points in the A/B build only (TMR_PROLOGUES, end of file)
-static int conv_fwd_bnstats_pro(const tmr_conv_desc* d, const float* x, const float* w_krsc,
-                                float* y, void* stats, size_t stats_bytes,
-                                const tmr_conv_prologue* pro, hipStream_t stream);
-static int conv_dgrad_pro(const tmr_conv_desc* d, const float* dy, const float* w_krsc, float* dx,
-                          float beta, const tmr_conv_prologue* pro, hipStream_t stream);
-static int conv_dgrad_bnbwd_pro(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
-                                float* dx, float beta, const float* y, const float* z,
-                                const float* scale, const float* shift, const float* mean,
-                                int mask, void* parts, size_t parts_bytes,
-                                const tmr_conv_prologue* pro, hipStream_t stream);
-static int conv_wgrad_pro(const tmr_conv_desc* d, const float* x, const float* dy,
-                          float* dw_oihw, int c_real, float beta, float* ws, size_t ws_bytes,
-                          const tmr_conv_prologue* pro, hipStream_t stream);
-
 namespace {
 
 // sum over the split slabs in split order, loads issued 8 at a time (the adds stay in order, so
@@ -138,36 +122,6 @@ void set_grid(GemmArgs& a, int n, int hg, int wg) {
   (void)n;
   a.dHW = make_fastdiv((uint32_t)(hg * wg));
   a.dW = make_fastdiv((uint32_t)wg);
-}
-
-// Operand prologues of one launch (tmr_conv_prologue; GemmArgs::pro).  X: the gathered input
-// operand of FWD / WGRAD; dY: the output-gradient operand of DGRAD / WGRAD, with its y at the
-// launch's frame offset y_off.  Dense layouts only (the offsets of y are dY's).
-int set_prologue(GemmArgs& a, const tmr_conv_prologue* pro, const tmr_conv_desc* d, bool x_ok,
-                 bool dy_ok, long y_off) {
-  if (!pro) return 0;
-#if !TMR_PROLOGUES
-  TMR_CHECK_ARG(false, "tmr_conv2d: operand prologues exist in the A/B build only (TMR_PROLOGUES)");
-#endif
-  if (pro->x_scale || pro->x_shift) {
-    TMR_CHECK_ARG(x_ok, "tmr_conv2d: an X-operand prologue applies to the forward and wgrad views");
-    TMR_CHECK_ARG(pro->x_scale && pro->x_shift, "tmr_conv2d: X prologue needs scale and shift");
-    TMR_CHECK_ARG(!d->x_ld || d->x_ld == d->c, "tmr_conv2d: X prologue needs a dense x (x_ld == c)");
-    a.px_scale = pro->x_scale;
-    a.px_shift = pro->x_shift;
-    a.pro |= 1;
-  }
-  if (pro->dy_y || pro->dy_coef) {
-    TMR_CHECK_ARG(dy_ok, "tmr_conv2d: a dY-operand prologue applies to the dgrad and wgrad views");
-    TMR_CHECK_ARG(pro->dy_y && pro->dy_coef, "tmr_conv2d: dY prologue needs y and coefficients");
-    TMR_CHECK_ARG(!d->y_ld || d->y_ld == d->k, "tmr_conv2d: dY prologue needs a dense dy (y_ld == k)");
-    a.pd_y = adv(pro->dy_y, y_off, esz_dy(d));   // y has dY's element type
-    a.pd_a = pro->dy_coef;
-    a.pd_b = pro->dy_coef + d->k;
-    a.pd_c = pro->dy_coef + 2 * d->k;
-    a.pro |= 2;
-  }
-  return 0;
 }
 
 }  // namespace
@@ -448,22 +402,15 @@ TMR_API int tmr_conv2d_fwd_stats_parts(const tmr_conv_desc* d) {
   return parts;
 }
 
-TMR_API int tmr_conv2d_fwd_bnstats(const tmr_conv_desc* d, const float* x, const float* w_krsc,
-                                   float* y, void* stats, size_t stats_bytes, hipStream_t stream) {
-  return conv_fwd_bnstats_pro(d, x, w_krsc, y, stats, stats_bytes, nullptr, stream);
-}
-
 // stats: partial rows of part_ld columns (this launch's k columns at the pointer)
 static int fwd_bnstats_impl(const tmr_conv_desc* d, const float* x, const float* w_krsc, float* y,
-                            float4* st, int part_ld, const tmr_conv_prologue* pro,
-                            hipStream_t stream) {
+                            float4* st, int part_ld, hipStream_t stream) {
   const int fc = frames_per_launch(d);
   for (int f0 = 0; f0 < d->n; f0 += fc) {
     const tmr_conv_desc c = chunk_desc(d, d->n - f0 < fc ? d->n - f0 : fc);
     GemmArgs a;
     bool al;
     int rc = conv_fwd_args(&c, adv(x, f0 * x_frame(d), esz_x(d)), w_krsc, nullptr, adv(y, f0 * y_frame(d), esz_y(d)), 0.f, a, al);
-    if (!rc) rc = set_prologue(a, pro, d, true, false, 0);
     if (rc) return rc;
     a.stats = st;
     a.part_ld = part_ld;
@@ -474,10 +421,8 @@ static int fwd_bnstats_impl(const tmr_conv_desc* d, const float* x, const float*
   return 0;
 }
 
-static int conv_fwd_bnstats_pro(const tmr_conv_desc* d, const float* x,
-                                const float* w_krsc, float* y, void* stats,
-                                size_t stats_bytes, const tmr_conv_prologue* pro,
-                                hipStream_t stream) {
+TMR_API int tmr_conv2d_fwd_bnstats(const tmr_conv_desc* d, const float* x, const float* w_krsc,
+                                   float* y, void* stats, size_t stats_bytes, hipStream_t stream) {
   TMR_CHECK_ARG(d, "tmr_conv2d_fwd_bnstats: null descriptor");
   TMR_CHECK_ARG(yld_of(d) == d->k, "tmr_conv2d_fwd_bnstats: output must be dense (y_ld == k)");
   const int np = tmr_conv2d_fwd_stats_parts(d);
@@ -485,25 +430,20 @@ static int conv_fwd_bnstats_pro(const tmr_conv_desc* d, const float* x,
   const size_t need = (size_t)np * d->k * sizeof(float4);
   TMR_CHECK_ARG(stats && stats_bytes >= need, "tmr_conv2d_fwd_bnstats: stats buffer too small (%zu < %zu)",
                 stats_bytes, need);
-  // the parts query (above) sized `stats` for the direct stem's row layout: an operand prologue
-  // would route the stem to the engine, which writes a different number of partial rows
-  TMR_CHECK_ARG(!(pro && (stem_direct(d) || stem16_direct(d) || d3_fwd(d) || d3s_fwd(d))),
-                "tmr_conv2d_fwd_bnstats: the 7x7 stem takes no operand prologue");
   if (stem_direct(d))
     return tmr_stem_fwd_bnstats(d->n, d->h, d->w, d->ho, x, w_krsc, y, stats, stream);
   if (stem16_direct(d))
     return tmr_stem16_fwd_bnstats(d->n, d->h, d->w, d->ho, x, w_krsc, 4, y, stats, stream);
-  if (!pro && d3_fwd(d))
+  if (d3_fwd(d))
     return tmr_d3_fwd_bnstats(d->n, d->h, d->w, d->c, d->k, x, w_krsc, y, stats, stream);
-  if (!pro && d3s_fwd(d)) return tmr_d3s_fwd_bnstats(d->n, d->h, x, w_krsc, y, stats, stream);
-  if (ngroups(d) == 1) return fwd_bnstats_impl(d, x, w_krsc, y, (float4*)stats, d->k, pro, stream);
-  TMR_CHECK_ARG(!pro, "tmr_conv2d_fwd_bnstats: operand prologues take no groups");
+  if (d3s_fwd(d)) return tmr_d3s_fwd_bnstats(d->n, d->h, x, w_krsc, y, stats, stream);
+  if (ngroups(d) == 1) return fwd_bnstats_impl(d, x, w_krsc, y, (float4*)stats, d->k, stream);
   tmr_conv_desc g;
   if (group_split(d, g)) return 1;
   for (int i = 0; i < d->groups; ++i) {
     const int rc = fwd_bnstats_impl(&g, adv(x, (long)i * g.c, esz_x(d)), adv(w_krsc, i * group_wsize(&g), esz_w(d)),
                                     adv(y, (long)i * g.k, esz_y(d)), (float4*)stats + (long)i * g.k,
-                                    d->k, nullptr, stream);
+                                    d->k, stream);
     if (rc) return rc;
   }
   return 0;
@@ -523,8 +463,7 @@ struct BnBwdFuse {
 };
 
 static int conv_dgrad_impl(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
-                           float* dx, float beta, hipStream_t stream, BnBwdFuse* fz = nullptr,
-                           const tmr_conv_prologue* pro = nullptr) {
+                           float* dx, float beta, hipStream_t stream, BnBwdFuse* fz = nullptr) {
   TMR_CHECK_ARG(d->math == TMR_MATH_F32 || d->math == TMR_MATH_BF16, "tmr_conv2d: bad math mode %d", d->math);
   const int lk = ilog2_exact(d->k);
   TMR_CHECK_ARG(lk >= 2, "tmr_conv2d_dgrad: output channels %d must be a power of two >= 4", d->k);
@@ -541,7 +480,7 @@ static int conv_dgrad_impl(const tmr_conv_desc* d, const float* dy, const float*
   const int st = d->stride;
   // one GEMM per stride-parity class (ph,pw): rows h = st*y + ph.  Stride 2 on the LDS-DMA
   // engine: the classes go out as one launch (launch_gemm_dgrad_par; TMR_IO_CLASSES: one each)
-  const bool par = st == 2 && !pro && !(d->io & TMR_IO_CLASSES);
+  const bool par = st == 2 && !(d->io & TMR_IO_CLASSES);
   GemmArgs pend[PAR_MAX];
   bool pend_al[PAR_MAX];
   int npend = 0;
@@ -600,13 +539,12 @@ static int conv_dgrad_impl(const tmr_conv_desc* d, const float* dy, const float*
         fz->nparts += nmt;
       }
       bool al = aligned16(dy) && aligned16(w_krsc) && aligned16(dx) && a.lds % 4 == 0;
-      int rc = set_prologue(a, pro, d, false, true, 0);
-      if (!rc && par) {
+      if (par) {
         pend[npend] = a;
         pend_al[npend++] = al;
         continue;
       }
-      if (!rc) rc = launch_gemm<MODE_DGRAD>(a, al, 1, stream);
+      const int rc = launch_gemm<MODE_DGRAD>(a, al, 1, stream);
       if (rc) return rc;
     }
   }
@@ -622,16 +560,8 @@ static int conv_dgrad_impl(const tmr_conv_desc* d, const float* dy, const float*
   return 0;
 }
 
-// the prologue of the frame chunk starting at frame f0 (dY's y moves with dY)
-static tmr_conv_prologue chunk_pro(const tmr_conv_prologue* pro, const tmr_conv_desc* d, int f0) {
-  tmr_conv_prologue p = *pro;
-  if (p.dy_y) p.dy_y = adv(p.dy_y, f0 * y_frame(d), esz_dy(d));
-  return p;
-}
-
 static int dgrad_bnbwd_run(const tmr_conv_desc* d, const float* dy, const float* w_krsc, float* dx,
-                           float beta, BnBwdFuse* fz, hipStream_t stream,
-                           const tmr_conv_prologue* pro = nullptr) {
+                           float beta, BnBwdFuse* fz, hipStream_t stream) {
   const int fc = frames_per_launch(d);
   const long px_frame = (long)d->h * d->w * xld_of(d);   // y / z laid out like dx
   float2* part0 = fz->part;
@@ -644,11 +574,8 @@ static int dgrad_bnbwd_run(const tmr_conv_desc* d, const float* dy, const float*
                           : adv(fz->z, f0 * px_frame, esz_bn(d));
     fc_.nparts = 0;
     if (fz->old) fc_.old = adv(fz->old, f0 * x_frame(d), fz->old16 ? 2 : 4);
-    tmr_conv_prologue pc{};
-    if (pro) pc = chunk_pro(pro, d, f0);
     int rc = conv_dgrad_impl(&c, adv(dy, f0 * y_frame(d), esz_dy(d)), w_krsc,
-                             dx ? adv(dx, f0 * x_frame(d), esz_dx(d)) : nullptr, beta, stream, &fc_,
-                             pro ? &pc : nullptr);
+                             dx ? adv(dx, f0 * x_frame(d), esz_dx(d)) : nullptr, beta, stream, &fc_);
     if (rc) return rc;
     fz->part = fc_.part;
     fz->nparts += fc_.nparts;
@@ -675,30 +602,20 @@ TMR_API int tmr_conv2d_dgrad_bnbwd_parts(const tmr_conv_desc* d) {
   return (int)fz.nparts;
 }
 
-TMR_API int tmr_conv2d_dgrad_bnbwd(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
-                                   float* dx, float beta, const float* y, const float* z,
-                                   const float* scale, const float* shift, const float* mean,
-                                   int mask, void* parts, size_t parts_bytes, hipStream_t stream) {
-  return conv_dgrad_bnbwd_pro(d, dy, w_krsc, dx, beta, y, z, scale, shift, mean, mask, parts,
-                                    parts_bytes, nullptr, stream);
-}
-
 static int dgrad_bnbwd_entry(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
                              float* dx, float beta, const void* dx_old, int old_bf16,
                              const float* y, const float* z, const float* scale,
                              const float* shift, const float* mean, int mask, void* parts,
-                             size_t parts_bytes, const tmr_conv_prologue* pro, hipStream_t stream);
+                             size_t parts_bytes, hipStream_t stream);
 
-static int conv_dgrad_bnbwd_pro(const tmr_conv_desc* d, const float* dy,
-                                const float* w_krsc, float* dx, float beta, const float* y,
-                                const float* z, const float* scale, const float* shift,
-                                const float* mean, int mask, void* parts,
-                                size_t parts_bytes, const tmr_conv_prologue* pro,
-                                hipStream_t stream) {
+TMR_API int tmr_conv2d_dgrad_bnbwd(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
+                                   float* dx, float beta, const float* y, const float* z,
+                                   const float* scale, const float* shift, const float* mean,
+                                   int mask, void* parts, size_t parts_bytes, hipStream_t stream) {
   TMR_CHECK_ARG(d, "tmr_conv2d_dgrad_bnbwd: null descriptor");
   // in place: a bf16 gradient (TMR_IO_G16) accumulates into its own bf16 values
   return dgrad_bnbwd_entry(d, dy, w_krsc, dx, beta, nullptr, (d->io & TMR_IO_G16) ? 1 : 0, y, z,
-                           scale, shift, mean, mask, parts, parts_bytes, pro, stream);
+                           scale, shift, mean, mask, parts, parts_bytes, stream);
 }
 
 TMR_API int tmr_conv2d_dgrad_bnbwd_acc(const tmr_conv_desc* d, const float* dy,
@@ -713,17 +630,17 @@ TMR_API int tmr_conv2d_dgrad_bnbwd_acc(const tmr_conv_desc* d, const float* dy,
                 "tmr_conv2d_dgrad_bnbwd_acc: needs beta != 0, a 16-B aligned old dx and a bf16 "
                 "output (TMR_IO_G16) on the bf16 LDS-DMA engine (TMR_IO_WT_BF16)");
   return dgrad_bnbwd_entry(d, dy, w_krsc, (float*)dx, beta, dx_old, old_bf16 ? 1 : 0, y, z, scale,
-                           shift, mean, mask, parts, parts_bytes, nullptr, stream);
+                           shift, mean, mask, parts, parts_bytes, stream);
 }
 
 static int dgrad_bnbwd_entry(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
                              float* dx, float beta, const void* dx_old, int old_bf16,
                              const float* y, const float* z, const float* scale,
                              const float* shift, const float* mean, int mask, void* parts,
-                             size_t parts_bytes, const tmr_conv_prologue* pro, hipStream_t stream) {
+                             size_t parts_bytes, hipStream_t stream) {
   TMR_CHECK_ARG(xld_of(d) == d->c, "tmr_conv2d_dgrad_bnbwd: dx must be dense (x_ld == c)");
-  TMR_CHECK_ARG(ngroups(d) == 1 || (mask != 3 && !pro),
-                "tmr_conv2d_dgrad_bnbwd: a grouped dgrad takes no ReLU-mask bits / prologue");
+  TMR_CHECK_ARG(ngroups(d) == 1 || mask != 3,
+                "tmr_conv2d_dgrad_bnbwd: a grouped dgrad takes no ReLU-mask bits");
   TMR_CHECK_ARG(y && mean && parts, "tmr_conv2d_dgrad_bnbwd: null y / mean / parts");
   TMR_CHECK_ARG(!(d->io & TMR_IO_G16) ||
                     (d->math == TMR_MATH_BF16 && (d->io & TMR_IO_WT_BF16) &&
@@ -745,8 +662,8 @@ static int dgrad_bnbwd_entry(const tmr_conv_desc* d, const float* dy, const floa
   TMR_CHECK_ARG(np >= 0 && parts_bytes >= (size_t)np * d->c * sizeof(float2),
                 "tmr_conv2d_dgrad_bnbwd: parts buffer too small");
   if (d3_dgrad(d)) {   // (the parts query above counted the direct kernel's rows)
-    TMR_CHECK_ARG(!pro && !dx_old && !((d->io & TMR_IO_G16) && beta != 0.f),
-                  "tmr_conv2d_dgrad_bnbwd: the direct 3x3 dgrad takes no prologue / old dx / "
+    TMR_CHECK_ARG(!dx_old && !((d->io & TMR_IO_G16) && beta != 0.f),
+                  "tmr_conv2d_dgrad_bnbwd: the direct 3x3 dgrad takes no old dx / "
                   "accumulating bf16 gradient");
     return tmr_d3_dgrad_bnbwd(d->n, d->h, d->w, d->c, d->k, dy, w_krsc, dx,
                               (d->io & TMR_IO_G16) ? 1 : 0, beta, y, z, scale, shift, mean, mask,
@@ -776,25 +693,18 @@ static int dgrad_bnbwd_entry(const tmr_conv_desc* d, const float* dy, const floa
   fz.part_ld = d->c;
   fz.old = dx_old;
   fz.old16 = beta != 0.f ? old_bf16 : 0;
-  return dgrad_bnbwd_run(d, dy, w_krsc, dx, beta, &fz, stream, pro);
+  return dgrad_bnbwd_run(d, dy, w_krsc, dx, beta, &fz, stream);
 }
 
 TMR_API int tmr_conv2d_dgrad(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
                              float* dx, float beta, hipStream_t stream) {
-  return conv_dgrad_pro(d, dy, w_krsc, dx, beta, nullptr, stream);
-}
-
-static int conv_dgrad_pro(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
-                          float* dx, float beta, const tmr_conv_prologue* pro,
-                          hipStream_t stream) {
   TMR_CHECK_ARG(d, "tmr_conv2d_dgrad: null descriptor");
   if (ngroups(d) > 1) {
-    TMR_CHECK_ARG(!pro, "tmr_conv2d_dgrad: operand prologues take no groups");
     tmr_conv_desc g;
     if (group_split(d, g)) return 1;
     for (int i = 0; i < d->groups; ++i) {
-      const int rc = conv_dgrad_pro(&g, adv(dy, (long)i * g.k, esz_dy(d)), adv(w_krsc, i * group_wsize(&g), esz_w(d)),
-                                          dx + (long)i * g.c, beta, nullptr, stream);
+      const int rc = tmr_conv2d_dgrad(&g, adv(dy, (long)i * g.k, esz_dy(d)), adv(w_krsc, i * group_wsize(&g), esz_w(d)),
+                                      dx + (long)i * g.c, beta, stream);
       if (rc) return rc;
     }
     return 0;
@@ -802,10 +712,7 @@ static int conv_dgrad_pro(const tmr_conv_desc* d, const float* dy, const float* 
   const int fc = frames_per_launch(d);
   for (int f0 = 0; f0 < d->n; f0 += fc) {
     const tmr_conv_desc c = chunk_desc(d, d->n - f0 < fc ? d->n - f0 : fc);
-    tmr_conv_prologue pc{};
-    if (pro) pc = chunk_pro(pro, d, f0);
-    int rc = conv_dgrad_impl(&c, adv(dy, f0 * y_frame(d), esz_dy(d)), w_krsc, dx + f0 * x_frame(d), beta, stream,
-                             nullptr, pro ? &pc : nullptr);
+    int rc = conv_dgrad_impl(&c, adv(dy, f0 * y_frame(d), esz_dy(d)), w_krsc, dx + f0 * x_frame(d), beta, stream);
     if (rc) return rc;
   }
   return 0;
@@ -884,28 +791,20 @@ TMR_API size_t tmr_conv2d_wgrad_ws_bytes(const tmr_conv_desc* d) {
 
 static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* dy,
                            float* dw_oihw, int c_real, float beta, float* ws, size_t ws_bytes,
-                           hipStream_t stream, const tmr_conv_prologue* pro);
+                           hipStream_t stream);
 
 // frame chunks accumulate into dw in chunk order (beta = 1 after the first): deterministic
 TMR_API int tmr_conv2d_wgrad(const tmr_conv_desc* d, const float* x, const float* dy,
                              float* dw_oihw, int c_real, float beta, float* ws, size_t ws_bytes,
                              hipStream_t stream) {
-  return conv_wgrad_pro(d, x, dy, dw_oihw, c_real, beta, ws, ws_bytes, nullptr, stream);
-}
-
-static int conv_wgrad_pro(const tmr_conv_desc* d, const float* x, const float* dy,
-                          float* dw_oihw, int c_real, float beta, float* ws,
-                          size_t ws_bytes, const tmr_conv_prologue* pro,
-                          hipStream_t stream) {
   TMR_CHECK_ARG(d, "tmr_conv2d_wgrad: null descriptor");
   if (ngroups(d) > 1) {   // c_real = real input channels per group; dw (k, c_real, r, s)
-    TMR_CHECK_ARG(!pro, "tmr_conv2d_wgrad: operand prologues take no groups");
     tmr_conv_desc g;
     if (group_split(d, g)) return 1;
     for (int i = 0; i < d->groups; ++i) {
-      const int rc = conv_wgrad_pro(&g, adv(x, (long)i * g.c, esz_x(d)), adv(dy, (long)i * g.k, esz_dy(d)),
-                                          dw_oihw + (long)i * g.k * c_real * g.r * g.s, c_real,
-                                          beta, ws, ws_bytes, nullptr, stream);
+      const int rc = tmr_conv2d_wgrad(&g, adv(x, (long)i * g.c, esz_x(d)), adv(dy, (long)i * g.k, esz_dy(d)),
+                                      dw_oihw + (long)i * g.k * c_real * g.r * g.s, c_real,
+                                      beta, ws, ws_bytes, stream);
       if (rc) return rc;
     }
     return 0;
@@ -913,10 +812,8 @@ static int conv_wgrad_pro(const tmr_conv_desc* d, const float* x, const float* d
   const int fc = frames_per_launch(d);
   for (int f0 = 0; f0 < d->n; f0 += fc) {
     const tmr_conv_desc c = chunk_desc(d, d->n - f0 < fc ? d->n - f0 : fc);
-    tmr_conv_prologue pc{};
-    if (pro) pc = chunk_pro(pro, d, f0);
     int rc = conv_wgrad_impl(&c, adv(x, f0 * x_frame(d), esz_x(d)), adv(dy, f0 * y_frame(d), esz_dy(d)), dw_oihw, c_real,
-                             f0 == 0 ? beta : 1.f, ws, ws_bytes, stream, pro ? &pc : nullptr);
+                             f0 == 0 ? beta : 1.f, ws, ws_bytes, stream);
     if (rc) return rc;
   }
   return 0;
@@ -924,14 +821,13 @@ static int conv_wgrad_pro(const tmr_conv_desc* d, const float* x, const float* d
 
 static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* dy,
                            float* dw_oihw, int c_real, float beta, float* ws, size_t ws_bytes,
-                           hipStream_t stream, const tmr_conv_prologue* pro) {
+                           hipStream_t stream) {
   TMR_CHECK_ARG(d->math == TMR_MATH_F32 || d->math == TMR_MATH_BF16, "tmr_conv2d: bad math mode %d", d->math);
   const int lc = ilog2_exact(d->c);
   TMR_CHECK_ARG(lc >= 2, "tmr_conv2d_wgrad: stored input channels %d must be a power of two >= 4", d->c);
   TMR_CHECK_ARG(c_real >= 1 && c_real <= d->c, "tmr_conv2d_wgrad: bad c_real %d", c_real);
-  const bool s16 = !pro && c_real == 3 && !(d->io & TMR_IO_ENGINE) &&
-                   stem16_wgrad_geometry(d);
-  if (s16 || (!pro && c_real == 3 && stem_direct(d))) {
+  const bool s16 = c_real == 3 && !(d->io & TMR_IO_ENGINE) && stem16_wgrad_geometry(d);
+  if (s16 || (c_real == 3 && stem_direct(d))) {
     int ns = 0;
     const int rc = s16 ? tmr_stem16_wgrad_slabs(d->n, d->h, d->w, d->ho, x, dy,
                                                 (d->io & TMR_IO_DY_BF16) ? 0 : 1, ws, ws_bytes,
@@ -943,7 +839,7 @@ static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* 
     TMR_CHECK_LAUNCH("wgrad_reduce_taps_kernel");
     return 0;
   }
-  if (!pro && c_real == 3 && d3s_wgrad(d)) {
+  if (c_real == 3 && d3s_wgrad(d)) {
     int ns = 0;
     const int rc = tmr_d3s_wgrad_slabs(d->n, d->h, x, dy, ws, ws_bytes, &ns, stream);
     if (rc) return rc;
@@ -952,7 +848,7 @@ static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* 
     TMR_CHECK_LAUNCH("wgrad_reduce_taps_kernel");
     return 0;
   }
-  if (!pro && d3_wgrad(d)) {
+  if (d3_wgrad(d)) {
     int ns = 0;
     const int rc = tmr_d3_wgrad_slabs(d->n, d->h, d->w, d->c, d->k, x, dy, ws, ws_bytes, &ns, stream);
     if (rc) return rc;
@@ -974,8 +870,7 @@ static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* 
   a.kchunk = kc; a.slab = slab;
   a.Cbytes = clamp_bytes(slab);
   bool al = aligned16(x) && aligned16(dy) && (d->k % 4 == 0) && a.lds % 4 == 0 && a.ldb % 4 == 0;
-  int rc = set_prologue(a, pro, d, true, true, 0);
-  if (!rc) rc = launch_gemm<MODE_WGRAD>(a, al, sp, stream);
+  const int rc = launch_gemm<MODE_WGRAD>(a, al, sp, stream);
   if (rc) return rc;
   const int ntaps = d->r * d->s;
   if (ntaps > 1 && ntaps <= 49) {
@@ -1056,50 +951,3 @@ TMR_API int tmr_gemm_tn(int M, int N, int K, const float* A, int lda, const floa
   return launch_gemm<MODE_WGRAD>(a, al, 1, stream);
 }
 
-#if TMR_PROLOGUES
-TMR_API int tmr_conv2d_fwd_bnstats_pro(const tmr_conv_desc* d, const float* x,
-                                       const float* w_krsc, float* y, void* stats,
-                                       size_t stats_bytes, const tmr_conv_prologue* pro,
-                                       hipStream_t stream) {
-  return conv_fwd_bnstats_pro(d, x, w_krsc, y, stats, stats_bytes, pro, stream);
-}
-
-TMR_API int tmr_conv2d_dgrad_pro(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
-                                 float* dx, float beta, const tmr_conv_prologue* pro,
-                                 hipStream_t stream) {
-  return conv_dgrad_pro(d, dy, w_krsc, dx, beta, pro, stream);
-}
-
-TMR_API int tmr_conv2d_dgrad_bnbwd_pro(const tmr_conv_desc* d, const float* dy,
-                                       const float* w_krsc, float* dx, float beta, const float* y,
-                                       const float* z, const float* scale, const float* shift,
-                                       const float* mean, int mask, void* parts,
-                                       size_t parts_bytes, const tmr_conv_prologue* pro,
-                                       hipStream_t stream) {
-  return conv_dgrad_bnbwd_pro(d, dy, w_krsc, dx, beta, y, z, scale, shift, mean, mask, parts,
-                              parts_bytes, pro, stream);
-}
-
-TMR_API int tmr_conv2d_dgrad_bnbwd_acc_pro(const tmr_conv_desc* d, const float* dy,
-                                           const float* w_krsc, void* dx, float beta,
-                                           const void* dx_old, int old_bf16, const float* y,
-                                           const float* z, const float* scale, const float* shift,
-                                           const float* mean, int mask, void* parts,
-                                           size_t parts_bytes, const tmr_conv_prologue* pro,
-                                           hipStream_t stream) {
-  TMR_CHECK_ARG(d, "tmr_conv2d_dgrad_bnbwd_acc_pro: null descriptor");
-  TMR_CHECK_ARG(beta != 0.f && dx_old && ((uintptr_t)dx_old & 15) == 0 &&
-                    (d->io & TMR_IO_G16) && (d->io & TMR_IO_WT_BF16),
-                "tmr_conv2d_dgrad_bnbwd_acc_pro: needs beta != 0, a 16-B aligned old dx and a bf16 "
-                "output (TMR_IO_G16) on the bf16 LDS-DMA engine (TMR_IO_WT_BF16)");
-  return dgrad_bnbwd_entry(d, dy, w_krsc, (float*)dx, beta, dx_old, old_bf16 ? 1 : 0, y, z, scale,
-                           shift, mean, mask, parts, parts_bytes, pro, stream);
-}
-
-TMR_API int tmr_conv2d_wgrad_pro(const tmr_conv_desc* d, const float* x, const float* dy,
-                                 float* dw_oihw, int c_real, float beta, float* ws,
-                                 size_t ws_bytes, const tmr_conv_prologue* pro,
-                                 hipStream_t stream) {
-  return conv_wgrad_pro(d, x, dy, dw_oihw, c_real, beta, ws, ws_bytes, pro, stream);
-}
-#endif

@@ -25,7 +25,7 @@
 // k-tile).  LDS tiles are k-major ([16][BM+pad]) so each MFMA operand read is a
 // conflict-free ds_read_b32 of 32 consecutive floats per half-wave.
 #include "common.h"
-#include "tmr_prologue.h"
+#include "tmr.h"
 #include <stdlib.h>
 
 namespace tmrg {
@@ -91,20 +91,6 @@ struct GemmArgs {
   // laid out like C: res, bn_y, bn_z; WGRAD: one split slab)
   uint32_t Abytes, Bbytes, Cbytes;
   int prec;  // TMR_MATH_F32 / TMR_MATH_BF16
-  // Operand prologue (tmr_conv_prologue): the BatchNorm that produced an operand, applied while
-  // it is loaded, so its output is never written to HBM.  pro bit 1, the gathered X operand (FWD
-  // A, WGRAD B): x' = relu(fmaf(x, px_scale[c], px_shift[c])) -- the forward BN+ReLU of the unit
-  // that produced x (bn_apply_k's arithmetic) -- and 0 wherever the loader is out of range (the
-  // zero padding belongs to the post-ReLU tensor).  pro bit 2, the dY operand (DGRAD A, WGRAD A):
-  // dy' = fmaf(pd_a[k], g, fmaf(pd_b[k], y, pd_c[k])) with y read from pd_y at g's offset -- the
-  // BatchNorm backward of this conv's BN (bn_bwd_apply's arithmetic), 0 out of range.
-  const float* px_scale;
-  const float* px_shift;
-  const float* pd_y;
-  const float* pd_a;
-  const float* pd_b;
-  const float* pd_c;
-  int pro;
   // bf16-stored operands (bf16 math only): bit 0 = A, bit 1 = B holds bf16 values (2-byte
   // elements; byte extents and offsets in bf16 units).  Exact w.r.t. the fp32-stored bf16 path:
   // the loaders would round those operands to bf16 (RNE) anyway.
@@ -859,21 +845,14 @@ __device__ __forceinline__ void epilogue_guarded(const GemmArgs& a, floatx16 (&a
 //           lane's 8-element k-fragment is one ds_read_b128, v_mfma_f32_32x32x16_bf16.
 //           M/N-contiguous operands are loaded as k-row pairs so the LDS writes are packed
 //           bf16x2 dwords (conflict-free); K-contiguous operands write bf16x4.
-template <int MODE, int BM, int BN, int WM, int WN, int BK, int VAR, int PREC = 0, int PRO = 0,
-          int SAB = 0>
+template <int MODE, int BM, int BN, int WM, int WN, int BK, int VAR, int PREC = 0, int SAB = 0>
 __global__ TMR_GEMM_LB void gemm_kernel(const GemmArgs a) {
   constexpr bool AL = (VAR != 2);
   // bf16-stored operands: 8-byte loads of 4 bf16 per slot (the fp32 slot of 4 elements, half the
   // bytes, no conversion), written to LDS as they are
   constexpr bool SA = (SAB & 1) != 0, SB = (SAB & 2) != 0;
   constexpr uint32_t ESA = SA ? 2u : 4u, ESB = SB ? 2u : 4u;   // element bytes of A / B
-  static_assert(SAB == 0 || (PREC == 1 && PRO == 0 && AL), "bf16 storage: bf16 math, aligned");
-  // operand prologues (GemmArgs::pro): X operand BN+ReLU on A (FWD) or B (WGRAD); dY operand BN
-  // backward on A (DGRAD, WGRAD)
-  constexpr bool PX_A = (PRO & 1) && MODE == MODE_FWD;
-  constexpr bool PX_B = (PRO & 1) && MODE == MODE_WGRAD;
-  constexpr bool PD_A = (PRO & 2) && MODE != MODE_FWD;
-  static_assert(PRO == 0 || VAR == 0, "operand prologues need aligned, tap-uniform k-tiles");
+  static_assert(SAB == 0 || (PREC == 1 && AL), "bf16 storage: bf16 math, aligned");
   constexpr int NT = 64 * WM * WN;       // threads per workgroup
   constexpr int TM = BM / WM / 32;
   constexpr int TN = BN / WN / 32;
@@ -931,8 +910,6 @@ __global__ TMR_GEMM_LB void gemm_kernel(const GemmArgs a) {
 
   const __amdgpu_buffer_rsrc_t rA = make_rsrc(a.A, a.Abytes);
   const __amdgpu_buffer_rsrc_t rB = make_rsrc(a.B, a.Bbytes);
-  // dY prologue: the pre-BN conv output y, laid out exactly like dY (same offsets and extent)
-  const __amdgpu_buffer_rsrc_t rY = make_rsrc(PD_A ? a.pd_y : a.A, a.Abytes);
   const int cmask = (1 << a.log2C) - 1;
 
   // ---- per-thread loader state (fixed across k-tiles) ----
@@ -975,46 +952,9 @@ __global__ TMR_GEMM_LB void gemm_kernel(const GemmArgs a) {
     }
   }
 
-  // prologue constants fixed per thread (the WGRAD operands' columns never change): dY columns
-  // i (output channels) of A, X channels of B
-  // fp32: a thread's M/N-contiguous column is the same for every q (NT is a multiple of the row
-  // width); bf16: one column per k-row pair q / 2
-  constexpr int QA = PREC ? RA / 2 : 1, QB = PREC ? RB / 2 : 1;
-  auto qa = [](int q) { return PREC ? q >> 1 : 0; };
-  float4 wpa[(PD_A && MODE == MODE_WGRAD) ? QA : 1], wpb[(PD_A && MODE == MODE_WGRAD) ? QA : 1],
-      wpc[(PD_A && MODE == MODE_WGRAD) ? QA : 1];
-  float4 xsb[PX_B ? QB : 1], xhb[PX_B ? QB : 1];
-  if constexpr (PD_A && MODE == MODE_WGRAD) {
-#pragma unroll
-    for (int p = 0; p < QA; ++p) {
-      const int i = m0 + mn_c4(PREC ? 2 * p : 0, BM / 4) * 4;
-      const int ii = i < a.M ? i : 0;
-      wpa[p] = *reinterpret_cast<const float4*>(a.pd_a + ii);
-      wpb[p] = *reinterpret_cast<const float4*>(a.pd_b + ii);
-      wpc[p] = *reinterpret_cast<const float4*>(a.pd_c + ii);
-    }
-  }
-  if constexpr (PX_B) {
-#pragma unroll
-    for (int p = 0; p < QB; ++p) {
-      const int q = PREC ? 2 * p : 0;
-      const int c = bjok[q] ? (int)(bcoff[q] / ESB) : 0;
-      xsb[p] = *reinterpret_cast<const float4*>(a.px_scale + c);
-      xhb[p] = *reinterpret_cast<const float4*>(a.px_shift + c);
-    }
-  }
-  // per prefetch set: in-range bits of the prologue operands, the y values of the dY prologue and
-  // the per-k-tile channel coefficients (FWD: scale, shift; DGRAD: A, B, C)
-  struct Aux {
-    uint32_t oka, okb;
-    float4 ya[PD_A ? RA : 1];
-    float4 c0, c1, c2;
-  };
-  Aux aux0{}, aux1{};
-
   float4 ra0[RA], rb0[RB], ra1[RA], rb1[RB];  // two prefetch register sets
 
-  auto load_tile = [&](int kt, float4 (&ra)[RA], float4 (&rb)[RB], Aux& aux) {
+  auto load_tile = [&](int kt, float4 (&ra)[RA], float4 (&rb)[RB]) {
     const int kb = kbeg + kt * BK;
     // ---- A ----
     if (A_KC) {
@@ -1047,23 +987,6 @@ __global__ TMR_GEMM_LB void gemm_kernel(const GemmArgs a) {
         const uint32_t off = apix[q] + (uint32_t)(((dy * a.Ws + dx) * a.lds + c) * (int)ESA);
         if constexpr (SA) ra[q] = ld4h(rA, off, ok);
         else ra[q] = ld4v<AL>(rA, off, ok, kend - k);
-        if constexpr (PD_A) aux.ya[q] = ld4v<AL>(rY, off, ok, kend - k);
-        if constexpr (PX_A || PD_A) {
-          if (q == 0) aux.oka = 0;
-          aux.oka |= (uint32_t)ok << q;
-        }
-      }
-      if constexpr (PX_A || PD_A) {
-        // channel quad of this thread's k-column (KQ divides NT: the same for every q)
-        const int cq = (cbU + (tid % KQ) * 4) & cmask;
-        if constexpr (PX_A) {
-          aux.c0 = *reinterpret_cast<const float4*>(a.px_scale + cq);
-          aux.c1 = *reinterpret_cast<const float4*>(a.px_shift + cq);
-        } else {
-          aux.c0 = *reinterpret_cast<const float4*>(a.pd_a + cq);
-          aux.c1 = *reinterpret_cast<const float4*>(a.pd_b + cq);
-          aux.c2 = *reinterpret_cast<const float4*>(a.pd_c + cq);
-        }
       }
     } else {  // WGRAD: A[i][kk] = dY[m][co], co contiguous
 #pragma unroll
@@ -1074,11 +997,6 @@ __global__ TMR_GEMM_LB void gemm_kernel(const GemmArgs a) {
         const uint32_t off = ((uint32_t)m * (uint32_t)a.ldb + (uint32_t)i) * ESA;
         if constexpr (SA) ra[q] = ld4h(rA, off, ok);
         else ra[q] = ld4v<AL>(rA, off, ok, a.M - i);
-        if constexpr (PD_A) {
-          aux.ya[q] = ld4v<AL>(rY, off, ok, a.M - i);
-          if (q == 0) aux.oka = 0;
-          aux.oka |= (uint32_t)ok << q;
-        }
       }
     }
     // ---- B ----
@@ -1131,10 +1049,6 @@ __global__ TMR_GEMM_LB void gemm_kernel(const GemmArgs a) {
         const int j = n0 + mn_c4(q, BN / 4) * 4;
         if constexpr (SB) rb[q] = ld4h(rB, off, ok);
         else rb[q] = ld4v<AL>(rB, off, ok, a.N - j);
-        if constexpr (PX_B) {
-          if (q == 0) aux.okb = 0;
-          aux.okb |= (uint32_t)ok << q;
-        }
       }
     }
   };
@@ -1200,37 +1114,15 @@ __global__ TMR_GEMM_LB void gemm_kernel(const GemmArgs a) {
     }
   };
 
-  // the prologue transforms, applied when a prefetch set is written to LDS
-  auto relu_aff = [](float4 v, float4 sc, float4 sf, bool ok) -> float4 {
-    float4 o;
-    o.x = fmaxf(fmaf(v.x, sc.x, sf.x), 0.f); o.y = fmaxf(fmaf(v.y, sc.y, sf.y), 0.f);
-    o.z = fmaxf(fmaf(v.z, sc.z, sf.z), 0.f); o.w = fmaxf(fmaf(v.w, sc.w, sf.w), 0.f);
-    return ok ? o : make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  auto bn_bwd4 = [](float4 g, float4 y, float4 A, float4 B, float4 C, bool ok) -> float4 {
-    float4 o;
-    o.x = fmaf(A.x, g.x, fmaf(B.x, y.x, C.x)); o.y = fmaf(A.y, g.y, fmaf(B.y, y.y, C.y));
-    o.z = fmaf(A.z, g.z, fmaf(B.z, y.z, C.z)); o.w = fmaf(A.w, g.w, fmaf(B.w, y.w, C.w));
-    return ok ? o : make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  auto store_tile = [&](int buf, const float4 (&ra_in)[RA], const float4 (&rb_in)[RB],
-                        const Aux& aux) {
+  auto store_tile = [&](int buf, const float4 (&ra_in)[RA], const float4 (&rb_in)[RB]) {
+    // the set is copied to locals first: the fp32 two-set pipeline's kernels keep the register
+    // allocation they were measured with (written from ra_in / rb_in directly they get another
+    // one, with different spills in the 256-row dgrads)
     float4 ra[RA], rb[RB];
 #pragma unroll
-    for (int q = 0; q < RA; ++q) {
-      const bool ok = (aux.oka >> q) & 1u;
-      if constexpr (PX_A) ra[q] = relu_aff(ra_in[q], aux.c0, aux.c1, ok);
-      else if constexpr (PD_A && MODE == MODE_DGRAD)
-        ra[q] = bn_bwd4(ra_in[q], aux.ya[q], aux.c0, aux.c1, aux.c2, ok);
-      else if constexpr (PD_A && MODE == MODE_WGRAD)
-        ra[q] = bn_bwd4(ra_in[q], aux.ya[q], wpa[qa(q)], wpb[qa(q)], wpc[qa(q)], ok);
-      else ra[q] = ra_in[q];
-    }
+    for (int q = 0; q < RA; ++q) ra[q] = ra_in[q];
 #pragma unroll
-    for (int q = 0; q < RB; ++q) {
-      if constexpr (PX_B) rb[q] = relu_aff(rb_in[q], xsb[qa(q)], xhb[qa(q)], (aux.okb >> q) & 1u);
-      else rb[q] = rb_in[q];
-    }
+    for (int q = 0; q < RB; ++q) rb[q] = rb_in[q];
     if (PREC) { store_tile_h(buf, ra, rb); return; }
     float* As = As0 + buf * BK * LDA;
     float* Bs = Bs0 + buf * BK * LDB;
@@ -1327,37 +1219,37 @@ __global__ TMR_GEMM_LB void gemm_kernel(const GemmArgs a) {
   // of range (k >= kend) so they return zeros, and the loop has no load/store branches, which
   // lets the compiler place exact (counted) vmcnt waits.
   // bf16: one register set (BK=32 tiles are twice as many registers per set)
-  constexpr int PFD = (PREC || PRO) ? 1 : TMR_PF;   // prologue variants: one register set
+  constexpr int PFD = PREC ? 1 : TMR_PF;
   if constexpr (PFD == 2) {
     // prefetch distance 2: while the MFMAs run on LDS buffer kt&1, one register set holds
     // tile kt+1 (written to the other buffer after the MFMAs) and the other set has tile
     // kt+2's loads in flight.
     if (ntiles > 0) {
-      load_tile(0, ra0, rb0, aux0);
-      load_tile(1, ra1, rb1, aux1);
-      store_tile(0, ra0, rb0, aux0);
+      load_tile(0, ra0, rb0);
+      load_tile(1, ra1, rb1);
+      store_tile(0, ra0, rb0);
       __syncthreads();
       for (int kt = 0; kt < ntiles; kt += 2) {
-        load_tile(kt + 2, ra0, rb0, aux0);
+        load_tile(kt + 2, ra0, rb0);
         compute(0);
-        store_tile(1, ra1, rb1, aux1);
+        store_tile(1, ra1, rb1);
         __syncthreads();
         if (kt + 1 >= ntiles) break;
-        load_tile(kt + 3, ra1, rb1, aux1);
+        load_tile(kt + 3, ra1, rb1);
         compute(1);
-        store_tile(0, ra0, rb0, aux0);
+        store_tile(0, ra0, rb0);
         __syncthreads();
       }
     }
   } else {
     if (ntiles > 0) {
-      load_tile(0, ra0, rb0, aux0);
-      store_tile(0, ra0, rb0, aux0);
+      load_tile(0, ra0, rb0);
+      store_tile(0, ra0, rb0);
       __syncthreads();
       for (int kt = 0; kt < ntiles; ++kt) {
-        load_tile(kt + 1, ra0, rb0, aux0);
+        load_tile(kt + 1, ra0, rb0);
         compute(kt & 1);
-        store_tile((kt & 1) ^ 1, ra0, rb0, aux0);
+        store_tile((kt & 1) ^ 1, ra0, rb0);
         __syncthreads();
       }
     }
@@ -1381,41 +1273,23 @@ int launch_cfg(const GemmArgs& a, int var, dim3 grid, hipStream_t st) {
     if (a.sab) {   // bf16-stored operands (combinations checked by launch_gemm_t)
       if constexpr (MODE == MODE_FWD) {
         if (a.sab == 2 && var == 1)
-          hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 1, 1, 0, 2>), grid, blk, 0, st, a);
+          hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 1, 1, 2>), grid, blk, 0, st, a);
         else if (a.sab == 2)
-          hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, 1, 0, 2>), grid, blk, 0, st, a);
+          hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, 1, 2>), grid, blk, 0, st, a);
         else
-          hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, 1, 0, 3>), grid, blk, 0, st, a);
+          hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, 1, 3>), grid, blk, 0, st, a);
       } else if constexpr (MODE == MODE_DGRAD) {
-        hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, 1, 0, 3>), grid, blk, 0, st, a);
+        hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, 1, 3>), grid, blk, 0, st, a);
       } else {
         if (a.sab == 1)
-          hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, 1, 0, 1>), grid, blk, 0, st, a);
+          hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, 1, 1>), grid, blk, 0, st, a);
         else
-          hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, 1, 0, 3>), grid, blk, 0, st, a);
+          hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, 1, 3>), grid, blk, 0, st, a);
       }
       TMR_CHECK_LAUNCH("gemm_kernel");
       return 0;
     }
   }
-#if TMR_PROLOGUES
-  if (a.pro) {   // operand prologues (var == 0, checked by launch_gemm_t; A/B build only)
-    if constexpr (MODE == MODE_FWD) {
-      hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, PREC, 1>), grid, blk, 0, st, a);
-    } else if constexpr (MODE == MODE_DGRAD) {
-      hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, PREC, 2>), grid, blk, 0, st, a);
-    } else {
-      if (a.pro == 1)
-        hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, PREC, 1>), grid, blk, 0, st, a);
-      else if (a.pro == 2)
-        hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, PREC, 2>), grid, blk, 0, st, a);
-      else
-        hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 0, PREC, 3>), grid, blk, 0, st, a);
-    }
-    TMR_CHECK_LAUNCH("gemm_kernel");
-    return 0;
-  }
-#endif
   if (var == 2)
     hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, BKT, 2, PREC>), grid, blk, 0, st, a);
   else if (MODE == MODE_FWD && var == 1)
@@ -1494,19 +1368,12 @@ int launch_gemm_t(const GemmArgs& a, bool al, int splits, hipStream_t st) {
   const int bk = a.prec == TMR_MATH_BF16 ? 32 : 16;
   const bool uniform = MODE == MODE_WGRAD || a.ntaps <= 1 || (1 << a.log2C) >= bk;
   int var = al ? (uniform ? 0 : 1) : 2;
-  TMR_CHECK_ARG(!a.pro || var == 0,
-                "gemm: operand prologues need aligned operands with one tap per k-tile");
-  TMR_CHECK_ARG(!a.sab || (a.prec == TMR_MATH_BF16 && !a.pro &&
+  TMR_CHECK_ARG(!a.sab || (a.prec == TMR_MATH_BF16 &&
                            (MODE == MODE_FWD ? ((a.sab == 2 && var <= 1) || (a.sab == 3 && var == 0))
                             : MODE == MODE_DGRAD ? (a.sab == 3 && var == 0)
                                                  : ((a.sab == 1 || a.sab == 3) && var == 0))),
                 "gemm: unsupported bf16-stored operand combination (sab %d, view %d, var %d)",
                 a.sab, MODE, var);
-  TMR_CHECK_ARG(!a.pro || ((a.pro & 1) ? (MODE != MODE_DGRAD && a.px_scale && a.px_shift) : true),
-                "gemm: X-operand prologue needs scale/shift (forward or wgrad view)");
-  TMR_CHECK_ARG(!a.pro || ((a.pro & 2) ? (MODE != MODE_FWD && a.pd_y && a.pd_a && a.pd_b && a.pd_c)
-                                       : true),
-                "gemm: dY-operand prologue needs y and coefficients (dgrad or wgrad view)");
   TMR_CHECK_ARG(uniform || (al && MODE == MODE_FWD),
                 "gemm: per-element taps need aligned channels and the forward view");
   TMR_CHECK_ARG(!a.wt, "gemm: transposed weights (TMR_IO_WT_BF16 / TMR_IO_WT_F32) need the LDS-DMA "

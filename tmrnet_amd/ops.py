@@ -12,7 +12,7 @@ import weakref
 import numpy as np
 import torch
 
-from ._lib import call, query, stream_ptr, has_prologues, ConvDesc, ConvPrologue
+from ._lib import call, query, stream_ptr, ConvDesc
 from . import health
 import ctypes
 
@@ -254,31 +254,9 @@ def conv_fwd_fused(x, w_krsc, stride, pad, scale, shift, residual=None, relu=Tru
     return out
 
 
-def _need_prologues():
-    if not has_prologues():
-        raise RuntimeError("operand prologues (TMR_FOLD_BN=1) are a retired A/B experiment: build "
-                           "`make PROLOGUES=1` and set TMR_LIB_PATH=tmrnet_amd/libtmr_pro.so")
-
-
-def _prologue(xpro=None, dpro=None):
-    """tmr_conv_prologue from (scale, shift) of the X operand's producer BN+ReLU and/or (y, coef)
-    of this conv's BN backward; None when neither is given."""
-    if xpro is None and dpro is None:
-        return None
-    _need_prologues()
-    p = ConvPrologue()
-    if xpro is not None:
-        p.x_scale, p.x_shift = _req(xpro[0], "x_scale").data_ptr(), _req(xpro[1], "x_shift").data_ptr()
-    if dpro is not None:
-        # (y fp32, or bf16 with the bf16 engine's dY prologue: g's element type)
-        p.dy_y, p.dy_coef = _req_op(dpro[0], "dy_y").data_ptr(), _req(dpro[1], "dy_coef").data_ptr()
-    return p
-
-
-def conv_fwd_bnstats(x, w_krsc, stride, pad, c_real=None, pad_w=None, math="fp32", xpro=None,
-                     y16=False, groups=1):
+def conv_fwd_bnstats(x, w_krsc, stride, pad, c_real=None, pad_w=None, math="fp32", y16=False,
+                     groups=1):
     """conv_fwd whose epilogue also emits BatchNorm partials; returns (y, stats, nparts).
-    xpro = (scale, shift): x is a pre-BN tensor read as relu(x*scale + shift) (0 at padding).
     y16: y stored rounded to bf16, the partials describing the rounded values (TMR_IO_Y_BF16).
     groups: a grouped conv (w_krsc (K, R, S, C/groups), torch's grouped layout); c_real is the
     total real input channels."""
@@ -295,13 +273,8 @@ def conv_fwd_bnstats(x, w_krsc, stride, pad, c_real=None, pad_w=None, math="fp32
                (n, h, w, c, k, r, stride),
                _esz(x) * n * h * w * c + _esz(w_krsc) * k * r * s * c2
                + out.element_size() * n * d.ho * d.wo * k + stats.numel() * 4):
-        pro = _prologue(xpro)
-        if pro is None:
-            call("tmr_conv2d_fwd_bnstats", ctypes.byref(d), x, w_krsc, out, stats,
-                 ctypes.c_size_t(stats.numel() * 4), stream_ptr())
-        else:
-            call("tmr_conv2d_fwd_bnstats_pro", ctypes.byref(d), x, w_krsc, out, stats,
-                 ctypes.c_size_t(stats.numel() * 4), ctypes.byref(pro), stream_ptr())
+        call("tmr_conv2d_fwd_bnstats", ctypes.byref(d), x, w_krsc, out, stats,
+             ctypes.c_size_t(stats.numel() * 4), stream_ptr())
     return out, stats, nparts
 
 
@@ -318,10 +291,9 @@ def bn_finalize(stats, nparts, gamma, beta, running_mean, running_var, momentum,
 
 
 def conv_dgrad(dy, w_krsc, in_hw, stride, pad, out=None, beta=0.0, pad_w=None, math="fp32",
-               dpro=None, wt=False, groups=1):
+               wt=False, groups=1):
     """dy (N,Ho,Wo,K), w_krsc (K,R,S,C) -> dx (N,H,W,C) (dy/out may be channel slices).
-    dpro = (y, coef): dy is the masked BN-output gradient g, read as the BN backward
-    A*g + B*y + C (tmr_bn_bwd_coefs).  wt: w_krsc is the transposed copy (C,R,S,K)
+    wt: w_krsc is the transposed copy (C,R,S,K)
     (weight_to_crsk; the LDS-DMA engine: bf16 with bf16 dy, or fp32 with fp32 math)."""
     _req_op(w_krsc, "w")
     n, ho, wo, k = dy.shape
@@ -335,19 +307,14 @@ def conv_dgrad(dy, w_krsc, in_hw, stride, pad, out=None, beta=0.0, pad_w=None, m
     d.x_ld = _nhwc_ld(out, "dx")
     d.y_ld = _nhwc_ld(dy, "dy")
     with _prof("conv_dgrad" + _SUFFIX[math], 2.0 * n * ho * wo * k * r * s * c / groups, (n, h, w, c, k, r, stride),
-               _esz(dy) * n * ho * wo * k * (2 if dpro is not None else 1) + _esz(w_krsc) * w_krsc.numel()
+               _esz(dy) * n * ho * wo * k + _esz(w_krsc) * w_krsc.numel()
                + 4 * n * h * w * c * (2 if beta else 1)):
-        pro = _prologue(None, dpro)
-        if pro is None:
-            call("tmr_conv2d_dgrad", ctypes.byref(d), dy, w_krsc, out, float(beta), stream_ptr())
-        else:
-            call("tmr_conv2d_dgrad_pro", ctypes.byref(d), dy, w_krsc, out, float(beta),
-                 ctypes.byref(pro), stream_ptr())
+        call("tmr_conv2d_dgrad", ctypes.byref(d), dy, w_krsc, out, float(beta), stream_ptr())
     return out
 
 
 def conv_dgrad_bnbwd(dy, w_krsc, in_hw, stride, pad, y, mean, mask, z=None, scale=None,
-                     shift=None, out=None, beta=0.0, math="fp32", dpro=None, wt=False, groups=1,
+                     shift=None, out=None, beta=0.0, math="fp32", wt=False, groups=1,
                      g16=False, old=None):
     """conv_dgrad whose epilogue masks dx by the previous unit's ReLU (mask 1: z > 0, 2:
     y*scale+shift > 0) and emits that unit's BN-backward partials -> (dx_masked, parts, nparts).
@@ -393,29 +360,20 @@ def conv_dgrad_bnbwd(dy, w_krsc, in_hw, stride, pad, y, mean, mask, z=None, scal
         raise RuntimeError("tmr_conv2d_dgrad_bnbwd_parts failed")
     parts = torch.empty((max(nparts, 1), c, 2), dtype=f32, device=dy.device)
     with _prof("conv_dgrad" + _SUFFIX[math], 2.0 * n * ho * wo * k * r * s * c / groups, (n, h, w, c, k, r, stride),
-               _esz(dy) * n * ho * wo * k * (2 if dpro is not None else 1) + _esz(w_krsc) * w_krsc.numel()
+               _esz(dy) * n * ho * wo * k + _esz(w_krsc) * w_krsc.numel()
                + (2 if g16 else 4) * n * h * w * c
                + ((old.element_size() if old is not None else (2 if g16 else 4)) * n * h * w * c
                   if beta else 0)
                + y.element_size() * n * h * w * c * (2 if z is not None and mask != 3 else 1)
                + (n * h * w * c // 8 if mask == 3 else 0)):
-        pro = _prologue(None, dpro)
-        if old is not None and pro is None:
+        if old is not None:
             call("tmr_conv2d_dgrad_bnbwd_acc", ctypes.byref(d), dy, w_krsc, out, float(beta), old,
                  int(old.dtype == BF16), y, z, scale, shift, mean, int(mask), parts,
                  ctypes.c_size_t(parts.numel() * 4), stream_ptr())
-        elif old is not None:
-            call("tmr_conv2d_dgrad_bnbwd_acc_pro", ctypes.byref(d), dy, w_krsc, out, float(beta),
-                 old, int(old.dtype == BF16), y, z, scale, shift, mean, int(mask), parts,
-                 ctypes.c_size_t(parts.numel() * 4), ctypes.byref(pro), stream_ptr())
-        elif pro is None:
+        else:
             call("tmr_conv2d_dgrad_bnbwd", ctypes.byref(d), dy, w_krsc, out, float(beta), y, z,
                  scale, shift, mean, int(mask), parts, ctypes.c_size_t(parts.numel() * 4),
                  stream_ptr())
-        else:
-            call("tmr_conv2d_dgrad_bnbwd_pro", ctypes.byref(d), dy, w_krsc, out, float(beta), y,
-                 z, scale, shift, mean, int(mask), parts, ctypes.c_size_t(parts.numel() * 4),
-                 ctypes.byref(pro), stream_ptr())
     return out, parts, nparts
 
 
@@ -436,53 +394,6 @@ def bn_bwd_maxpool(dyp, am, y, scale, shift, mean, inv, gamma, bf16=False):
     call("tmr_bn_bwd_maxpool_x", dyp, am, n, h, w, ho, wo, y, scale, shift, mean, inv, gamma, dy,
          dgamma, dbeta, c, ws, ctypes.c_size_t(nb), int(bf16), stream_ptr())
     return dy, dgamma, dbeta
-
-
-def bn_bwd_coefs(parts, nparts, mean, inv, gamma, rows):
-    """BN backward coefficients from conv_dgrad_bnbwd partials -> (coef [3][c], dgamma, dbeta);
-    the consumers apply dy = A*g + B*y + C on load (dpro=(y, coef))."""
-    _need_prologues()
-    c = mean.shape[0]
-    coef = _empty((3, c), mean)
-    dgamma = _empty((c,), mean); dbeta = _empty((c,), mean)
-    nb = query("tmr_bn_parts_ws_bytes", int(nparts), c)
-    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=mean.device)
-    call("tmr_bn_bwd_coefs", parts, int(nparts), mean, inv, gamma, coef, dgamma, dbeta, int(rows),
-         c, ws, ctypes.c_size_t(ws.numel() * 8), stream_ptr())
-    return coef, dgamma, dbeta
-
-
-def bn_bwd_coefs_dense(g, y, z, scale, shift, mean, inv, gamma, relu):
-    """BN backward coefficients from the output gradient g itself (one reduction pass over g and
-    y); with relu, g is masked IN PLACE (z > 0, or y*scale+shift > 0 when z is None).
-    -> (coef [3][c], dgamma, dbeta)."""
-    _need_prologues()
-    c = y.shape[-1]
-    rows = y.numel() // c
-    _req(g, "g"); _req(y, "y")
-    coef = _empty((3, c), y)
-    dgamma = _empty((c,), y); dbeta = _empty((c,), y)
-    ws, nb = _bn_ws(rows, c, y.device)
-    call("tmr_bn_bwd_coefs_dense", g, y, z, scale, shift, mean, inv, gamma, coef, dgamma, dbeta,
-         rows, c, int(relu), ws, ctypes.c_size_t(nb), stream_ptr())
-    return coef, dgamma, dbeta
-
-
-def bn_bwd_coefs_g16(g, y, mean, inv, gamma):
-    """BN backward coefficients of a unit without ReLU from its bf16 output gradient g and bf16 y
-    (the downsample BN of the bf16-activation step) -> (coef [3][c], dgamma, dbeta)."""
-    _need_prologues()
-    c = y.shape[-1]
-    rows = y.numel() // c
-    if g.dtype != BF16 or y.dtype != BF16 or g.shape != y.shape:
-        raise RuntimeError("bn_bwd_coefs_g16: g and y must be bf16 tensors of one shape")
-    _req_op(g, "g"); _req_op(y, "y")
-    coef = _empty((3, c), mean)
-    dgamma = _empty((c,), mean); dbeta = _empty((c,), mean)
-    ws, nb = _bn_ws(rows, c, y.device)
-    call("tmr_bn_bwd_coefs_g16", g, y, mean, inv, gamma, coef, dgamma, dbeta, rows, c, ws,
-         ctypes.c_size_t(nb), stream_ptr())
-    return coef, dgamma, dbeta
 
 
 def bn_bwd_parts_ds(g, y, parts, nparts, mean, inv, gamma, yd, mean_d, inv_d, gamma_d):
@@ -530,10 +441,9 @@ def bn_bwd_parts(g, y, parts, nparts, mean, inv, gamma, bf16=False):
 
 
 def conv_wgrad(x, dy, r, s, stride, pad, c_real=None, out=None, beta=0.0, pad_w=None,
-               math="fp32", xpro=None, dpro=None, groups=1):
+               math="fp32", groups=1):
     """x (N,H,W,C), dy (N,Ho,Wo,K) -> dW (K, c_real, R, S) in OIHW (x/dy may be channel slices).
-    xpro = (scale, shift): x read as relu(x*scale + shift); dpro = (y, coef): dy read as the BN
-    backward A*dy + B*y + C.  groups: c_real = real input channels per group."""
+    groups: c_real = real input channels per group."""
     n, h, w, c = x.shape
     k = dy.shape[3]
     c_real = c // groups if c_real is None else c_real
@@ -548,15 +458,10 @@ def conv_wgrad(x, dy, r, s, stride, pad, c_real=None, out=None, beta=0.0, pad_w=
     ws = torch.empty(max(1, (ws_bytes + 3) // 4), dtype=f32, device=x.device)
     with _prof("conv_wgrad" + _SUFFIX[math], 2.0 * n * d.ho * d.wo * k * r * s * c_real,
                (n, h, w, c, k, r, stride),
-               _esz(x) * n * h * w * c + _esz(dy) * n * d.ho * d.wo * k * (2 if dpro is not None else 1)
+               _esz(x) * n * h * w * c + _esz(dy) * n * d.ho * d.wo * k
                + 4 * k * r * s * c_real):
-        pro = _prologue(xpro, dpro)
-        if pro is None:
-            call("tmr_conv2d_wgrad", ctypes.byref(d), x, dy, out, int(c_real), float(beta), ws,
-                 ctypes.c_size_t(ws.numel() * 4), stream_ptr())
-        else:
-            call("tmr_conv2d_wgrad_pro", ctypes.byref(d), x, dy, out, int(c_real), float(beta),
-                 ws, ctypes.c_size_t(ws.numel() * 4), ctypes.byref(pro), stream_ptr())
+        call("tmr_conv2d_wgrad", ctypes.byref(d), x, dy, out, int(c_real), float(beta), ws,
+             ctypes.c_size_t(ws.numel() * 4), stream_ptr())
     return out
 
 

@@ -454,8 +454,8 @@ def _splat_bwd(sp, spl, r2, dout, grads):
 
 def _trunk_node_ok(share):
     """The whole-trunk node covers fp32 math and bf16 math under the bf16-activation contract."""
-    from .trunk import _act16, FOLD_BN
-    return not FOLD_BN and (share.precision == "fp32" or _act16(share.precision))
+    from .trunk import _act16
+    return share.precision == "fp32" or _act16(share.precision)
 
 
 def conv_bn_act(x, conv, bn, stride, pad, relu, groups=1, residual=None, c_real=None,

@@ -76,51 +76,6 @@ def _bn_momentum(bn):
     return bn.momentum
 
 
-# Train-mode BatchNorm folding (TMR_FOLD_BN=1; off by default): the BN+ReLU outputs of each
-# Bottleneck's first two units are never written -- the next conv reads the pre-BN y through an
-# X-operand prologue (tmr_conv_prologue) in its forward and wgrad loaders -- and no BatchNorm
-# backward writes dy: the conv's dgrad and wgrad read the masked gradient g and y through a
-# dY-operand prologue with per-channel coefficients.  Bit-identical to the explicit passes
-# (tests/test_kernels_gpu.py::test_bn_fold_bit_identical), but measured slower on MI355X: the
-# prologue costs the MFMA-bound fp32 GEMMs more than the HBM-bound passes it removes (~17 ms).
-# Register-staged engine (round 2): wgrad +21 ms, dgrad +12 ms, fwd +6 ms per step, C2 210 vs 181
-# ms/step (profiles/r2/convbench_fold/).  LDS-DMA engine (round 4, gemm16_kernel PRO: each lane
-# transforms its landed pieces in LDS before the barrier that publishes the k-tile): fwd +3.0,
-# wgrad +12.7, dgrad +21.0 ms per step, C2 193.3 vs 173.9 ms/step, 3312 vs 3680 frames/s, same
-# box (profiles/r4/fold_ab/): the transform sits between the LDS-DMA landing and the barrier with
-# every MFMA idle, and on the narrow tiles (256x64: 8 pieces per lane per k-tile) it triples the
-# LDS traffic; the dgrads also read y next to g (twice the A-operand bytes).  Retired to an A/B
-# build: the prologue entry points (include/tmr_prologue.h) exist only in `make PROLOGUES=1`'s
-# tmrnet_amd/libtmr_pro.so (run with TMR_LIB_PATH pointing at it); the default library rejects
-# TMR_FOLD_BN=1 at the first conv.
-FOLD_BN = os.environ.get("TMR_FOLD_BN", "0") == "1"
-# The bf16 form (round 5, same A/B build, TMR_FOLD16=1): under the bf16-activation step the relu(bn)
-# outputs of each Bottleneck's bn1 / bn2 are never written -- conv2 / conv3 read the bf16 pre-BN y
-# through the bf16 X-operand prologue of the LDS-DMA engine (relu(fmaf(y, scale, shift)) rounded
-# RNE: bn_apply8_a16_k's arithmetic, so bit-identical), forward and wgrad views.  Not for an input
-# the direct 3x3 kernels read (direct3.hip: ResNet-50 layer1's 56x56 64 -> 64 conv2).
-FOLD16 = os.environ.get("TMR_FOLD16", "0") == "1"
-# ... and its dY half (round 5, same A/B build, TMR_FOLD16_DY=1): no BatchNorm backward writes dy --
-# the conv's dgrad and wgrad read the bf16 masked gradient g and the bf16 y through the bf16
-# dY-operand prologue (fmaf(A, g, fmaf(B, y, C)) rounded RNE: bn_bwd_apply8_a16's arithmetic, so
-# bit-identical), for every unit whose g is stored bf16 (bn1 / bn2 under G16, bn3 / downsample
-# under R16: all but the last block's bn3) and whose conv is not a direct 3x3 (direct3.hip).
-FOLD16DY = os.environ.get("TMR_FOLD16_DY", "0") == "1"
-
-
-def _direct3_conv(rec):
-    """This unit's conv runs on the direct 3x3 kernels (direct3.hip d3_shape: 56x56 64 -> 64,
-    ResNeSt's deep-stem 112x112 32 -> 32 / 64), which take no operand prologue."""
-    k, c, r, s = rec["conv"].weight.shape
-    w = rec["x"].shape[2]
-    return (r == 3 and s == 3 and rec["stride"] == 1 and rec.get("groups", 1) == 1
-            and ((w == 56 and c == 64 and k == 64) or (w == 112 and c == 32 and k in (32, 64))))
-
-
-def _direct3_input(blk, h):
-    """The direct 3x3 kernel (direct3.hip d3_shape) serves conv2 of this block at input width h."""
-    return tuple(blk.conv2.weight.shape) == (64, 64, 3, 3) and blk.stride == 1 and h == 56
-
 # bf16 math (configs C4/C5): the tensors consumed only as conv operands -- the KRSC weights, the
 # BN+ReLU outputs of each Bottleneck's first two units, every BatchNorm-backward output dy -- are
 # stored as bf16 (tmr_conv_desc.io).  Exact: the bf16 convs round those operands to bf16 (RNE)
@@ -152,11 +107,6 @@ FULL16 = True
 ACT16 = os.environ.get("TMR_BF16_ACT", "1") != "0"
 
 
-# fp32 math: the dgrad view runs on the fp32 form of the LDS-DMA engine, reading a transposed fp32
-# weight copy (TMR_IO_WT_F32; the forward view takes that engine by itself).  (A module attribute
-# for the prologue A/B test of the retired fold build, tests/test_kernels_gpu.py.)
-DMA32 = True
-
 # bf16-activation step: the masked BN-output gradient of the non-residual units (bn1, bn2 of every
 # Bottleneck) stored bf16 by the fused dgrad (TMR_IO_G16; the residual stream's gradient stays
 # fp32) -- halves the bytes of the dgrad store and of the BN-backward apply's read of g.  The
@@ -183,10 +133,9 @@ DS_DUAL = True
 
 def _ds_dual(g, r3, rd):
     """DS_DUAL applies: g, y3 and y_ds of one dtype, which is also the dy dtype the separate passes
-    would write (fp32 y under bf16 storage writes bf16 dy: not this path), 8-channel multiples;
-    not under the dY-prologue A/B (FOLD16DY), which writes no dy at all."""
+    would write (fp32 y under bf16 storage writes bf16 dy: not this path), 8-channel multiples."""
     y = r3["y"]
-    return (DS_DUAL and not FOLD16DY and g.is_contiguous() and g.dtype == y.dtype == rd["y"].dtype
+    return (DS_DUAL and g.is_contiguous() and g.dtype == y.dtype == rd["y"].dtype
             and y.shape == rd["y"].shape and y.shape[-1] % 8 == 0
             and not (_store16(r3["math"]) and y.dtype == torch.float32))
 
@@ -195,9 +144,10 @@ def _ds_dual(g, r3, rd):
 # faster there (profiles/r3/bench_r4i/, round-4 A/B under R16: the step unchanged) and were retired.
 
 
+# fp32 math: the dgrad view runs on the fp32 form of the LDS-DMA engine, reading a transposed fp32
+# weight copy (TMR_IO_WT_F32; the forward view takes that engine by itself)
 def _dma32(math):
-    # (FOLD_BN too: the fp32 LDS-DMA engine applies the operand prologues in LDS, gemm16_kernel PRO)
-    return math == "fp32" and DMA32
+    return math == "fp32"
 
 
 # bf16 activations: the direct bf16 stem takes the NHWC4 fp32 input itself (stem16.hip, round 4:
@@ -206,7 +156,7 @@ def _dma32(math):
 
 
 def _full16(math):
-    return _store16(math) and FULL16 and not FOLD_BN
+    return _store16(math) and FULL16
 
 
 def _act16(math):
@@ -226,15 +176,11 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
 
     Train mode only: ``defer`` returns (y, scale, shift) instead of applying the BN -- the
     consumer applies it on load (the downsample branch inside its block's BN3 pass, the stem
-    inside the maxpool, with FOLD_BN the next conv's loaders); ``branch`` = such a deferred
-    (y, scale, shift) used as the residual; ``x`` may itself be a deferred (y, scale, shift) of a
-    ReLU unit, read through the conv's X-operand prologue.  ``dual`` (block outputs under
+    inside the maxpool); ``branch`` = such a deferred (y, scale, shift) used as the residual.
+    ``dual`` (block outputs under
     _full16): returns (z fp32, z bf16 copy).  ``groups``: a grouped conv
     (train mode; ResNeSt's radix-2 3x3, tmr_conv_desc.groups).  ``y16`` (eval mode, bf16
     activations: ResNet50Share.infer_act16): x and residual bf16, z rounded once to bf16."""
-    xpro = None
-    if isinstance(x, tuple):
-        x, xpro = x[0], (x[1], x[2])
     w = conv.weight
     k, c, r, s = w.shape
     cs = x.shape[3]
@@ -248,7 +194,7 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
     if training:
         # batch statistics come out of the conv epilogue (no separate pass over y)
         y, stats, nparts = ops.conv_fwd_bnstats(x, wk, stride, pad, c_real=c * groups, math=math,
-                                                xpro=xpro, y16=_act16(math), groups=groups)
+                                                y16=_act16(math), groups=groups)
         mean, inv, scale, shift = ops.bn_finalize(
             stats, nparts, bn.weight.detach(), bn.bias.detach(), bn.running_mean,
             bn.running_var, _bn_momentum(bn), bn.eps)
@@ -258,8 +204,6 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
         else:
             nbt.append(bn.num_batches_tracked)
     else:
-        if xpro is not None:
-            raise RuntimeError("deferred BatchNorm inputs exist in train mode only")
         # eval: running-stat BN, residual and ReLU in the conv epilogue (one launch, no y pass;
         # same arithmetic as conv_fwd + bn_apply)
         scale, shift = ops.bn_eval_params(bn.weight.detach(), bn.bias.detach(), bn.running_mean,
@@ -300,7 +244,7 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
             wt = ops.weight_to_crsk(w.detach().contiguous(), bf16=False)
         else:   # (the stem's 3 input channels: no dgrad)
             wt = None
-        recs.append({"x": x, "xpro": xpro, "wk": wk, "wt": wt, "y": y,
+        recs.append({"x": x, "wk": wk, "wt": wt, "y": y,
                      "z": (z[0] if dual else z) if has_res else None, "zbits": zbits,
                      "scale": scale, "shift": shift, "mean": mean, "inv": inv,
                      "stride": stride, "pad": pad, "relu": relu, "conv": conv, "bn": bn,
@@ -328,7 +272,6 @@ def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need
     r16: the same for fuse_prev a block output (R16): the dgrad adds into dx_out (bf16 in place,
     or fp32 read and a new bf16 tensor returned)."""
     conv, bn = rec["conv"], rec["bn"]
-    dpro = None    # (y, coef): dy = A*g + B*y + C evaluated by the consumer convs' loaders
     s16 = _store16(rec["math"])   # dy feeds only this conv's dgrad / wgrad
     dy_given = dy is not None
     if dy_given:
@@ -338,31 +281,6 @@ def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need
         dy, dg, db = ops.bn_bwd_maxpool(pool[0], pool[1], rec["y"], rec["scale"], rec["shift"],
                                         rec["mean"], rec["inv"], bn.weight.detach(), bf16=s16)
         dres = None
-    elif FOLD_BN:
-        rows = rec["y"].numel() // rec["y"].shape[-1]
-        if parts is not None:   # dz already masked by the producing dgrad's epilogue
-            coef, dg, db = ops.bn_bwd_coefs(parts[0], parts[1], rec["mean"], rec["inv"],
-                                            bn.weight.detach(), rows)
-        else:                   # one reduction pass; the ReLU mask is applied to dz in place
-            if want_dres and not dres_inplace:
-                raise RuntimeError("folded BN backward: the identity gradient is dz itself")
-            coef, dg, db = ops.bn_bwd_coefs_dense(dz, rec["y"], rec["z"], rec["scale"],
-                                                  rec["shift"], rec["mean"], rec["inv"],
-                                                  bn.weight.detach(), rec["relu"])
-        dy, dpro = dz, (rec["y"], coef)
-        dres = dz if want_dres else None
-    elif (FOLD16DY and dz.dtype == torch.bfloat16 and rec["y"].dtype == torch.bfloat16
-          and (parts is not None or not rec["relu"]) and rec.get("groups", 1) == 1
-          and not _direct3_conv(rec)):
-        # the bf16 dY prologue: coefficients only, the consumers read g and y
-        if parts is not None:
-            coef, dg, db = ops.bn_bwd_coefs(parts[0], parts[1], rec["mean"], rec["inv"],
-                                            bn.weight.detach(), rec["y"].numel() // rec["y"].shape[-1])
-        else:   # the downsample BN (no ReLU): one reduction pass over g and y
-            coef, dg, db = ops.bn_bwd_coefs_g16(dz, rec["y"], rec["mean"], rec["inv"],
-                                                bn.weight.detach())
-        dy, dpro = dz, (rec["y"], coef)
-        dres = dz if want_dres else None
     elif parts is not None:
         dy, dg, db = ops.bn_bwd_parts(dz, rec["y"], parts[0], parts[1], rec["mean"], rec["inv"],
                                       bn.weight.detach(), bf16=s16)
@@ -380,7 +298,7 @@ def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need
     grp = rec.get("groups", 1)
     grads[conv.weight] = ops.conv_wgrad(x, dy, r, s, rec["stride"], rec["pad"],
                                         c_real=rec["c_real"], math=rec["math"],
-                                        xpro=rec.get("xpro"), dpro=dpro, groups=grp)
+                                        groups=grp)
     dx, fused = None, None
     if need_dx:
         hw = (x.shape[1], x.shape[2])
@@ -392,8 +310,7 @@ def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need
             zm = p["z"]
             if mask == 1 and wt and p.get("zbits") is not None:
                 mask, zm = 3, p["zbits"]   # the ReLU mask as bits (fp32 LDS-DMA dgrad)
-            bf8 = (wt and (dpro is None or dpro[0].dtype == torch.bfloat16) and
-                   p["y"].dtype == torch.bfloat16 and
+            bf8 = (wt and p["y"].dtype == torch.bfloat16 and
                    (p["y"].shape[-1] // grp) % 8 == 0)
             # (a grouped dgrad -- ResNeSt's radix-2 conv -- stores its per-group channel slices bf16
             # too; the residual accumulation stays ungrouped)
@@ -406,12 +323,12 @@ def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need
             dx, pp, npp = ops.conv_dgrad_bnbwd(dy, wdg, hw, rec["stride"], rec["pad"],
                                                p["y"], p["mean"], mask, z=zm,
                                                scale=p["scale"], shift=p["shift"], out=dx_out,
-                                               beta=dx_beta, math=rec["math"], dpro=dpro,
+                                               beta=dx_beta, math=rec["math"],
                                                wt=wt, groups=grp, g16=gb or rb, old=old)
             fused = (pp, npp)
         else:
             dx = ops.conv_dgrad(dy, wdg, hw, rec["stride"], rec["pad"], out=dx_out,
-                                beta=dx_beta, math=rec["math"], dpro=dpro, wt=wt, groups=grp)
+                                beta=dx_beta, math=rec["math"], wt=wt, groups=grp)
     return dx, dres, fused
 
 
@@ -469,13 +386,10 @@ class TrunkFn(torch.autograd.Function):
         for layer in layers:
             for blk in layer:
                 brec = [] if keep else None
-                fold = training and FOLD_BN
-                fd16 = a16 and FOLD16
                 z1 = _conv_bn(hx, blk.conv1, blk.bn1, 1, 0, True, training, recs=brec, math=mt,
-                              nbt=nbt, y16=i16,
-                              defer=fold or (fd16 and not _direct3_input(blk, hx.shape[2])))
+                              nbt=nbt, y16=i16)
                 z2 = _conv_bn(z1, blk.conv2, blk.bn2, blk.stride, 1, True, training, recs=brec,
-                              math=mt, nbt=nbt, defer=fold or fd16, y16=i16)
+                              math=mt, nbt=nbt, y16=i16)
                 if blk.downsample is not None:
                     # train: the branch's BN is applied inside the BN3 pass (bn_apply2)
                     idn = _conv_bn(hx, blk.downsample[0], blk.downsample[1], blk.stride, 0, False,
