@@ -728,6 +728,20 @@ int tmr_lstm_bwd(const float* dy, const float* x, int b, int t, int i, int h, co
                  const float* w_hh, const float* y, const void* saved, size_t saved_bytes,
                  float* dx, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, void* ws,
                  size_t ws_bytes, hipStream_t stream);
+/* Online path (no reference counterpart: the reference scores offline, clip by clip): clip b runs
+ * the t-step nn.LSTM recurrence (gates i,f,g,o; h_0 = c_0 = 0) over the gate rows
+ * gates[rows[b*t + s]], s = 0..t-1 -- each row 4h floats of x W_ih^T + b_ih + b_hh -- and writes
+ * h_{t-1} to out + (out_rows ? out_rows[b] : b) * h.  Rows may repeat between clips.
+ * gates is a table of nrows rows; out must not overlap it.  h = 512, b <= 64 and a resident
+ * grid: one persistent launch (the forward recurrence of tmr_lstm_fwd reading its gate rows
+ * through `rows`; same residency rule, bounded barrier, solo recomputation after a give-up and
+ * env switches; the barrier words are the first bytes of ws, so tmr_lstm_sync_status and
+ * tmr_lstm_status_or apply).  Otherwise tmr_lfb_gather into ws, then one gate GEMM and one
+ * tmr_lstm_cell_fwd per step.  Nothing is saved for a backward. */
+size_t tmr_lstm_window_ws_bytes(int b, int t, int h);
+int tmr_lstm_window_fwd(const float* gates, long nrows, const int32_t* rows, int b, int t, int h,
+                        const float* w_hh, float* out, const int32_t* out_rows, void* ws,
+                        size_t ws_bytes, hipStream_t stream);
 /* timeout word of the last persistent LSTM launch on ws (0 = every grid barrier completed,
  * 1 = a barrier gave up and the results are invalid, 2 = gave up and recomputed);
  * synchronises the stream */

@@ -9,5 +9,6 @@ from .loss import CrossEntropyLoss  # noqa: F401
 from .optim import SGD, Adam  # noqa: F401
 from . import jpeg  # noqa: F401
 from .jpeg import DeviceJpegDecoder  # noqa: F401
+from .stream import OnlineRecognizer  # noqa: F401
 
 __version__ = "0.1.0"

@@ -174,7 +174,9 @@ SIGNATURES = {
     "tmr_lstm_ws_bytes": [I, I, I, I],
     "tmr_lstm_fwd": [P, I, I, I, I, P, P, P, P, P, P, P, P, SZ, P, SZ, P],
     "tmr_lstm_bwd": [P, P, I, I, I, I, P, P, P, P, SZ, P, P, P, P, P, P, SZ, P],
-    "tmr_lstm_sync_status": [P, ctypes.POINTER(ctypes.c_uint), P],
+    "tmr_lstm_window_ws_bytes": [I, I, I],
+    "tmr_lstm_window_fwd": [P, L, P, I, I, I, P, P, P, P, SZ, P],
+    "tmr_lstm_sync_status": [P,ctypes.POINTER(ctypes.c_uint), P],
     "tmr_lstm_status_or": [P, P, P],
     "tmr_test_hold_cus": [I, F, P],
     "tmr_dgrad_ws_launches": [],
@@ -201,6 +203,7 @@ _RESTYPES = {
     "tmr_timeconv_ws_bytes": SZ,
     "tmr_lstm_saved_bytes": SZ,
     "tmr_lstm_ws_bytes": SZ,
+    "tmr_lstm_window_ws_bytes": SZ,
 }
 
 _lib = None

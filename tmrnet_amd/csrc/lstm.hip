@@ -6,6 +6,9 @@
 //             h_{t-1} W_hh^T, sigma/tanh and the cell update without leaving the kernel.
 //   backward: BPTT in one persistent launch (dh = dy_t + dg_{t+1} W_hh, gate backward, dc), then
 //             one GEMM each for dW_ih, dW_hh, dx and a column sum for the biases.
+//   window  : tmr_lstm_window_fwd, the online path -- the forward recurrence alone over gate rows
+//             that already lie in a resident table, addressed through a row table (a sliding
+//             window of a ring); a second instantiation of the forward kernels, nothing saved.
 //
 // Persistent geometry (hidden size 512): workgroup (jx, by) owns hidden units 8*jx..8*jx+7 -- the
 // 32 rows of W_hh (forward) / 8 columns of W_hh (backward) that feed them stay on the CU for all
@@ -115,13 +118,19 @@ __device__ bool grid_barrier(unsigned* sync, unsigned target, unsigned limit) {
 // Thread (kg = tid / 32, c = tid % 32) keeps W_hh[row(c)][64 kg .. 64 kg + 63] in registers for
 // all steps (the slice never leaves the CU); h_{t-1} of the 16 clips is staged in LDS with one
 // batch of loads per thread; the 8 k-group partial dot products are added in a fixed order.
-__global__ __launch_bounds__(256) void lstm_rec_fwd_k(const float* __restrict__ gx,
-                                                      const float* __restrict__ whh,
-                                                      float* __restrict__ y, float* __restrict__ cs,
-                                                      float* __restrict__ acts,
-                                                      float* __restrict__ hn,
-                                                      float* __restrict__ cn, int B, int T,
-                                                      unsigned* sync, unsigned limit) {
+//
+// WIN (tmr_lstm_window_fwd): the gate row of (clip, step) is gx + rows[clip * T + step] * 4H, a
+// row of a resident gate table of nrows rows (an index outside it reads as zeros); nothing is
+// saved, and only h_{T-1} leaves the hand-off sequence: hn + (out_rows ? out_rows[clip] : clip) * H.
+template <bool WIN>
+__device__ __forceinline__ void lstm_rec_fwd_body(const float* __restrict__ gx,
+                                                  const float* __restrict__ whh,
+                                                  float* __restrict__ y, float* __restrict__ cs,
+                                                  float* __restrict__ acts,
+                                                  float* __restrict__ hn, float* __restrict__ cn,
+                                                  int B, int T, unsigned* sync, unsigned limit,
+                                                  const int32_t* __restrict__ rows, long nrows,
+                                                  const int32_t* __restrict__ out_rows) {
   constexpr int KG = 64;                 // k per register slice
   constexpr int HLD = LH + 4 * (LH / KG);  // padded h row: +4 floats per 64 (bank spread)
   __shared__ __attribute__((aligned(16))) float hs[BBC * HLD];
@@ -152,9 +161,14 @@ __global__ __launch_bounds__(256) void lstm_rec_fwd_k(const float* __restrict__ 
     for (int e = 0; e < 2; ++e) {
       const int o = tid + 256 * e;
       const int bl = o / NGC, cc = o % NGC;
-      gxv[e] = b0 + bl < B
-                   ? gx[((long)(b0 + bl) * T + t) * (4 * LH) + (cc / HU) * LH + j0 + (cc % HU)]
-                   : 0.f;
+      if (WIN) {
+        const long r = b0 + bl < B ? (long)rows[(long)(b0 + bl) * T + t] : -1;
+        gxv[e] = r >= 0 && r < nrows ? gx[r * (4 * LH) + (cc / HU) * LH + j0 + (cc % HU)] : 0.f;
+      } else {
+        gxv[e] = b0 + bl < B
+                     ? gx[((long)(b0 + bl) * T + t) * (4 * LH) + (cc / HU) * LH + j0 + (cc % HU)]
+                     : 0.f;
+      }
     }
     if (t > 0) {
       constexpr int NL = BBC * (LH / 4) / 256;   // float4 loads per thread (8)
@@ -205,18 +219,44 @@ __global__ __launch_bounds__(256) void lstm_rec_fwd_k(const float* __restrict__ 
       const float h = cell_fwd(gs[cb][cu], gs[cb][HU + cu], gs[cb][2 * HU + cu],
                                gs[cb][3 * HU + cu], creg, ig, fg, gg, og);
       st_sc1(&y[((long)cgb * T + t) * LH + cj], h);   // handed to every workgroup
-      if (cs) cs[((long)t * B + cgb) * LH + cj] = creg;
-      if (acts) {
-        float* a = acts + ((long)t * B + cgb) * (4 * LH);
-        a[cj] = ig; a[LH + cj] = fg; a[2 * LH + cj] = gg; a[3 * LH + cj] = og;
-      }
-      if (t + 1 == T) {
-        if (hn) hn[(long)cgb * LH + cj] = h;
-        if (cn) cn[(long)cgb * LH + cj] = creg;
+      if (WIN) {
+        if (t + 1 == T) hn[(long)(out_rows ? out_rows[cgb] : cgb) * LH + cj] = h;
+      } else {
+        if (cs) cs[((long)t * B + cgb) * LH + cj] = creg;
+        if (acts) {
+          float* a = acts + ((long)t * B + cgb) * (4 * LH);
+          a[cj] = ig; a[LH + cj] = fg; a[2 * LH + cj] = gg; a[3 * LH + cj] = og;
+        }
+        if (t + 1 == T) {
+          if (hn) hn[(long)cgb * LH + cj] = h;
+          if (cn) cn[(long)cgb * LH + cj] = creg;
+        }
       }
     }
     if (t + 1 < T && !grid_barrier(sync, (unsigned)((t + 1) * nwg), limit)) return;
   }
+}
+
+__global__ __launch_bounds__(256) void lstm_rec_fwd_k(const float* __restrict__ gx,
+                                                      const float* __restrict__ whh,
+                                                      float* __restrict__ y, float* __restrict__ cs,
+                                                      float* __restrict__ acts,
+                                                      float* __restrict__ hn,
+                                                      float* __restrict__ cn, int B, int T,
+                                                      unsigned* sync, unsigned limit) {
+  lstm_rec_fwd_body<false>(gx, whh, y, cs, acts, hn, cn, B, T, sync, limit, nullptr, 0, nullptr);
+}
+
+// The window instantiation: y is the hand-off sequence in the workspace, out the caller's rows.
+__global__ __launch_bounds__(256) void lstm_win_fwd_k(const float* __restrict__ gates,
+                                                      const float* __restrict__ whh,
+                                                      float* __restrict__ y,
+                                                      float* __restrict__ out, int B, int T,
+                                                      unsigned* sync, unsigned limit,
+                                                      const int32_t* __restrict__ rows, long nrows,
+                                                      const int32_t* __restrict__ out_rows) {
+  lstm_rec_fwd_body<true>(gates, whh, y, nullptr, nullptr, out, nullptr, B, T, sync, limit, rows,
+                          nrows, out_rows);
 }
 
 // ---------------------------------------------------------------- backward recurrence
@@ -328,14 +368,18 @@ __global__ __launch_bounds__(256) void lstm_rec_bwd_k(const float* __restrict__ 
 // ("recovered") so tmr_lstm_status_or does not report the step as failed.
 constexpr int SPC = 4;   // clips per workgroup of the solo kernels
 
-__global__ __launch_bounds__(256) void lstm_rec_fwd_solo_k(const float* __restrict__ gx,
-                                                           const float* __restrict__ whh,
-                                                           float* __restrict__ y,
-                                                           float* __restrict__ cs,
-                                                           float* __restrict__ acts,
-                                                           float* __restrict__ hn,
-                                                           float* __restrict__ cn, int B, int T,
-                                                           unsigned* sync) {
+template <bool WIN>
+__device__ __forceinline__ void lstm_rec_fwd_solo_body(const float* __restrict__ gx,
+                                                       const float* __restrict__ whh,
+                                                       float* __restrict__ y,
+                                                       float* __restrict__ cs,
+                                                       float* __restrict__ acts,
+                                                       float* __restrict__ hn,
+                                                       float* __restrict__ cn, int B, int T,
+                                                       unsigned* sync,
+                                                       const int32_t* __restrict__ rows,
+                                                       long nrows,
+                                                       const int32_t* __restrict__ out_rows) {
   if (sync[1] == 0u) return;
   if (blockIdx.x == 0 && threadIdx.x == 0) sync[1] = 2u;
   constexpr int G4 = 4 * LH, KG = 64;
@@ -374,8 +418,15 @@ __global__ __launch_bounds__(256) void lstm_rec_fwd_solo_k(const float* __restri
         }
       }
 #pragma unroll
-      for (int bl = 0; bl < SPC; ++bl)
-        if (b0 + bl < B) gs[bl][col] = gx[((long)(b0 + bl) * T + t) * G4 + col] + a[bl];
+      for (int bl = 0; bl < SPC; ++bl) {
+        if (b0 + bl >= B) continue;
+        if (WIN) {
+          const long r = rows[(long)(b0 + bl) * T + t];
+          gs[bl][col] = (r >= 0 && r < nrows ? gx[r * G4 + col] : 0.f) + a[bl];
+        } else {
+          gs[bl][col] = gx[((long)(b0 + bl) * T + t) * G4 + col] + a[bl];
+        }
+      }
     }
     __syncthreads();
 #pragma unroll
@@ -390,19 +441,46 @@ __global__ __launch_bounds__(256) void lstm_rec_fwd_solo_k(const float* __restri
                                  gs[bl][3 * LH + j], creg[e][bl], ig, fg, gg, og);
         y[((long)cgb * T + t) * LH + j] = h;
         hs[bl][j] = h;
-        if (cs) cs[((long)t * B + cgb) * LH + j] = creg[e][bl];
-        if (acts) {
-          float* ap = acts + ((long)t * B + cgb) * G4;
-          ap[j] = ig; ap[LH + j] = fg; ap[2 * LH + j] = gg; ap[3 * LH + j] = og;
-        }
-        if (t + 1 == T) {
-          if (hn) hn[(long)cgb * LH + j] = h;
-          if (cn) cn[(long)cgb * LH + j] = creg[e][bl];
+        if (WIN) {
+          if (t + 1 == T) hn[(long)(out_rows ? out_rows[cgb] : cgb) * LH + j] = h;
+        } else {
+          if (cs) cs[((long)t * B + cgb) * LH + j] = creg[e][bl];
+          if (acts) {
+            float* ap = acts + ((long)t * B + cgb) * G4;
+            ap[j] = ig; ap[LH + j] = fg; ap[2 * LH + j] = gg; ap[3 * LH + j] = og;
+          }
+          if (t + 1 == T) {
+            if (hn) hn[(long)cgb * LH + j] = h;
+            if (cn) cn[(long)cgb * LH + j] = creg[e][bl];
+          }
         }
       }
     }
     __syncthreads();
   }
+}
+
+__global__ __launch_bounds__(256) void lstm_rec_fwd_solo_k(const float* __restrict__ gx,
+                                                           const float* __restrict__ whh,
+                                                           float* __restrict__ y,
+                                                           float* __restrict__ cs,
+                                                           float* __restrict__ acts,
+                                                           float* __restrict__ hn,
+                                                           float* __restrict__ cn, int B, int T,
+                                                           unsigned* sync) {
+  lstm_rec_fwd_solo_body<false>(gx, whh, y, cs, acts, hn, cn, B, T, sync, nullptr, 0, nullptr);
+}
+
+__global__ __launch_bounds__(256) void lstm_win_fwd_solo_k(const float* __restrict__ gates,
+                                                           const float* __restrict__ whh,
+                                                           float* __restrict__ y,
+                                                           float* __restrict__ out, int B, int T,
+                                                           unsigned* sync,
+                                                           const int32_t* __restrict__ rows,
+                                                           long nrows,
+                                                           const int32_t* __restrict__ out_rows) {
+  lstm_rec_fwd_solo_body<true>(gates, whh, y, nullptr, nullptr, out, nullptr, B, T, sync, rows,
+                               nrows, out_rows);
 }
 
 __global__ __launch_bounds__(256) void lstm_rec_bwd_solo_k(const float* __restrict__ dy,
@@ -648,6 +726,102 @@ TMR_API int tmr_lstm_fwd(const float* x, int b, int t, int i, int h, const float
                                    (size_t)h * 4, b, hipMemcpyDeviceToDevice, stream) == hipSuccess,
                   "tmr_lstm_fwd: h_n copy failed");
   }
+  return 0;
+}
+
+// ---------------------------------------------------------------- sliding-window forward
+namespace {
+
+// per-step path of tmr_lstm_window_fwd: out row of clip b = its last hidden state
+__global__ void win_out_k(const float* __restrict__ y, float* __restrict__ out,
+                          const int32_t* __restrict__ out_rows, int B, int T, int H) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)B * H) return;
+  const int j = (int)(i % H);
+  const long b = i / H;
+  out[(long)(out_rows ? out_rows[b] : b) * H + j] = y[(b * T + (T - 1)) * H + j];
+}
+
+// workspace of tmr_lstm_window_fwd (bytes, 256-aligned pieces); the barrier words come first, as
+// in LstmWs, so tmr_lstm_sync_status / tmr_lstm_status_or read them
+struct WinWs {
+  size_t sync, gx, ghh, y, c, total;
+};
+WinWs win_ws(int b, int t, int h) {
+  WinWs w;
+  size_t o = 0;
+  w.sync = o; o += 256;
+  w.gx = o; o += al256((size_t)b * t * 4 * h * 4);    // per-step path: the gathered gate rows
+  w.ghh = o; o += al256((size_t)b * 4 * h * 4);       // per-step path: h W_hh^T
+  w.y = o; o += al256((size_t)b * t * h * 4);         // hand-off sequence h_t
+  w.c = o; o += al256((size_t)2 * b * h * 4);         // per-step path: cell states
+  w.total = o;
+  return w;
+}
+
+}  // namespace
+
+TMR_API size_t tmr_lstm_window_ws_bytes(int b, int t, int h) {
+  if (b < 0 || t < 0 || h <= 0) {
+    tmr_set_error("tmr_lstm_window_ws_bytes: bad sizes b=%d t=%d h=%d", b, t, h);
+    return 0;
+  }
+  return win_ws(b, t, h).total;
+}
+
+TMR_API int tmr_lstm_window_fwd(const float* gates, long nrows, const int32_t* rows, int b, int t,
+                                int h, const float* w_hh, float* out, const int32_t* out_rows,
+                                void* ws, size_t ws_bytes, hipStream_t stream) {
+  TMR_CHECK_ARG(b >= 0 && t >= 0 && h > 0 && h % 4 == 0 && nrows >= 0,
+                "tmr_lstm_window_fwd: bad sizes b=%d t=%d h=%d nrows=%ld", b, t, h, nrows);
+  TMR_CHECK_ARG(gates && rows && w_hh && out, "tmr_lstm_window_fwd: null operand");
+  const WinWs L = win_ws(b, t, h);
+  TMR_CHECK_ARG(ws && ws_bytes >= L.total, "tmr_lstm_window_fwd: workspace %zu < %zu bytes",
+                ws_bytes, L.total);
+  // as tmr_lstm_fwd: the barrier words start at 0 on every call, on every path
+  TMR_CHECK_ARG(hipMemsetAsync((char*)ws + L.sync, 0, 16, stream) == hipSuccess,
+                "tmr_lstm_window_fwd: memset failed");
+  if (b == 0 || t == 0) return 0;
+  char* w = (char*)ws;
+  unsigned* sync = (unsigned*)(w + L.sync);
+  float* y = (float*)(w + L.y);
+  if (persist_allowed() && lstm_persistent_shape(b, t, h) && b <= 4 * BBC) {
+    dim3 grid(LH / HU, cdiv(b, BBC));
+    unsigned lim = spin_limit();
+    if (resident((const void*)lstm_win_fwd_k, grid, 256)) {
+      hipLaunchKernelGGL(lstm_win_fwd_k, grid, dim3(256), 0, stream, gates, w_hh, y, out, b, t,
+                         sync, lim, rows, nrows, out_rows);
+      if (hipGetLastError() == hipSuccess) {
+        if (recover_allowed()) {   // exits at once unless the launch above gave up
+          hipLaunchKernelGGL(lstm_win_fwd_solo_k, dim3(cdiv(b, SPC)), dim3(256), 0, stream, gates,
+                             w_hh, y, out, b, t, sync, rows, nrows, out_rows);
+          TMR_CHECK_LAUNCH("lstm_win_fwd_solo_k");
+        }
+        return 0;
+      }
+    }
+    // not resident: per-step path below
+  }
+  // per-step path: gather the window's gate rows, then gate GEMM + fused cell kernel per step
+  float* gx = (float*)(w + L.gx);
+  float* ghh = (float*)(w + L.ghh);
+  float* cbuf[2] = {(float*)(w + L.c), (float*)(w + L.c) + (size_t)b * h};
+  int rc = tmr_lfb_gather(gates, rows, gx, (long)b * t, 4 * h, stream);
+  if (rc) return rc;
+  for (int s = 0; s < t; ++s) {
+    if (s > 0) {
+      rc = tmr_gemm_nt(b, 4 * h, h, y + (size_t)(s - 1) * h, t * h, w_hh, h, nullptr, ghh, 4 * h,
+                       0.f, stream);
+      if (rc) return rc;
+    }
+    rc = tmr_lstm_cell_fwd(gx + (size_t)s * 4 * h, t * 4 * h, s > 0 ? ghh : nullptr,
+                           s > 0 ? cbuf[(s - 1) & 1] : nullptr, y + (size_t)s * h, t * h,
+                           cbuf[s & 1], nullptr, b, h, stream);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(win_out_k, dim3(cdiv((long)b * h, 256)), dim3(256), 0, stream, y, out,
+                     out_rows, b, t, h);
+  TMR_CHECK_LAUNCH("lstm window out");
   return 0;
 }
 

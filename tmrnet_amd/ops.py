@@ -1155,6 +1155,37 @@ def lstm_bwd(dy, x, w_ih, w_hh, y, saved, want_dx=True):
     return dx, dw_ih, dw_hh, db_ih, db_hh, ws
 
 
+def lstm_window_fwd(gates, rows, w_hh, out=None, out_rows=None):
+    """tmr_lstm_window_fwd: gates (N, 4H) gate table, rows (B, T) int32 rows of it per clip ->
+    (out, ws); out[out_rows[b] or b] = h_{T-1} of clip b.  ws holds the barrier words
+    (lstm_sync_status, health.note_lstm)."""
+    _req(gates, "gates")
+    _req(rows, "rows", torch.int32)
+    _req(w_hh, "w_hh")
+    B, T = rows.shape
+    H = w_hh.shape[1]
+    if gates.dim() != 2 or gates.shape[1] != 4 * H or w_hh.shape[0] != 4 * H:
+        raise RuntimeError("lstm_window_fwd: gates %s / w_hh %s are not (N, 4H) / (4H, H)"
+                           % (tuple(gates.shape), tuple(w_hh.shape)))
+    if out_rows is not None:
+        _req(out_rows, "out_rows", torch.int32)
+        if out_rows.numel() != B:
+            raise RuntimeError("lstm_window_fwd: %d out_rows for %d clips" % (out_rows.numel(), B))
+        if out is None:
+            raise RuntimeError("lstm_window_fwd: out_rows needs the out tensor they index")
+    if out is None:
+        out = _empty((B, H), gates)
+    else:
+        _req(out, "out")
+        if out.dim() != 2 or out.shape[1] != H or (out_rows is None and out.shape[0] < B):
+            raise RuntimeError("lstm_window_fwd: out %s does not hold %d rows of %d"
+                               % (tuple(out.shape), B, H))
+    ws = _ws(query("tmr_lstm_window_ws_bytes", B, T, H), gates)
+    call("tmr_lstm_window_fwd", gates, gates.shape[0], rows, B, T, H, w_hh, out, out_rows, ws,
+         ws.numel(), stream_ptr())
+    return out, ws
+
+
 def lstm_sync_status(ws):
     """Timeout word of the last persistent LSTM launch on `ws` (0 = all grid barriers done)."""
     v = ctypes.c_uint(0)
