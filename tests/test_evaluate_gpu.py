@@ -18,12 +18,16 @@ def test_softmax_max_kernel(dev):
     g = torch.Generator().manual_seed(0)
     x = torch.randn(1000, 7, generator=g) * 5
     x[3] = 1.0                                   # ties: first index wins, like ce_sum / torch.max
+    x[5, 2] = x[5, 5] = x[5].max() + 1.0         # a repeated maximum away from index 0
+    x[999, 6] = x[999, 4] = x[999].max() + 0.5   # ... in the last, partly filled block of 256
+    assert x.shape[0] % 256 != 0
     probs, pmax, preds = ops.softmax_max(x.to(dev))
     p_ref = torch.softmax(x.double(), 1)
     assert (probs.cpu().double() - p_ref).abs().max().item() < 1e-6
     assert (pmax.cpu().double() - p_ref.max(1).values).abs().max().item() < 1e-6
     assert torch.equal(preds.cpu(), x.argmax(1))
     assert preds[3].item() == 0
+    assert preds[5].item() == 2 and preds[999].item() == 4
 
 
 def test_phase_evaluator_matches_reference_loop(dev):

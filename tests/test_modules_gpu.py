@@ -7,7 +7,10 @@ tmr_linear_*) against float64 torch, and their two execution paths.
   -- both against nn.LSTM in float64 (train_only_non-local_pretrained.py:215, :230-231), and the
   barrier's timeout word must read 0; a barrier give-up (forced, or caused by a kernel resident
   on another stream) is recomputed by the solo kernels, bit-identical.
-* tmr_nl_attn split over 32-row chunks at the C5 shape (B=64, L=300, bank rows) against float64.
+* tmr_nl_attn split over 32-row chunks at the C5 shape (B=64, L=300, bank rows) against float64,
+  at every advertised width (256, 512, 1024), with scores spanning +-60 (the online-softmax
+  rescale) and with all scores equal.
+* tmr_timeconv_fwd/wgrad at L = 1, 2, 7 against TimeConvRef in float64 under autograd.
 * tmr_linear_fwd/bwd against float64 nn.Linear.
 """
 import json
@@ -15,7 +18,9 @@ import os
 
 import pytest
 import torch
+import torch.nn.functional as F
 
+from oracle import tmrnet_ref as ref
 from tmrnet_amd import ops
 from tmrnet_amd._lib import call, stream_ptr
 from tmrnet_amd.lstm import LSTM
@@ -214,13 +219,17 @@ def _giveup_steps(dev, monkeypatch):
         m(x)
 
 
-@pytest.mark.parametrize("B,L,rows", [(64, 300, True), (3, 40, False), (2, 1, False),
-                                      (4, 33, True)])
-def test_nl_attn_split(dev, B, L, rows):
+@pytest.mark.parametrize("B,L,rows,D", [
+    pytest.param(64, 300, True, 512, id="64-300-True"),
+    pytest.param(3, 40, False, 512, id="3-40-False"),
+    pytest.param(2, 1, False, 512, id="2-1-False"),
+    pytest.param(4, 33, True, 512, id="4-33-True"),
+    (3, 40, False, 256), (2, 33, True, 1024), (2, 1, False, 1024), (4, 70, True, 256)])
+def test_nl_attn_split(dev, B, L, rows, D):
     """Chunked attention core (32-row chunks + ordered combine) vs float64, incl. a ragged last
-    chunk (L=33), L=1 and C5's B=64, L=300 read from a bank through the row table."""
+    chunk (L=33), L=1 and C5's B=64, L=300 read from a bank through the row table; every
+    advertised width (D = 256, 512, 1024: one template instantiation each)."""
     g = torch.Generator().manual_seed(B * 1000 + L)
-    D = 512
     u = torch.randn(B, D, generator=g, dtype=torch.float64)
     dctx = torch.randn(B, D, generator=g, dtype=torch.float64)
     if rows:
@@ -246,6 +255,160 @@ def test_nl_attn_split(dev, B, L, rows):
     assert rel(ut, ut64) < 2e-5
     if rows_d is None:
         assert rel(dlt, dlt64) < 2e-5
+
+
+def _attn_ref(lt64, u, dctx, scale):
+    """float64 attention core and its backward (include/tmr.h, tmr_nl_attn_fwd / _bwd)"""
+    s = torch.einsum("bld,bd->bl", lt64, u) * scale
+    p = torch.softmax(s, 1)
+    ctx = torch.einsum("bl,bld->bd", p, lt64)
+    dp = torch.einsum("bld,bd->bl", lt64, dctx)
+    ds = scale * p * (dp - (p * dp).sum(1, keepdim=True))
+    ut = torch.einsum("bl,bld->bd", ds, lt64)
+    return s, p, ctx, dp, ut
+
+
+ATTN_PEAK_MARGIN = 4.0
+
+
+def _attn_large_score_case(D):
+    """(lt, u, dctx), fp32-exact float64: B = 2 clips of L = 77 rows (chunks of 32, 32 and a
+    ragged 13 = one full wave + 5 rows) whose scores span about +-60, the clip maximum in the
+    last row.  The peak row is the clip's best row moved to the end and shrunk until its score is
+    ATTN_PEAK_MARGIN above the runner-up: far above the typical score, so every other chunk is
+    rescaled by exp(-4) ... exp(-120) in the combine, yet 1 - p_peak stays near 2e-2.  (ut is
+    proportional to 1 - p_peak while the fp32 rounding of dp_peak - sum_k p_k dp_k is not: a
+    peak e.g. 12 above the runner-up would leave ut with a relative fp32 error of 1e-3 in any
+    implementation.)"""
+    B, L = 2, 77
+    g = torch.Generator().manual_seed(D)
+    u = (torch.randn(B, D, generator=g, dtype=torch.float64) * 45).float().double()
+    dctx = torch.randn(B, D, generator=g, dtype=torch.float64).float().double()
+    lt = (torch.rand(B, L, D, generator=g, dtype=torch.float64) * 2 - 1).float().double()
+    scale = (1.0 / D) ** 0.5
+    for _ in range(2):          # the second pass absorbs the fp32 rounding of the shrunk row
+        s = torch.einsum("bld,bd->bl", lt, u) * scale
+        for b in range(B):
+            j = int(s[b].argmax())
+            if j != L - 1:
+                lt[b, [j, L - 1]] = lt[b, [L - 1, j]]
+                s[b, [j, L - 1]] = s[b, [L - 1, j]]
+            top, second = s[b, L - 1], s[b, :L - 1].max()
+            lt[b, L - 1] = (lt[b, L - 1] * ((second + ATTN_PEAK_MARGIN) / top)).float().double()
+    return lt, u, dctx, scale
+
+
+@pytest.mark.parametrize("D,rows", [(256, False), (512, True), (1024, False)])
+def test_nl_attn_large_scores(dev, D, rows):
+    """The online-softmax rescale between waves and chunks under stress: scores spanning about
+    +-60 with the clip maximum in the last, ragged chunk, at every width.  p, ctx < 1e-5 (the
+    bounds of test_nl_attn_split), |sum_l p_l - 1| < 1e-6, ut < 2e-5 of its own magnitude; the
+    backward reads the reference's p rounded to fp32."""
+    lt64, u, dctx, scale = _attn_large_score_case(D)
+    B, L, _ = lt64.shape
+    s, p64, ctx64, _, ut64 = _attn_ref(lt64, u, dctx, scale)
+    # conditions on the data, from the float64 reference alone
+    assert bool((s.argmax(1) == L - 1).all())
+    assert float((s.max(1).values - s.min(1).values).min()) > 100.0
+    margin = s[:, L - 1] - s[:, :L - 1].max(1).values
+    assert bool(((margin - ATTN_PEAK_MARGIN).abs() < 0.05).all())
+    assert float((s[:, L - 1] - s[:, :64].max(1).values).min()) > ATTN_PEAK_MARGIN - 0.05
+    if rows:
+        perm = torch.randperm(B * L, generator=torch.Generator().manual_seed(1))
+        bank = torch.empty(B * L, D)
+        bank[perm] = lt64.float().view(B * L, D)
+        lt_d, rows_d = bank.to(dev), perm.view(B, L).to(torch.int32).to(dev)
+    else:
+        lt_d, rows_d = lt64.float().to(dev), None
+    ud = u.float().to(dev)
+    p, ctx = ops.nl_attn_fwd(lt_d, rows_d, ud, B, L, scale)
+    assert rel(p, p64) < 1e-5 and rel(ctx, ctx64) < 1e-5
+    assert (p.double().sum(1) - 1).abs().max().item() < 1e-6
+    ut, dlt = ops.nl_attn_bwd(lt_d, rows_d, ud, p64.float().to(dev), dctx.float().to(dev), B, L,
+                              scale, rows_d is None)
+    assert rel(ut, ut64) < 2e-5
+    if rows_d is None:
+        assert bool(torch.isfinite(dlt).all())
+
+
+def test_nl_attn_equal_scores(dev):
+    """Every bank index of a clip is the same row: all scores equal, p = 1/L (L = 50: 1/L is not
+    an fp32 number), ctx = that row.  ut vanishes in exact arithmetic (ds_l = scale p_l (dp_l -
+    sum_k p_k dp_k) = 0); in fp32 it is bounded by the rounding of the sum against dp, so it is
+    held to 2e-5 of the size of its terms, scale * max|dp| * max|row|."""
+    B, L, D = 3, 50, 512
+    g = torch.Generator().manual_seed(50)
+    bank = (torch.rand(20, D, generator=g, dtype=torch.float64) * 2 - 1).float().double()
+    u = torch.randn(B, D, generator=g, dtype=torch.float64).float().double()
+    dctx = torch.randn(B, D, generator=g, dtype=torch.float64).float().double()
+    which = torch.tensor([7, 0, 19])
+    idx = which[:, None].expand(B, L).contiguous()
+    scale = (1.0 / D) ** 0.5
+    _, p64, ctx64, dp, _ = _attn_ref(bank[idx], u, dctx, scale)
+    assert (p64 - 1.0 / L).abs().max().item() < 1e-15
+    bank_d, rows_d = bank.float().to(dev), idx.to(torch.int32).to(dev)
+    p, ctx = ops.nl_attn_fwd(bank_d, rows_d, u.float().to(dev), B, L, scale)
+    assert rel(p, p64) < 1e-5 and rel(ctx, ctx64) < 1e-5
+    assert (p.double().sum(1) - 1).abs().max().item() < 1e-6
+    ut, _ = ops.nl_attn_bwd(bank_d, rows_d, u.float().to(dev), p, dctx.float().to(dev), B, L,
+                            scale, False)
+    size = scale * dp.abs().max().item() * bank[which].abs().max().item()
+    assert ut.abs().max().item() < 2e-5 * size
+
+
+# seeds 100*L + s, s = 0..3, whose inputs meet the gap condition below (smallest gaps 1.8e-5 ..
+# 3.7e-4); L = 7, s = 3 does not (5.7e-7 between x and conv3 at one element) and is left out
+TC_SMALL_L = [(L, s) for L in (1, 2, 7) for s in range(4) if (L, s) != (7, 3)]
+
+
+@pytest.mark.parametrize("L,s", TC_SMALL_L)
+def test_timeconv_backward_small_L(dev, L, s):
+    """TimeConv forward, x.grad and the six parameter gradients vs TimeConvRef in float64 under
+    autograd, where the 7-tap window is mostly padding (L = 1, 2) -- the only rectangular-filter
+    (k x 1) use of the conv engine's dgrad / wgrad.  Forward 1e-5 absolute
+    (test_timeconv_generalised_L), gradients rel_err < 1e-5 (test_timeconv_golden).
+    amax splits the gradient of the structural x / maxpool tie evenly and both shares land on
+    x[t], so the float64 gradients agree with the first-maximum rule -- provided no other two
+    branches come close: the smallest gap between the top two of (x, y1, y2, y3, prev) is asserted
+    to be >= 1e-5 in float64, ten times the forward bound."""
+    from tmrnet_amd.timeconv import TimeConv
+    torch.manual_seed(100 * L + s)
+    r = ref.TimeConvRef()
+    x = torch.rand(2, L, 512) * 2 - 1
+    dy = torch.randn(2, L, 512)
+    m = TimeConv().to(dev)
+    m.load_state_dict(r.state_dict())
+    r = r.double()
+    with torch.no_grad():
+        xt = x.double().transpose(1, 2)
+        prev = F.pad(xt, (1, 0))[..., :-1]
+        top = torch.stack((xt, r.timeconv1(xt), r.timeconv2(xt), r.timeconv3(xt), prev)
+                          ).sort(0).values
+        assert (top[-1] - top[-2]).min().item() >= 1e-5
+    xr = x.double().requires_grad_(True)
+    yr = r(xr)
+    yr.backward(dy.double())
+    xd = x.to(dev).requires_grad_(True)
+    y = m(xd)
+    y.backward(dy.to(dev))
+    assert (y.detach().cpu().double() - yr.detach()).abs().max().item() < 1e-5
+    assert rel(xd.grad, xr.grad) < 1e-5
+    grads = dict(r.named_parameters())
+    for name, p in m.named_parameters():
+        assert rel(p.grad, grads[name].grad) < 1e-5, name
+
+
+def test_linear_bwd_single_row(dev):
+    """rows = 1, out = 7: the bias gradient is the column sum of one row (tmr_col_sum's tail
+    alone), dW an outer product."""
+    g = torch.Generator().manual_seed(17)
+    x = torch.randn(1, 1024, generator=g, dtype=torch.float64).float().double()
+    w = torch.randn(7, 1024, generator=g, dtype=torch.float64).float().double()
+    dy = torch.randn(1, 7, generator=g, dtype=torch.float64).float().double()
+    dx, dw, db = ops.linear_bwd(dy.float().to(dev), x.float().to(dev), w.float().to(dev))
+    assert rel(db, dy[0]) < 2e-6
+    assert rel(dw, dy.t() @ x) < 2e-6
+    assert rel(dx, dy @ w) < 2e-6
 
 
 def test_linear_entry_points(dev):
