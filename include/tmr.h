@@ -423,6 +423,39 @@ int tmr_resize_u8(const uint8_t* in, int n, int h, int w, uint8_t* tmp, size_t t
                   uint8_t* out, int oh, int ow, const int32_t* bounds_h, const int32_t* k_h,
                   int ksize_h, const int32_t* bounds_v, const int32_t* k_v, int ksize_v, int y0,
                   int y1, hipStream_t stream);
+/* Boxed, per-frame form: frame i of out = Image.resize((ow, oh), BILINEAR) of
+ * in[i, r0:r1, c0:c1].  One descriptor of TMR_RESIZE_BOX_INTS int32 per frame:
+ *   [r0, r1, c0, c1, hb, hk, ksh, vb, vk, ksv]
+ * hb / hk: int32 offsets into `pool` of the horizontal bounds (ow x 2) and coefficients
+ * (ow x ksh) of c1 - c0 -> ow; vb / vk / ksv the same for r1 - r0 -> oh.  ksize 0 marks an axis
+ * whose size does not change (no table; the pass is skipped, as in Pillow).  desc_host is the host
+ * copy every check reads before any launch (box inside the frame, ksize, offsets inside the pool
+ * of pool_ints int32); desc and pool are the same descriptors and the tables in device memory.
+ * tmp: tmr_resize_tmp_bytes(n, h, w, oh, ow) bytes, needed when a frame runs both passes.  One
+ * launch per pass for the whole batch. */
+#define TMR_RESIZE_BOX_INTS 10
+int tmr_resize_u8_boxes(const uint8_t* in, int n, int h, int w, const int32_t* desc_host,
+                        const int32_t* desc, const int32_t* pool, long pool_ints, uint8_t* tmp,
+                        size_t tmp_bytes, uint8_t* out, int oh, int ow, hipStream_t stream);
+
+/* ---------------- input pipeline: black-margin cut, frame statistics (margin.hip) -------- */
+/* change_size() of code/video2frame_cutmargin.py:20-48, bit-exact in integers.  in (n, h, w, 3)
+ * uint8 RGB -> boxes (n, 4) int32 [r0, r1, c0, c1]; the crop is rows [r0, r1), columns [c0, c1).
+ * Per frame: g = (9798 R + 19235 G + 3735 B + 16384) >> 15; m = g > 15; 19x19 median with
+ * replicated borders (= at least 181 of the 361 clamped window values set); r0 / r1 and c0 / c1
+ * are the min / max row and column of the set pixels whose column lies in [10, w - 10).  No such
+ * pixel, or r1 == r0, or c1 == c0: the box is the full frame [0, h, 0, w].
+ * ws: tmr_margin_ws_bytes(n, h, w) bytes, 16-byte aligned, reusable from call to call (a min / max
+ * slot per 64 x 64 tile, then one mask bit per pixel in 64-bit words).
+ * tmr_margin_mask (debug): the mask after the median, (n, h, w) uint8 0 / 255. */
+size_t tmr_margin_ws_bytes(int n, int h, int w);
+int tmr_margin_boxes(const uint8_t* in, int n, int h, int w, void* ws, size_t ws_bytes,
+                     int32_t* boxes, hipStream_t stream);
+int tmr_margin_mask(const uint8_t* in, int n, int h, int w, void* ws, size_t ws_bytes,
+                    uint8_t* mask, hipStream_t stream);
+/* sums (n, 3, 2) int64: per frame and channel the exact sum of v and of v * v (meanStd.py's
+ * statistic follows on the host, frames.mean_std). */
+int tmr_frame_sums(const uint8_t* in, int n, int h, int w, int64_t* sums, hipStream_t stream);
 
 /* ---------------- input pipeline: baseline JPEG decode (jpeg_host.cpp, jpeg.hip) -------- */
 /* pil_loader (:96-99) of a baseline JPEG file, bit-exact to Pillow / libjpeg-turbo's default

@@ -95,6 +95,11 @@ SIGNATURES = {
     "tmr_resize_coeffs": [I, I, P, P, I],
     "tmr_resize_tmp_bytes": [I, I, I, I, I],
     "tmr_resize_u8": [P, I, I, I, P, SZ, P, I, I, P, P, I, P, P, I, I, I, P],
+    "tmr_resize_u8_boxes": [P, I, I, I, P, P, P, L, P, SZ, P, I, I, P],
+    "tmr_margin_ws_bytes": [I, I, I],
+    "tmr_margin_boxes": [P, I, I, I, P, SZ, P, P],
+    "tmr_margin_mask": [P, I, I, I, P, SZ, P, P],
+    "tmr_frame_sums": [P, I, I, I, P, P],
     "tmr_jpeg_probe": [P, SZ, JP],
     "tmr_jpeg_entropy_decode": [P, SZ, JP, P, SZ],
     "tmr_jpeg_ws_bytes": [I, I, I, I],
@@ -191,6 +196,7 @@ _RESTYPES = {
     "tmr_conv2d_wgrad_ws_bytes": SZ,
     "tmr_dgrad_ws_launches": L,
     "tmr_resize_tmp_bytes": SZ,
+    "tmr_margin_ws_bytes": SZ,
     "tmr_jpeg_ws_bytes": SZ,
     "tmr_bn_ws_bytes": SZ,
     "tmr_bn_parts_ws_bytes": SZ,

@@ -185,3 +185,154 @@ TMR_API int tmr_resize_u8(const uint8_t* in, int n, int h, int w, uint8_t* tmp, 
   }
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Boxed, per-frame resize: frame i of out is Image.resize((ow, oh), BILINEAR) of
+// in[i, r0:r1, c0:c1].  Boxes differ from frame to frame (frames.margin_boxes), so every frame
+// carries a descriptor of kResizeBoxInts int32:
+//   [r0, r1, c0, c1, hb, hk, ksh, vb, vk, ksv]
+// hb / hk: where the horizontal bounds (ow x 2) and coefficients (ow x ksh) of c1 - c0 -> ow start
+// in the int32 table pool, vb / vk / ksv the same for r1 - r0 -> oh; a ksize of 0 marks a pass
+// whose size does not change (Pillow skips it).  One launch per pass covers the whole batch.
+namespace {
+
+constexpr int kResizeBoxInts = TMR_RESIZE_BOX_INTS;
+
+// horizontal pass over the rows of each box that its vertical pass reads -> tmp (n, h, ow, 3)
+// (frame stride h rows, the rows packed from the top), or straight to out without a vertical pass
+__global__ __launch_bounds__(NT) void resize_box_h_k(const uint8_t* __restrict__ in, int h, int w,
+                                                     int oh, int ow, const int* __restrict__ desc,
+                                                     const int* __restrict__ pool,
+                                                     uint8_t* __restrict__ tmp,
+                                                     uint8_t* __restrict__ out, long total) {
+  for (long i = blockIdx.x * (long)NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
+    const int xo = (int)(i % ow);
+    const long t = i / ow;
+    const int yr = (int)(t % h);
+    const long f = t / h;
+    const int* d = desc + f * kResizeBoxInts;
+    const int ksize = d[6];
+    if (ksize == 0) continue;                 // this frame has no horizontal pass
+    const int r0 = d[0], c0 = d[2], ksv = d[9];
+    int y0 = 0, rows = d[1] - r0;
+    if (ksv != 0) {                           // the rows its vertical pass reads
+      const int* bv = pool + d[7];
+      y0 = bv[0];
+      rows = bv[2 * (oh - 1)] + bv[2 * (oh - 1) + 1] - y0;
+    }
+    if (yr >= rows) continue;
+    const int* bounds = pool + d[4];
+    const int xmin = bounds[2 * xo], cnt = bounds[2 * xo + 1];
+    const int* k = pool + d[5] + (long)xo * ksize;
+    const uint8_t* src = in + ((f * h + r0 + y0 + yr) * (long)w + c0 + xmin) * 3;
+    int s0 = 1 << (kPrecisionBits - 1), s1 = s0, s2 = s0;
+    for (int x = 0; x < cnt; ++x) {
+      const int kx = k[x];
+      s0 += (int)src[3 * x] * kx;
+      s1 += (int)src[3 * x + 1] * kx;
+      s2 += (int)src[3 * x + 2] * kx;
+    }
+    uint8_t* dst = ksv != 0 ? tmp + ((f * h + yr) * (long)ow + xo) * 3
+                            : out + ((f * oh + yr) * (long)ow + xo) * 3;
+    dst[0] = clip8(s0);
+    dst[1] = clip8(s1);
+    dst[2] = clip8(s2);
+  }
+}
+
+// vertical pass (from tmp after a horizontal pass, else from the box itself) -> out; a frame with
+// neither pass is copied, one with only the horizontal pass is already in out
+__global__ __launch_bounds__(NT) void resize_box_v_k(const uint8_t* __restrict__ in, int h, int w,
+                                                     int oh, int ow, const int* __restrict__ desc,
+                                                     const int* __restrict__ pool,
+                                                     const uint8_t* __restrict__ tmp,
+                                                     uint8_t* __restrict__ out, long total) {
+  for (long i = blockIdx.x * (long)NT + threadIdx.x; i < total; i += (long)gridDim.x * NT) {
+    const int xo = (int)(i % ow);
+    const long t = i / ow;
+    const int yo = (int)(t % oh);
+    const long f = t / oh;
+    const int* d = desc + f * kResizeBoxInts;
+    const int ksh = d[6], ksv = d[9];
+    const int r0 = d[0], c0 = d[2];
+    uint8_t* dst = out + i * 3;
+    if (ksv == 0) {
+      if (ksh == 0) {                         // same size on both axes: the box's own bytes
+        const uint8_t* s = in + ((f * h + r0 + yo) * (long)w + c0 + xo) * 3;
+        dst[0] = s[0];
+        dst[1] = s[1];
+        dst[2] = s[2];
+      }
+      continue;
+    }
+    const int* bounds = pool + d[7];
+    const int ymin = bounds[2 * yo], cnt = bounds[2 * yo + 1];
+    const int* k = pool + d[8] + (long)yo * ksv;
+    const uint8_t* s;
+    long rs;
+    if (ksh != 0) {
+      s = tmp + ((f * h + ymin - bounds[0]) * (long)ow + xo) * 3;
+      rs = (long)ow * 3;
+    } else {
+      s = in + ((f * h + r0 + ymin) * (long)w + c0 + xo) * 3;
+      rs = (long)w * 3;
+    }
+    int s0 = 1 << (kPrecisionBits - 1), s1 = s0, s2 = s0;
+    for (int y = 0; y < cnt; ++y) {
+      const int ky = k[y];
+      s0 += (int)s[y * rs] * ky;
+      s1 += (int)s[y * rs + 1] * ky;
+      s2 += (int)s[y * rs + 2] * ky;
+    }
+    dst[0] = clip8(s0);
+    dst[1] = clip8(s1);
+    dst[2] = clip8(s2);
+  }
+}
+
+}  // namespace
+
+TMR_API int tmr_resize_u8_boxes(const uint8_t* in, int n, int h, int w, const int32_t* desc_host,
+                                const int32_t* desc, const int32_t* pool, long pool_ints,
+                                uint8_t* tmp, size_t tmp_bytes, uint8_t* out, int oh, int ow,
+                                hipStream_t stream) {
+  TMR_CHECK_ARG(in && out && desc_host && desc && n > 0 && h > 0 && w > 0 && oh > 0 && ow > 0,
+                "tmr_resize_u8_boxes: bad arguments");
+  TMR_CHECK_ARG(pool_ints >= 0, "tmr_resize_u8_boxes: negative pool size");
+  bool any_h = false, both = false;
+  for (int f = 0; f < n; ++f) {
+    const int32_t* d = desc_host + (long)f * kResizeBoxInts;
+    const int r0 = d[0], r1 = d[1], c0 = d[2], c1 = d[3];
+    TMR_CHECK_ARG(0 <= r0 && r0 < r1 && r1 <= h && 0 <= c0 && c0 < c1 && c1 <= w,
+                  "tmr_resize_u8_boxes: box [%d, %d) x [%d, %d) of frame %d outside %d x %d", r0,
+                  r1, c0, c1, f, h, w);
+    const int bh = r1 - r0, bw = c1 - c0;
+    const int ksh = bw == ow ? 0 : tmr_resize_ksize(bw, ow);
+    const int ksv = bh == oh ? 0 : tmr_resize_ksize(bh, oh);
+    TMR_CHECK_ARG(d[6] == ksh && d[9] == ksv,
+                  "tmr_resize_u8_boxes: frame %d has ksize (%d, %d), its box needs (%d, %d)", f,
+                  d[6], d[9], ksh, ksv);
+    TMR_CHECK_ARG(ksh == 0 || (pool && d[4] >= 0 && d[5] >= 0 && d[4] + 2L * ow <= pool_ints &&
+                               d[5] + (long)ow * ksh <= pool_ints),
+                  "tmr_resize_u8_boxes: horizontal tables of frame %d outside the pool", f);
+    TMR_CHECK_ARG(ksv == 0 || (pool && d[7] >= 0 && d[8] >= 0 && d[7] + 2L * oh <= pool_ints &&
+                               d[8] + (long)oh * ksv <= pool_ints),
+                  "tmr_resize_u8_boxes: vertical tables of frame %d outside the pool", f);
+    any_h |= ksh != 0;
+    both |= ksh != 0 && ksv != 0;
+  }
+  TMR_CHECK_ARG(!both || (tmp && tmp_bytes >= (size_t)n * h * ow * 3),
+                "tmr_resize_u8_boxes: tmp missing or smaller than %zu bytes",
+                (size_t)n * h * ow * 3);
+  if (any_h) {
+    const long total = (long)n * h * ow;
+    hipLaunchKernelGGL(resize_box_h_k, dim3(ew_blocks(total)), dim3(NT), 0, stream, in, h, w, oh,
+                       ow, (const int*)desc, (const int*)pool, tmp, out, total);
+    TMR_CHECK_LAUNCH("resize_box_h");
+  }
+  const long total = (long)n * oh * ow;
+  hipLaunchKernelGGL(resize_box_v_k, dim3(ew_blocks(total)), dim3(NT), 0, stream, in, h, w, oh, ow,
+                     (const int*)desc, (const int*)pool, (const uint8_t*)tmp, out, total);
+  TMR_CHECK_LAUNCH("resize_box_v");
+  return 0;
+}

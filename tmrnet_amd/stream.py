@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import health, ops
-from .frames import RESIZE, resize_frames
+from .frames import RESIZE, margin_boxes, resize_frames
 from .lfb_build import LFBBuilder, center_offset, check_activations, inference_mode
 from .nlblock import LFBRows
 
@@ -136,10 +136,16 @@ class OnlineRecognizer:
     activations: "fp32" or "bf16" (lfb_build.check_activations, for both models).
     window: "kernel" (tmr_lstm_window_fwd), "steps" (gather + LFBBuilder.recur) or "auto".
     gate_cap / bank_cap: ring sizes per stream (default T and lfb_length + 1).
+    cut_margin: cut each frame's black margin before the resize, as the reference prepares its
+    frames (frames.margin_boxes).  A stream's box is taken from the first frame it pushes at age
+    0, after construction or ``reset``, and reused for every later frame of that stream: an
+    endoscope's border does not move within a video.  Taking it reads 16 bytes per new stream to
+    the host, the only host read ``push`` makes, and only on those ticks.  Frames that already
+    are 250 x 250 are cropped and resized too.  ``margin_box(stream)`` returns the box.
     """
 
     def __init__(self, model, model_lfb, lfb_length, streams=1, activations="fp32",
-                 window="auto", gate_cap=None, bank_cap=None):
+                 window="auto", gate_cap=None, bank_cap=None, cut_margin=False):
         if window not in WINDOWS:
             raise ValueError("window must be one of %s, got %r" % (WINDOWS, window))
         if model.seq_len != model_lfb.seq_len:
@@ -170,6 +176,8 @@ class OnlineRecognizer:
         self._pin_ev = [None, None]
         self._tick = 0
         self._hist = [[] for _ in range(st.S)]
+        self.cut_margin = bool(cut_margin)
+        self._boxes = np.zeros((st.S, 4), dtype=np.int32)   # per stream, valid from its age 1 on
         self.mark = None   # optional callable(name): called after each phase of a tick was
         #                    enqueued (scripts/stream_bench.py times the phases with it)
 
@@ -181,6 +189,22 @@ class OnlineRecognizer:
         """The stream starts a new video: its age is 0 again.  The rings are left alone (a stale
         row is never read: every row a tick reads was written after the reset)."""
         self.state.reset(stream)
+
+    def margin_box(self, stream):
+        """[r0, r1, c0, c1] cut out of the stream's frames (cut_margin=True), taken from the first
+        frame of its current video; None before that frame."""
+        i = int(self.state.ids([stream])[0])
+        if not self.cut_margin or self.state.ages[i] == 0:
+            return None
+        return self._boxes[i].tolist()
+
+    def _cut(self, u8, ids):
+        """Crop every frame by its stream's box and resize it; streams at age 0 get their box."""
+        new = np.nonzero(self.state.ages[ids] == 0)[0]
+        if new.size:
+            first = u8 if new.size == ids.size else u8[torch.from_numpy(new).to(u8.device)]
+            self._boxes[ids[new]] = margin_boxes(first).cpu().numpy()
+        return resize_frames(u8, RESIZE, boxes=self._boxes[ids])
 
     def health(self):
         """Raise if a window recurrence gave up a grid barrier and was not recomputed."""
@@ -256,10 +280,11 @@ class OnlineRecognizer:
 
         frames_u8: (S', H, W, 3) uint8 in host or device memory, or a callable returning it (a
         decoder; called with the stream ids).  Frames of another size than 250 x 250 are resized
-        (frames.resize_frames).  Returns a dict: ``streams`` (ids), ``ready`` (host bool array:
+        (frames.resize_frames); with cut_margin every frame is cropped by its stream's box first.
+        Returns a dict: ``streams`` (ids), ``ready`` (host bool array:
         the push completed a clip, age + 1 >= T) and the device tensors ``preds``, ``scores``,
         ``probs``, ``logits``, ``lfb_rows`` with one row per pushed stream, meaningful where
-        ready.  Nothing is copied to the host."""
+        ready.  Nothing is copied to the host (but a new stream's box with cut_margin)."""
         st = self.state
         ids = st.ids(streams)
         n = ids.size
@@ -272,7 +297,9 @@ class OnlineRecognizer:
                                  % (n, n, u8.dtype, tuple(u8.shape)))
             bias = self._params()
             u8 = u8.to(self.device, non_blocking=True).contiguous()
-            if tuple(u8.shape[1:3]) != tuple(RESIZE):
+            if self.cut_margin:
+                u8 = self._cut(u8, ids)
+            elif tuple(u8.shape[1:3]) != tuple(RESIZE):
                 u8 = resize_frames(u8, RESIZE)
             x4 = ops.crop_normalize(u8, self._off, n)
             self._mark("input")
