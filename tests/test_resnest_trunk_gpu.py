@@ -91,6 +91,69 @@ def test_grouped_conv_views(dev, case, bf16):
     assert rel_err(dw.cpu(), dw64) < (5e-6 if bf16 else 2e-6)
 
 
+@pytest.mark.parametrize("bf16", [False, True])
+def test_grouped_conv_frame_chunks(dev, bf16, monkeypatch):
+    """groups = 2 together with frame chunks (tmr_conv_desc.max_frames): the ragged strided conv of
+    GROUPED on 5 frames, at 2 frames per launch (the last chunk is short), equals the
+    single-launch run in every view -- forward (plain, fused BN apply, BN statistics), dgrad
+    (plain, fused BN backward) bit-exact, wgrad to the chunks' summation order.  The partial rows
+    only regroup the same values: the statistics agree as in test_conv_frame_chunks, and the
+    BN-backward column sums within fp32 summation error, 2 (N + 2) 2^-24 sum |v| over the
+    N = n h w values of a column (each run adds N products in fp32, each rounded at most twice)."""
+    import ctypes
+    from tmrnet_amd._lib import call, stream_ptr
+    n, h, w, cin, cout, st = 5, 9, 7, 128, 256, 2
+    G = 2
+    g = torch.Generator().manual_seed(7)
+    math = "bf16" if bf16 else "fp32"
+    sdt = torch.bfloat16 if bf16 else torch.float32
+    wt = (torch.randn(cout, cin // G, 3, 3, generator=g) / np.sqrt(9 * cin / G)).to(dev)
+    xd = torch.randn(n, h, w, cin, generator=g).to(dev).to(sdt)
+    wk = ops.weight_to_krsc(wt, cpad=cin // G, bf16=bf16)
+    wtr = ops.weight_to_crsk_grouped(wt, G, bf16=bf16)
+    ho, wo = (h - 1) // st + 1, (w - 1) // st + 1
+    dyd = torch.randn(n, ho, wo, cout, generator=g).to(dev).to(sdt)
+    ypd = torch.randn(n, h, w, cin, generator=g).to(dev).to(sdt)
+    sc = (torch.rand(cin, generator=g) + 0.5).to(dev)
+    sh = (torch.randn(cin, generator=g) * 0.5).to(dev)
+    mu = (torch.randn(cin, generator=g) * 0.1).to(dev)
+    osc = (torch.rand(cout, generator=g) + 0.5).to(dev)
+    osh = torch.randn(cout, generator=g).to(dev)
+
+    def views(max_frames):
+        monkeypatch.setattr(ops, "MAX_FRAMES", max_frames)
+        d = ops.conv_desc(n, h, w, cin, cout, 3, 3, st, 1, math=math, io=ops._io(xd, wk), groups=G)
+        y = torch.empty(n, ho, wo, cout, device=dev)
+        call("tmr_conv2d_fwd", ctypes.byref(d), xd, wk, None, y, 0.0, stream_ptr())
+        yf = torch.empty_like(y)
+        call("tmr_conv2d_fwd_fused", ctypes.byref(d), xd, wk, osc, osh, None, yf, 1, stream_ptr())
+        ys, stats, nparts = ops.conv_fwd_bnstats(xd, wk, st, 1, math=math, y16=bf16, groups=G)
+        dx = ops.conv_dgrad(dyd, wtr, (h, w), st, 1, math=math, wt=True, groups=G)
+        dxm, parts, np_ = ops.conv_dgrad_bnbwd(dyd, wtr, (h, w), st, 1, ypd, mu, 2, scale=sc,
+                                               shift=sh, math=math, wt=True, groups=G)
+        dw = ops.conv_wgrad(xd, dyd, 3, 3, st, 1, math=math, groups=G)
+        return y, yf, ys, stats, nparts, dx, dxm, parts, np_, dw
+
+    y1, yf1, ys1, stats1, nparts1, dx1, dxm1, parts1, np1, dw1 = views(0)
+    y2, yf2, ys2, stats2, nparts2, dx2, dxm2, parts2, np2, dw2 = views(2)
+    assert torch.equal(y1, y2) and torch.equal(yf1, yf2) and torch.equal(ys1, ys2)
+    assert y1.abs().max() > 0 and not torch.equal(y1, yf1)
+    assert torch.equal(dx1, dx2) and torch.equal(dxm1, dxm2)
+    assert nparts2 >= nparts1 and np2 >= np1
+    assert rel_err(dw2, dw1) < 1e-6
+    c1 = torch.ones(cout, device=dev)
+    fin = [ops.bn_finalize(s_, p_, c1, torch.zeros_like(c1), torch.zeros_like(c1),
+                           torch.ones_like(c1), 0.1, 1e-5) for s_, p_ in ((stats1, nparts1),
+                                                                          (stats2, nparts2))]
+    assert rel_err(fin[1][0], fin[0][0]) < 1e-5 and rel_err(fin[1][1], fin[0][1]) < 1e-5
+    gm = dxm1.double().reshape(-1, cin)
+    v = torch.stack([gm, gm * (ypd.double().reshape(-1, cin) - mu.double())], 2)
+    bound = 2 * (n * h * w + 2) * 2.0 ** -24 * v.abs().sum(0)
+    ps1, ps2 = parts1[:np1].double().sum(0), parts2[:np2].double().sum(0)
+    assert ((ps1 - ps2).abs() <= bound).all()
+    assert ((ps1 - v.sum(0)).abs() <= bound).all()
+
+
 def _splat_tail_ref(m, y, C, gy, rnd):
     """bn0 (batch stats) -> relu -> [bf16 storage] -> SplAtConv2d's attention tail -> [bf16]
     in m's dtype; -> (out, dy, param grads)."""

@@ -25,7 +25,7 @@
 // transposed reads with the odd 16-lane groups taking their upper 4 rows first
 // (scripts/probe/lds_banks.py).
 #include "common.h"
-#include "tmr.h"
+#include "direct_conv.h"
 
 namespace {
 
@@ -777,133 +777,162 @@ int grid_of(int rows, int cin, int cout, int mode) {
 
 }  // namespace
 
-// ---- host entries (gemm_conv.hip routes the deep stem's geometry here) ----
+// ---- host side: the families' entries in gemm_conv.hip's routing table (direct_conv.h) ----
+namespace {
 
-// supported (width, input, output channels) of the forward / wgrad; the dgrad takes the same convs
-static bool d3_ok(int w, int cin, int cout) {
-  return (w == 112 && cin == 32 && (cout == 32 || cout == 64)) ||
-         (w == 56 && cin == 64 && cout == 64);
+// The stride-1 convs served (width, input, output channels): the deep stem's 32 -> 32 / 32 -> 64 at
+// 112 and ResNet-50 layer1's 64 -> 64 at 56; bf16 math, every operand bf16 in HBM, dense NHWC, one
+// launch over all frames (no max_frames).  The dgrad takes the same convs.
+bool d3_shape(const tmr_conv_desc* d) {
+  const bool wc = (d->w == DW && d->c == 32 && (d->k == 32 || d->k == 64)) ||
+                  (d->w == 56 && d->c == 64 && d->k == 64);
+  return d->math == TMR_MATH_BF16 && ngroups(d) == 1 && d->r == 3 && d->s == 3 && d->stride == 1 &&
+         d->pad == 1 && d->pad_w == 1 && wc && d->wo == d->w && d->ho == d->h &&
+         xld_of(d) == d->c && yld_of(d) == d->k && d->max_frames == 0;
+}
+bool d3_fwd_serves(const tmr_conv_desc* d) {
+  return d3_shape(d) && d->io == (TMR_IO_X_BF16 | TMR_IO_W_BF16 | TMR_IO_Y_BF16);
+}
+bool d3_dgrad_serves(const tmr_conv_desc* d) {
+  const int io = d->io & ~TMR_IO_G16;   // (a bf16 masked gradient: the 56-wide convs)
+  return d3_shape(d) && io == (TMR_IO_DY_BF16 | TMR_IO_WT_BF16 | TMR_IO_BN_BF16) &&
+         (!(d->io & TMR_IO_G16) || d->w == 56);
+}
+bool d3_wgrad_serves(const tmr_conv_desc* d) {
+  return d3_shape(d) && d->io == (TMR_IO_X_BF16 | TMR_IO_DY_BF16);
 }
 
-int tmr_d3_stats_parts(int n, int h, int w, int cin, int cout) {
-  const int ks = 9 * cin / 32, npw = 18 / ks, wn = (cout / 16) / npw, wm = 4 / wn;   // d3_k's WM
-  return grid_of(n * h, cin, cout, 0) * wm;
+int d3_fwd_parts(const tmr_conv_desc* d) {
+  const int ks = 9 * d->c / 32, npw = 18 / ks, wn = (d->k / 16) / npw, wm = 4 / wn;   // d3_k's WM
+  return grid_of(d->n * d->h, d->c, d->k, 0) * wm;
 }
 
-int tmr_d3_dgrad_parts(int n, int h, int w, int cin_conv, int cout_conv) {
-  (void)w;
-  return grid_of(n * h, cout_conv, cin_conv, 1);   // the dgrad kernel runs over dy
-}
+// (the dgrad kernel runs over dy: k -> c)
+int d3_dgrad_parts(const tmr_conv_desc* d) { return grid_of(d->n * d->h, d->k, d->c, 1); }
 
-size_t tmr_d3_wgrad_ws_bytes(int n, int h, int w, int cin, int cout) {
-  (void)w;
-  const int rows = n * h;
-  return (size_t)(rows < kGridW ? rows : kGridW) * cout * 9 * cin * sizeof(float);
-}
-
-int tmr_d3_fwd_bnstats(int n, int h, int w, int cin, int cout, const void* x, const void* w_krsc,
-                       void* y, void* stats, hipStream_t stream) {
-  TMR_CHECK_ARG(n > 0 && h > 0 && d3_ok(w, cin, cout), "tmr_d3_fwd: unsupported shape (w %d, %d -> %d)",
-                w, cin, cout);
+int d3_fwd(const tmr_conv_desc* d, const void* x, const void* w_krsc, void* y, void* stats,
+           hipStream_t stream) {
   TMR_CHECK_ARG((((uintptr_t)x | (uintptr_t)y | (uintptr_t)w_krsc) & 15) == 0,
                 "tmr_d3_fwd: x / y / w must be 16-B aligned");
-  const int rows = n * h, grid = grid_of(rows, cin, cout, 0);
+  const int rows = d->n * d->h, grid = grid_of(rows, d->c, d->k, 0);
 #define D3F(CI, CO, W)                                                                            \
   hipLaunchKernelGGL((d3_k<CI, CO, 0, W>), dim3(grid), dim3(256), 0, stream, (const uint4*)x,     \
                      (const __bf16*)w_krsc, y, (float4*)stats, nullptr, nullptr, nullptr, nullptr, \
-                     nullptr, 0, 0.f, nullptr, h, rows)
-  if (w == 56) D3F(64, 64, 56);
-  else if (cout == 64) D3F(32, 64, 112);
+                     nullptr, 0, 0.f, nullptr, d->h, rows)
+  if (d->w == 56) D3F(64, 64, 56);
+  else if (d->k == 64) D3F(32, 64, 112);
   else D3F(32, 32, 112);
 #undef D3F
   TMR_CHECK_LAUNCH("d3_fwd");
   return 0;
 }
 
-// dgrad of the conv cin_conv -> cout_conv: dy (rows, w, cout_conv) bf16, w_crsk (cin_conv, 3, 3,
-// cout_conv) bf16, dx (rows, w, cin_conv) fp32 (read when beta != 0), or bf16 when g16 (the masked
-// gradient rounded, no beta); the BatchNorm backward of the unit that produced the conv input:
-// y / z bf16 like dx, mask 0 / 1 / 2
-int tmr_d3_dgrad_bnbwd(int n, int h, int w, int cin_conv, int cout_conv, const void* dy,
-                       const void* w_crsk, void* dx, int g16, float beta, const void* y,
-                       const void* z, const float* scale, const float* shift, const float* mean,
-                       int mask, void* parts, hipStream_t stream) {
-  TMR_CHECK_ARG(n > 0 && h > 0 && d3_ok(w, cin_conv, cout_conv) && (!g16 || w == 56) &&
-                    !(g16 && beta != 0.f),
-                "tmr_d3_dgrad: unsupported shape (w %d, %d -> %d, g16 %d, beta %g)", w, cin_conv,
-                cout_conv, g16, beta);
+// dgrad of the conv c -> k: dy (rows, w, k) bf16, w_crsk (c, 3, 3, k) bf16, dx (rows, w, c) fp32
+// (read when beta != 0), or bf16 with TMR_IO_G16 (the masked gradient rounded, no beta); the
+// BatchNorm backward of the unit that produced the conv input: y / z bf16 like dx, mask 0 / 1 / 2
+int d3_dgrad(const tmr_conv_desc* d, const void* dy, const void* w_crsk, void* dx, float beta,
+             const void* y, const void* z, const float* scale, const float* shift,
+             const float* mean, int mask, void* parts, hipStream_t stream) {
+  const int g16 = (d->io & TMR_IO_G16) ? 1 : 0;
+  TMR_CHECK_ARG(!(g16 && beta != 0.f), "tmr_d3_dgrad: a bf16 gradient takes no beta (%g)", beta);
   TMR_CHECK_ARG((((uintptr_t)dy | (uintptr_t)dx | (uintptr_t)w_crsk | (uintptr_t)y |
                   (uintptr_t)z) & 15) == 0,
                 "tmr_d3_dgrad: operands must be 16-B aligned");
   TMR_CHECK_ARG(mask == 0 || (mask == 1 && z) || (mask == 2 && scale && shift),
                 "tmr_d3_dgrad: mask %d operands", mask);
-  const int rows = n * h, grid = grid_of(rows, cout_conv, cin_conv, 1);
+  const int rows = d->n * d->h, grid = grid_of(rows, d->k, d->c, 1);
 #define D3D(CI, CO, W, G)                                                                         \
   hipLaunchKernelGGL((d3_k<CI, CO, 1, W, G>), dim3(grid), dim3(256), 0, stream, (const uint4*)dy, \
                      (const __bf16*)w_crsk, dx, nullptr, (const uint4*)y, (const uint4*)z, scale,  \
-                     shift, mean, mask, beta, (float2*)parts, h, rows)
-  if (w == 56 && g16) D3D(64, 64, 56, 1);
-  else if (w == 56) D3D(64, 64, 56, 0);
-  else if (cout_conv == 64) D3D(64, 32, 112, 0);
+                     shift, mean, mask, beta, (float2*)parts, d->h, rows)
+  if (d->w == 56 && g16) D3D(64, 64, 56, 1);
+  else if (d->w == 56) D3D(64, 64, 56, 0);
+  else if (d->k == 64) D3D(64, 32, 112, 0);
   else D3D(32, 32, 112, 0);
 #undef D3D
   TMR_CHECK_LAUNCH("d3_dgrad");
   return 0;
 }
 
-int tmr_d3_wgrad_slabs(int n, int h, int w, int cin, int cout, const void* x, const void* dy,
-                       float* ws, size_t ws_bytes, int* nslabs, hipStream_t stream) {
-  TMR_CHECK_ARG(n > 0 && h > 0 && d3_ok(w, cin, cout), "tmr_d3_wgrad: unsupported shape (w %d, %d -> %d)",
-                w, cin, cout);
+// wgrad: one partial slab (k, 9, c) of the engine's wgrad layout per workgroup
+int gridw_of(int rows) { return rows < kGridW ? rows : kGridW; }
+long wslab_of(const tmr_conv_desc* d) { return (long)d->k * 9 * d->c; }
+size_t d3_ws_bytes(const tmr_conv_desc* d) {
+  return (size_t)gridw_of(d->n * d->ho) * wslab_of(d) * sizeof(float);
+}
+
+int d3_wgrad(const tmr_conv_desc* d, const void* x, const void* dy, float* ws, size_t ws_bytes,
+             DirectSlabs* slabs, hipStream_t stream) {
   TMR_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy) & 15) == 0, "tmr_d3_wgrad: x / dy must be 16-B aligned");
-  const int rows = n * h, grid = rows < kGridW ? rows : kGridW;
-  TMR_CHECK_ARG(ws && ws_bytes >= tmr_d3_wgrad_ws_bytes(n, h, w, cin, cout),
-                "tmr_d3_wgrad: workspace too small (%zu)", ws_bytes);
-  if (w == 56)
+  const int rows = d->n * d->h, grid = gridw_of(rows);
+  TMR_CHECK_ARG(ws && ws_bytes >= d3_ws_bytes(d), "tmr_d3_wgrad: workspace too small (%zu)", ws_bytes);
+  if (d->w == 56)
     hipLaunchKernelGGL((d3w_k<64, 64, 56>), dim3(grid), dim3(256), 0, stream, (const uint4*)x,
-                       (const uint4*)dy, ws, h, rows);
-  else if (cout == 64)
+                       (const uint4*)dy, ws, d->h, rows);
+  else if (d->k == 64)
     hipLaunchKernelGGL((d3w_k<32, 64>), dim3(grid), dim3(256), 0, stream, (const uint4*)x,
-                       (const uint4*)dy, ws, h, rows);
+                       (const uint4*)dy, ws, d->h, rows);
   else
     hipLaunchKernelGGL((d3w_k<32, 32>), dim3(grid), dim3(256), 0, stream, (const uint4*)x,
-                       (const uint4*)dy, ws, h, rows);
+                       (const uint4*)dy, ws, d->h, rows);
   TMR_CHECK_LAUNCH("d3_wgrad");
-  *nslabs = grid;
+  *slabs = {grid, wslab_of(d), 9, d->c};
   return 0;
 }
 
-// the deep stem's first conv (3x3/2, 3 -> 32 on the NHWC4 fp32 input): stats partial rows
-int tmr_d3s_stats_parts(int n, int ho) {
-  const int rows = n * ho;
-  return 4 * (rows < 3 * 256 ? rows : 3 * 256);
+// The deep stem's first conv, 3x3/2 3 (4 stored) -> 32 on the NHWC4 fp32 input of width SW2, bf16
+// math, even heights; one launch over all frames (no max_frames)
+bool d3s_shape(const tmr_conv_desc* d) {
+  return d->math == TMR_MATH_BF16 && ngroups(d) == 1 && d->c == 4 && d->k == 32 && d->r == 3 &&
+         d->s == 3 && d->stride == 2 && d->pad == 1 && d->pad_w == 1 && d->w == SW2 &&
+         d->wo == DW && d->h % 2 == 0 && d->ho == d->h / 2 && xld_of(d) == 4 &&
+         yld_of(d) == 32 && d->max_frames == 0;
 }
+bool d3s_fwd_serves(const tmr_conv_desc* d) {
+  return d3s_shape(d) && d->io == (TMR_IO_W_BF16 | TMR_IO_Y_BF16);
+}
+bool d3s_wgrad_serves(const tmr_conv_desc* d) { return d3s_shape(d) && d->io == TMR_IO_DY_BF16; }
 
-int tmr_d3s_fwd_bnstats(int n, int h, const float* x, const void* w_krsc, void* y, void* stats,
-                        hipStream_t stream) {
-  TMR_CHECK_ARG(n > 0 && h > 0 && h % 2 == 0, "tmr_d3s_fwd: unsupported height %d", h);
+constexpr int kGridS = 3 * 256;   // the forward's persistent workgroups, 4 statistics rows each
+int d3s_grid(const tmr_conv_desc* d) {
+  const int rows = d->n * d->ho;
+  return rows < kGridS ? rows : kGridS;
+}
+int d3s_parts(const tmr_conv_desc* d) { return 4 * d3s_grid(d); }
+
+int d3s_fwd(const tmr_conv_desc* d, const void* x, const void* w_krsc, void* y, void* stats,
+            hipStream_t stream) {
   TMR_CHECK_ARG((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "tmr_d3s_fwd: x / y must be 16-B aligned");
-  const int ho = h / 2, rows = n * ho, grid = rows < 3 * 256 ? rows : 3 * 256;
-  hipLaunchKernelGGL(d3s_k, dim3(grid), dim3(256), 0, stream, (const float4*)x,
-                     (const __bf16*)w_krsc, (__bf16*)y, (float4*)stats, h, ho, rows);
+  hipLaunchKernelGGL(d3s_k, dim3(d3s_grid(d)), dim3(256), 0, stream, (const float4*)x,
+                     (const __bf16*)w_krsc, (__bf16*)y, (float4*)stats, d->h, d->ho,
+                     d->n * d->ho);
   TMR_CHECK_LAUNCH("d3s_fwd");
   return 0;
 }
 
-size_t tmr_d3s_wgrad_ws_bytes(int n, int ho) {
-  const int rows = n * ho;
-  return (size_t)(rows < kGridW ? rows : kGridW) * 32 * 9 * 4 * sizeof(float);
+int d3s_wgrad(const tmr_conv_desc* d, const void* x, const void* dy, float* ws, size_t ws_bytes,
+              DirectSlabs* slabs, hipStream_t stream) {
+  TMR_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy) & 15) == 0, "tmr_d3s_wgrad: x / dy must be 16-B aligned");
+  const int rows = d->n * d->ho, grid = gridw_of(rows);
+  TMR_CHECK_ARG(ws && ws_bytes >= d3_ws_bytes(d), "tmr_d3s_wgrad: workspace too small");
+  hipLaunchKernelGGL(d3sw_k, dim3(grid), dim3(256), 0, stream, (const float4*)x, (const uint4*)dy,
+                     ws, d->h, d->ho, rows);
+  TMR_CHECK_LAUNCH("d3s_wgrad");
+  *slabs = {grid, wslab_of(d), 9, 4};
+  return 0;
 }
 
-int tmr_d3s_wgrad_slabs(int n, int h, const float* x, const void* dy, float* ws, size_t ws_bytes,
-                        int* nslabs, hipStream_t stream) {
-  TMR_CHECK_ARG(n > 0 && h > 0 && h % 2 == 0, "tmr_d3s_wgrad: unsupported height %d", h);
-  TMR_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy) & 15) == 0, "tmr_d3s_wgrad: x / dy must be 16-B aligned");
-  const int ho = h / 2, rows = n * ho, grid = rows < kGridW ? rows : kGridW;
-  TMR_CHECK_ARG(ws && ws_bytes >= tmr_d3s_wgrad_ws_bytes(n, ho), "tmr_d3s_wgrad: workspace too small");
-  hipLaunchKernelGGL(d3sw_k, dim3(grid), dim3(256), 0, stream, (const float4*)x, (const uint4*)dy,
-                     ws, h, ho, rows);
-  TMR_CHECK_LAUNCH("d3s_wgrad");
-  *nslabs = grid;
-  return 0;
+}  // namespace
+
+const DirectConv& tmr_direct_d3() {
+  static const DirectConv f = {{d3_fwd_serves, d3_fwd_parts, d3_fwd},
+                               {d3_dgrad_serves, d3_dgrad_parts, d3_dgrad},
+                               {d3_wgrad_serves, 0, d3_ws_bytes, d3_wgrad}};
+  return f;
+}
+const DirectConv& tmr_direct_d3s() {
+  static const DirectConv f = {{d3s_fwd_serves, d3s_parts, d3s_fwd},
+                               {},
+                               {d3s_wgrad_serves, 3, d3_ws_bytes, d3s_wgrad}};
+  return f;
 }

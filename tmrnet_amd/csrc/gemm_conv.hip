@@ -1,4 +1,5 @@
 // Implicit-GEMM convolution / GEMM engine: host side and C ABI (kernel template: gemm_kernel.h).
+#include "direct_conv.h"
 #include "gemm16_select.h"
 
 #include <type_traits>
@@ -46,11 +47,12 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ slabs, int nsplit,
 // The same reduction for multi-tap weights: one block per (co, 64-channel group) sums the splits
 // with reads along c (coalesced), transposes (tap, c) -> (c, tap) through LDS and writes OIHW rows
 // contiguously.  Per element the split order is the same as wgrad_reduce_kernel's.
+constexpr int kReduceTaps = 7 * 7;   // the most taps it takes (its LDS tile)
 __global__ __launch_bounds__(256) void wgrad_reduce_taps_kernel(const float* __restrict__ slabs,
                                                                 int nsplit, long slab,
                                                                 float* __restrict__ out, int ntaps,
                                                                 int Cpad, int creal, float beta) {
-  __shared__ float tile[49 * 64];   // ntaps <= 49 (7x7), checked on the host
+  __shared__ float tile[kReduceTaps * 64];   // ntaps <= kReduceTaps, checked on the host
   const int co = blockIdx.x;
   const int c0 = blockIdx.y * 64;
   const int nc = min(64, creal - c0);
@@ -76,8 +78,6 @@ int launch_gemm(const GemmArgs& a, bool al, int splits, hipStream_t st) {
   return launch_gemm_wgrad(a, al, splits, st);
 }
 
-static inline int xld_of(const tmr_conv_desc* d) { return d->x_ld ? d->x_ld : d->c; }
-static inline int yld_of(const tmr_conv_desc* d) { return d->y_ld ? d->y_ld : d->k; }
 static inline long span(long pixels, int ld, int width) { return pixels > 0 ? (pixels - 1) * ld + width : 0; }
 
 // element bytes of the conv operands (tmr_conv_desc.io: bf16-stored x / w / dy)
@@ -191,7 +191,6 @@ static long y_frame(const tmr_conv_desc* d) { return (long)d->ho * d->wo * yld_o
 // channel slices (pixel strides = the whole tensors').  Weights per group are consecutive blocks
 // of (k/G)*(c/G)*r*s elements: KRSC (k, r, s, c/G), the transposed copy (G, c/G, r, s, k/G), and
 // OIHW gradients (k, c/G, r, s), i.e. torch's grouped Conv2d weight layout.
-static int ngroups(const tmr_conv_desc* d) { return d->groups > 1 ? d->groups : 1; }
 static int group_split(const tmr_conv_desc* d, tmr_conv_desc& g) {
   const int G = ngroups(d);
   TMR_CHECK_ARG(d->c % G == 0 && d->k % G == 0, "tmr_conv2d: channels %d / %d not divisible by %d groups",
@@ -206,34 +205,52 @@ static int group_split(const tmr_conv_desc* d, tmr_conv_desc& g) {
 }
 static long group_wsize(const tmr_conv_desc* g) { return (long)g->k * g->r * g->s * g->c; }
 
+// One visit per (group, frame chunk) of a conv, groups outermost: body(slice, group, first frame),
+// slice = the group's channel-slice descriptor cut to the chunk's frames.  one_group: group 0
+// only (the planning queries: every group has the same tiling).
+template <typename F>
+static int for_slices(const tmr_conv_desc* d, F&& body, bool one_group = false) {
+  tmr_conv_desc g = *d;
+  if (ngroups(d) > 1 && group_split(d, g)) return 1;
+  const int fc = frames_per_launch(&g), G = one_group ? 1 : ngroups(d);
+  for (int i = 0; i < G; ++i)
+    for (int f0 = 0; f0 < g.n; f0 += fc) {
+      const int rc = body(chunk_desc(&g, g.n - f0 < fc ? g.n - f0 : fc), i, f0);
+      if (rc) return rc;
+    }
+  return 0;
+}
+// element offsets of a slice in the whole operands: x / dx, y / dy, the weights
+static long x_off(const tmr_conv_desc& c, int g, int f0) { return (long)g * c.c + f0 * x_frame(&c); }
+static long y_off(const tmr_conv_desc& c, int g, int f0) { return (long)g * c.k + f0 * y_frame(&c); }
+static long w_off(const tmr_conv_desc& c, int g) { return g * group_wsize(&c); }
+
+// The direct kernel families (direct_conv.h), in lookup order.  A geometry one of them serves
+// skips the engine; TMR_IO_ENGINE (tests) keeps every conv on the engine.
+static const DirectConv* const kDirect[] = {&tmr_direct_stem(), &tmr_direct_stem16(),
+                                            &tmr_direct_d3(), &tmr_direct_d3s()};
+template <typename V>
+static const V* direct_view(const tmr_conv_desc* d, V DirectConv::*view) {
+  if (d->io & TMR_IO_ENGINE) return nullptr;
+  for (const DirectConv* f : kDirect)
+    if ((f->*view).serves && (f->*view).serves(d)) return &(f->*view);
+  return nullptr;
+}
+
 TMR_API int tmr_conv2d_fwd(const tmr_conv_desc* d, const float* x, const float* w_krsc,
                            const float* bias, float* y, float beta, hipStream_t stream) {
   TMR_CHECK_ARG(d, "tmr_conv2d_fwd: null descriptor");
-  if (ngroups(d) > 1) {
-    tmr_conv_desc g;
-    if (group_split(d, g)) return 1;
-    for (int i = 0; i < d->groups; ++i) {
-      const int rc = tmr_conv2d_fwd(&g, adv(x, (long)i * g.c, esz_x(d)), adv(w_krsc, i * group_wsize(&g), esz_w(d)),
-                                    bias ? bias + (long)i * g.k : nullptr,
-                                    adv(y, (long)i * g.k, esz_y(d)), beta, stream);
-      if (rc) return rc;
-    }
-    return 0;
-  }
-  const int fc = frames_per_launch(d);
-  for (int f0 = 0; f0 < d->n; f0 += fc) {
-    const tmr_conv_desc c = chunk_desc(d, d->n - f0 < fc ? d->n - f0 : fc);
+  return for_slices(d, [&](const tmr_conv_desc& c, int g, int f0) -> int {
     GemmArgs a;
     bool al;
-    int rc = conv_fwd_args(&c, adv(x, f0 * x_frame(d), esz_x(d)), w_krsc, bias, adv(y, f0 * y_frame(d), esz_y(d)), beta, a, al);
-    if (!rc && a.c16 && (beta != 0.f || bias)) {
-      tmr_set_error("tmr_conv2d_fwd: a bf16 output (TMR_IO_Y_BF16) takes no beta / bias");
-      rc = 1;
-    }
-    if (!rc) rc = launch_gemm<MODE_FWD>(a, al, 1, stream);
+    const int rc = conv_fwd_args(&c, adv(x, x_off(c, g, f0), esz_x(d)), adv(w_krsc, w_off(c, g), esz_w(d)),
+                                 bias ? bias + (long)g * c.k : nullptr,
+                                 adv(y, y_off(c, g, f0), esz_y(d)), beta, a, al);
     if (rc) return rc;
-  }
-  return 0;
+    TMR_CHECK_ARG(!(a.c16 && (beta != 0.f || bias)),
+                  "tmr_conv2d_fwd: a bf16 output (TMR_IO_Y_BF16) takes no beta / bias");
+    return launch_gemm<MODE_FWD>(a, al, 1, stream);
+  });
 }
 
 TMR_API int tmr_conv2d_fwd_fused(const tmr_conv_desc* d, const float* x, const float* w_krsc,
@@ -242,29 +259,17 @@ TMR_API int tmr_conv2d_fwd_fused(const tmr_conv_desc* d, const float* x, const f
   TMR_CHECK_ARG(d, "tmr_conv2d_fwd_fused: null descriptor");
   TMR_CHECK_ARG(scale && shift, "tmr_conv2d_fwd_fused: null BatchNorm scale/shift");
   TMR_CHECK_ARG(!residual || residual != y, "tmr_conv2d_fwd_fused: residual must not alias y");
-  if (ngroups(d) > 1) {
-    TMR_CHECK_ARG(!(d->io & TMR_IO_Y_BF16), "tmr_conv2d_fwd_fused: a grouped conv writes fp32 (no TMR_IO_Y_BF16)");
-    tmr_conv_desc g;
-    if (group_split(d, g)) return 1;
-    for (int i = 0; i < d->groups; ++i) {
-      const long o = (long)i * g.k;
-      const int rc = tmr_conv2d_fwd_fused(&g, adv(x, (long)i * g.c, esz_x(d)),
-                                          adv(w_krsc, i * group_wsize(&g), esz_w(d)), scale + o,
-                                          shift + o, residual ? residual + o : nullptr, y + o, relu,
-                                          stream);
-      if (rc) return rc;
-    }
-    return 0;
-  }
-  const int fc = frames_per_launch(d);
-  for (int f0 = 0; f0 < d->n; f0 += fc) {
-    const tmr_conv_desc c = chunk_desc(d, d->n - f0 < fc ? d->n - f0 : fc);
+  TMR_CHECK_ARG(ngroups(d) == 1 || !(d->io & TMR_IO_Y_BF16),
+                "tmr_conv2d_fwd_fused: a grouped conv writes fp32 (no TMR_IO_Y_BF16)");
+  return for_slices(d, [&](const tmr_conv_desc& c, int g, int f0) -> int {
+    const long o = (long)g * c.k;
     GemmArgs a;
     bool al;
-    int rc = conv_fwd_args(&c, adv(x, f0 * x_frame(d), esz_x(d)), w_krsc, shift, adv(y, f0 * y_frame(d), esz_y(d)), 0.f, a, al);
+    const int rc = conv_fwd_args(&c, adv(x, x_off(c, g, f0), esz_x(d)), adv(w_krsc, w_off(c, g), esz_w(d)),
+                                 shift + o, adv(y, y_off(c, g, f0), esz_y(d)), 0.f, a, al);
     if (rc) return rc;
-    a.scale = scale;
-    a.res = adv(residual, f0 * y_frame(d), esz_y(d));
+    a.scale = scale + o;
+    a.res = adv(residual, y_off(c, g, f0), esz_y(d));
     a.relu = relu;
     if (a.c16) {
       // bf16 activations (TMR_IO_Y_BF16): y and the residual are bf16, moved as dwords of two
@@ -277,109 +282,8 @@ TMR_API int tmr_conv2d_fwd_fused(const tmr_conv_desc* d, const float* x, const f
                     "aligned y and residual");
       a.Cbytes = clamp_bytes_e(span((long)c.n * c.ho * c.wo, a.ldc, c.k), 2);
     }
-    rc = launch_gemm<MODE_FWD>(a, al, 1, stream);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
-// The fp32 7x7/2 stem with BatchNorm statistics runs as a direct convolution over its 147 real
-// (tap, channel) pairs (stem.hip): a partial row per output row and wave; its weight gradient too
-// (partial slabs per workgroup, reduced by wgrad_reduce_taps_kernel).  TMR_IO_ENGINE: the
-// implicit-GEMM engine (tests).
-int tmr_stem_stats_parts(int n, int ho);
-int tmr_stem_fwd_bnstats(int n, int h, int w, int ho, const float* x, const float* w_krsc,
-                         float* y, void* stats, hipStream_t stream);
-int tmr_stem_wgrad_slabs(int n, int h, int w, int ho, const float* x, const float* dy, float* ws,
-                         size_t ws_bytes, int* nslabs, hipStream_t stream);
-constexpr long kStemSlabs = 512, kStemSlab = 64 * 49 * 4;   // stem.hip's grid and slab
-constexpr long kStem16Slabs = 768;                            // stem16.hip's grid
-static bool stem_geometry(const tmr_conv_desc* d) {
-  return d->math == TMR_MATH_F32 && d->io == 0 &&
-         ngroups(d) == 1 && d->c == 4 && d->k == 64 && d->r == 7 && d->s == 7 && d->stride == 2 &&
-         d->pad == 3 && d->pad_w == 3 && d->wo == 112 && d->w <= 226 && xld_of(d) == 4 &&
-         yld_of(d) == 64;
-}
-static bool stem_direct(const tmr_conv_desc* d) {
-  return !(d->io & TMR_IO_ENGINE) && stem_geometry(d);
-}
-// the bf16-activation step's stem (stem16.hip): bf16 math on the NHWC4 fp32 input, bf16 KRSC
-// weights (4 or 8 channels per tap), y bf16 with the statistics of the rounded values
-int tmr_stem16_stats_parts(int n, int ho);
-int tmr_stem16_fwd_bnstats(int n, int h, int w, int ho, const float* x, const void* w_krsc, int cp,
-                           void* y, void* stats, hipStream_t stream);
-static bool stem16_geometry(const tmr_conv_desc* d) {
-  return d->math == TMR_MATH_BF16 && d->io == (TMR_IO_W_BF16 | TMR_IO_Y_BF16) &&
-         ngroups(d) == 1 && d->c == 4 && d->k == 64 && d->r == 7 && d->s == 7 && d->stride == 2 &&
-         d->pad == 3 && d->pad_w == 3 && d->wo == 112 && d->w <= 224 && xld_of(d) == 4 &&
-         yld_of(d) == 64 && (d->h + 6 - 7) / 2 + 1 == d->ho;
-}
-static bool stem16_direct(const tmr_conv_desc* d) {
-  return !(d->io & TMR_IO_ENGINE) && stem16_geometry(d);
-}
-// its weight gradient (bf16 dy, the NHWC4 fp32 input)
-int tmr_stem16_wgrad_slabs(int n, int h, int w, int ho, const float* x, const void* dy, int dy32,
-                           float* ws, size_t ws_bytes, int* nslabs, hipStream_t stream);
-// (dy bf16 or fp32: both storages of the bf16-math step take this kernel, so they stay
-// bit-identical)
-static bool stem16_wgrad_geometry(const tmr_conv_desc* d) {
-  return d->math == TMR_MATH_BF16 && (d->io == TMR_IO_DY_BF16 || d->io == 0) && ngroups(d) == 1 &&
-         d->c == 4 &&
-         d->k == 64 && d->r == 7 && d->s == 7 && d->stride == 2 && d->pad == 3 && d->pad_w == 3 &&
-         d->wo == 112 && d->w <= 224 && xld_of(d) == 4 && yld_of(d) == 64 &&
-         (d->h + 6 - 7) / 2 + 1 == d->ho;
-}
-
-// the narrow stride-1 3x3 convs of the bf16-activation step (ResNeSt-50's deep stem: 32 -> 32,
-// 32 -> 64 at 112x112) as direct convolutions over an LDS ring of input rows (direct3.hip); every
-// operand bf16 in HBM, dense NHWC.  TMR_IO_ENGINE: the implicit-GEMM engine (tests).
-int tmr_d3_stats_parts(int n, int h, int w, int cin, int cout);
-int tmr_d3_dgrad_parts(int n, int h, int w, int cin_conv, int cout_conv);
-size_t tmr_d3_wgrad_ws_bytes(int n, int h, int w, int cin, int cout);
-int tmr_d3_fwd_bnstats(int n, int h, int w, int cin, int cout, const void* x, const void* w_krsc,
-                       void* y, void* stats, hipStream_t stream);
-int tmr_d3_dgrad_bnbwd(int n, int h, int w, int cin_conv, int cout_conv, const void* dy,
-                       const void* w_crsk, void* dx, int g16, float beta, const void* y,
-                       const void* z, const float* scale, const float* shift, const float* mean,
-                       int mask, void* parts, hipStream_t stream);
-int tmr_d3_wgrad_slabs(int n, int h, int w, int cin, int cout, const void* x, const void* dy,
-                       float* ws, size_t ws_bytes, int* nslabs, hipStream_t stream);
-// (round 4, C5: ResNet-50 layer1's 64 -> 64 3x3 convs at 56x56 too)
-static bool d3_shape(const tmr_conv_desc* d) {
-  const bool wc = (d->w == 112 && d->c == 32 && (d->k == 32 || d->k == 64)) ||
-                  (d->w == 56 && d->c == 64 && d->k == 64);
-  return !(d->io & TMR_IO_ENGINE) && d->math == TMR_MATH_BF16 && ngroups(d) == 1 &&
-         d->r == 3 && d->s == 3 && d->stride == 1 && d->pad == 1 && d->pad_w == 1 && wc &&
-         d->wo == d->w && d->ho == d->h && xld_of(d) == d->c && yld_of(d) == d->k &&
-         d->max_frames == 0;
-}
-// ... and the deep stem's first conv, 3x3/2 3 -> 32, on the NHWC4 fp32 input (bf16 math)
-int tmr_d3s_stats_parts(int n, int ho);
-int tmr_d3s_fwd_bnstats(int n, int h, const float* x, const void* w_krsc, void* y, void* stats,
-                        hipStream_t stream);
-size_t tmr_d3s_wgrad_ws_bytes(int n, int ho);
-int tmr_d3s_wgrad_slabs(int n, int h, const float* x, const void* dy, float* ws, size_t ws_bytes,
-                        int* nslabs, hipStream_t stream);
-static bool d3s_shape(const tmr_conv_desc* d) {
-  return !(d->io & TMR_IO_ENGINE) && d->math == TMR_MATH_BF16 && ngroups(d) == 1 &&
-         d->c == 4 && d->k == 32 && d->r == 3 && d->s == 3 && d->stride == 2 && d->pad == 1 &&
-         d->pad_w == 1 && d->w == 224 && d->wo == 112 && d->h % 2 == 0 && d->ho == d->h / 2 &&
-         xld_of(d) == 4 && yld_of(d) == 32 && d->max_frames == 0;
-}
-static bool d3s_fwd(const tmr_conv_desc* d) {
-  return d3s_shape(d) && d->io == (TMR_IO_W_BF16 | TMR_IO_Y_BF16);
-}
-static bool d3s_wgrad(const tmr_conv_desc* d) { return d3s_shape(d) && d->io == TMR_IO_DY_BF16; }
-static bool d3_fwd(const tmr_conv_desc* d) {
-  return d3_shape(d) && d->io == (TMR_IO_X_BF16 | TMR_IO_W_BF16 | TMR_IO_Y_BF16);
-}
-static bool d3_dgrad(const tmr_conv_desc* d) {
-  const int io = d->io & ~TMR_IO_G16;   // (a bf16 masked gradient: the 56-wide convs)
-  return d3_shape(d) && io == (TMR_IO_DY_BF16 | TMR_IO_WT_BF16 | TMR_IO_BN_BF16) &&
-         (!(d->io & TMR_IO_G16) || d->w == 56);
-}
-static bool d3_wgrad(const tmr_conv_desc* d) {
-  return d3_shape(d) && d->io == (TMR_IO_X_BF16 | TMR_IO_DY_BF16);
+    return launch_gemm<MODE_FWD>(a, al, 1, stream);
+  });
 }
 
 TMR_API int tmr_conv2d_fwd_stats_parts(const tmr_conv_desc* d) {
@@ -387,40 +291,17 @@ TMR_API int tmr_conv2d_fwd_stats_parts(const tmr_conv_desc* d) {
     tmr_set_error("tmr_conv2d_fwd_stats_parts: null or empty descriptor");
     return -1;
   }
-  if (stem_direct(d)) return tmr_stem_stats_parts(d->n, d->ho);
-  if (stem16_direct(d)) return tmr_stem16_stats_parts(d->n, d->ho);
-  if (d3_fwd(d)) return tmr_d3_stats_parts(d->n, d->h, d->w, d->c, d->k);
-  if (d3s_fwd(d)) return tmr_d3s_stats_parts(d->n, d->ho);
-  tmr_conv_desc g = *d;
-  if (ngroups(d) > 1 && group_split(d, g)) return -1;   // every group has the same row tiling
-  const int fc = frames_per_launch(&g);
+  if (const auto* f = direct_view(d, &DirectConv::fwd)) return f->parts(d);
   int parts = 0;
-  for (int f0 = 0; f0 < g.n; f0 += fc) {
-    const tmr_conv_desc c = chunk_desc(&g, g.n - f0 < fc ? g.n - f0 : fc);
+  const auto count = [&](const tmr_conv_desc& c, int, int) {
     parts += stats_parts_of(&c);
-  }
-  return parts;
+    return 0;
+  };
+  return for_slices(d, count, true) ? -1 : parts;
 }
 
-// stats: partial rows of part_ld columns (this launch's k columns at the pointer)
-static int fwd_bnstats_impl(const tmr_conv_desc* d, const float* x, const float* w_krsc, float* y,
-                            float4* st, int part_ld, hipStream_t stream) {
-  const int fc = frames_per_launch(d);
-  for (int f0 = 0; f0 < d->n; f0 += fc) {
-    const tmr_conv_desc c = chunk_desc(d, d->n - f0 < fc ? d->n - f0 : fc);
-    GemmArgs a;
-    bool al;
-    int rc = conv_fwd_args(&c, adv(x, f0 * x_frame(d), esz_x(d)), w_krsc, nullptr, adv(y, f0 * y_frame(d), esz_y(d)), 0.f, a, al);
-    if (rc) return rc;
-    a.stats = st;
-    a.part_ld = part_ld;
-    rc = launch_gemm<MODE_FWD>(a, al, 1, stream);
-    if (rc) return rc;
-    st += (long)stats_parts_of(&c) * part_ld;
-  }
-  return 0;
-}
-
+// stats: partial rows of d->k columns, a group's k columns at its offset; the rows of a group's
+// frame chunks follow each other
 TMR_API int tmr_conv2d_fwd_bnstats(const tmr_conv_desc* d, const float* x, const float* w_krsc,
                                    float* y, void* stats, size_t stats_bytes, hipStream_t stream) {
   TMR_CHECK_ARG(d, "tmr_conv2d_fwd_bnstats: null descriptor");
@@ -430,23 +311,20 @@ TMR_API int tmr_conv2d_fwd_bnstats(const tmr_conv_desc* d, const float* x, const
   const size_t need = (size_t)np * d->k * sizeof(float4);
   TMR_CHECK_ARG(stats && stats_bytes >= need, "tmr_conv2d_fwd_bnstats: stats buffer too small (%zu < %zu)",
                 stats_bytes, need);
-  if (stem_direct(d))
-    return tmr_stem_fwd_bnstats(d->n, d->h, d->w, d->ho, x, w_krsc, y, stats, stream);
-  if (stem16_direct(d))
-    return tmr_stem16_fwd_bnstats(d->n, d->h, d->w, d->ho, x, w_krsc, 4, y, stats, stream);
-  if (d3_fwd(d))
-    return tmr_d3_fwd_bnstats(d->n, d->h, d->w, d->c, d->k, x, w_krsc, y, stats, stream);
-  if (d3s_fwd(d)) return tmr_d3s_fwd_bnstats(d->n, d->h, x, w_krsc, y, stats, stream);
-  if (ngroups(d) == 1) return fwd_bnstats_impl(d, x, w_krsc, y, (float4*)stats, d->k, stream);
-  tmr_conv_desc g;
-  if (group_split(d, g)) return 1;
-  for (int i = 0; i < d->groups; ++i) {
-    const int rc = fwd_bnstats_impl(&g, adv(x, (long)i * g.c, esz_x(d)), adv(w_krsc, i * group_wsize(&g), esz_w(d)),
-                                    adv(y, (long)i * g.k, esz_y(d)), (float4*)stats + (long)i * g.k,
-                                    d->k, stream);
+  if (const auto* f = direct_view(d, &DirectConv::fwd)) return f->run(d, x, w_krsc, y, stats, stream);
+  float4* st = nullptr;
+  return for_slices(d, [&](const tmr_conv_desc& c, int g, int f0) -> int {
+    if (f0 == 0) st = (float4*)stats + (long)g * c.k;
+    GemmArgs a;
+    bool al;
+    const int rc = conv_fwd_args(&c, adv(x, x_off(c, g, f0), esz_x(d)), adv(w_krsc, w_off(c, g), esz_w(d)),
+                                 nullptr, adv(y, y_off(c, g, f0), esz_y(d)), 0.f, a, al);
     if (rc) return rc;
-  }
-  return 0;
+    a.stats = st;
+    a.part_ld = d->k;
+    st += (long)stats_parts_of(&c) * d->k;
+    return launch_gemm<MODE_FWD>(a, al, 1, stream);
+  });
 }
 
 // Fused BatchNorm-backward epilogue state of one dgrad call (nullptr: plain dgrad).  part
@@ -560,28 +438,30 @@ static int conv_dgrad_impl(const tmr_conv_desc* d, const float* dy, const float*
   return 0;
 }
 
+// The fused dgrad over every slice of d; fz holds the whole operands (group 0, frame 0): y / z /
+// the old dx are laid out like dx, a group's scale / shift / mean and partial columns start at its
+// channels.  count_only: launches nothing and adds one group's partial rows to *nparts.
 static int dgrad_bnbwd_run(const tmr_conv_desc* d, const float* dy, const float* w_krsc, float* dx,
-                           float beta, BnBwdFuse* fz, hipStream_t stream) {
-  const int fc = frames_per_launch(d);
-  const long px_frame = (long)d->h * d->w * xld_of(d);   // y / z laid out like dx
-  float2* part0 = fz->part;
-  for (int f0 = 0; f0 < d->n; f0 += fc) {
-    const tmr_conv_desc c = chunk_desc(d, d->n - f0 < fc ? d->n - f0 : fc);
-    BnBwdFuse fc_ = *fz;
-    fc_.y = adv(fz->y, f0 * px_frame, esz_bn(d));
-    // mask 3: z is bits, 32 elements per word (px_frame % 32 == 0, checked by the caller)
-    fc_.z = fz->mask == 3 ? (const float*)((const uint32_t*)fz->z + f0 * px_frame / 32)
-                          : adv(fz->z, f0 * px_frame, esz_bn(d));
-    fc_.nparts = 0;
-    if (fz->old) fc_.old = adv(fz->old, f0 * x_frame(d), fz->old16 ? 2 : 4);
-    int rc = conv_dgrad_impl(&c, adv(dy, f0 * y_frame(d), esz_dy(d)), w_krsc,
-                             dx ? adv(dx, f0 * x_frame(d), esz_dx(d)) : nullptr, beta, stream, &fc_);
-    if (rc) return rc;
-    fz->part = fc_.part;
-    fz->nparts += fc_.nparts;
-  }
-  fz->part = part0;
-  return 0;
+                           float beta, const BnBwdFuse& fz, long* nparts, hipStream_t stream) {
+  float2* part = nullptr;
+  const auto slice = [&](const tmr_conv_desc& c, int g, int f0) -> int {
+    const long o = (long)g * c.c, px = x_off(c, g, f0);
+    if (f0 == 0) part = adv(fz.part, o, sizeof(float2));
+    BnBwdFuse s = fz;
+    s.y = adv(fz.y, px, esz_bn(d));
+    // mask 3: z is bits, 32 elements per word (ungrouped, h*w*c % 32 == 0: checked by the caller)
+    s.z = fz.mask == 3 ? (const float*)((const uint32_t*)fz.z + px / 32) : adv(fz.z, px, esz_bn(d));
+    s.sc = adv(fz.sc, o, 4); s.sh = adv(fz.sh, o, 4); s.mean = adv(fz.mean, o, 4);
+    s.old = adv(fz.old, px, fz.old16 ? 2 : 4);
+    s.part = part;
+    s.nparts = 0;
+    const int rc = conv_dgrad_impl(&c, adv(dy, y_off(c, g, f0), esz_dy(d)), adv(w_krsc, w_off(c, g), esz_w(d)),
+                                   adv(dx, px, esz_dx(d)), beta, stream, &s);
+    part = s.part;
+    if (nparts) *nparts += s.nparts;
+    return rc;
+  };
+  return for_slices(d, slice, fz.count_only);
 }
 
 long tmrg::g_dgrad_ws_launches = 0;
@@ -592,45 +472,12 @@ TMR_API int tmr_conv2d_dgrad_bnbwd_parts(const tmr_conv_desc* d) {
     tmr_set_error("tmr_conv2d_dgrad_bnbwd_parts: null or empty descriptor");
     return -1;
   }
-  if (d3_dgrad(d)) return tmr_d3_dgrad_parts(d->n, d->h, d->w, d->c, d->k);
-  tmr_conv_desc g = *d;
-  if (ngroups(d) > 1 && group_split(d, g)) return -1;   // every group has the same row tiling
+  if (const auto* f = direct_view(d, &DirectConv::dgrad)) return f->parts(d);
   BnBwdFuse fz{};
   fz.count_only = true;
-  fz.part_ld = g.c;
-  if (dgrad_bnbwd_run(&g, nullptr, nullptr, nullptr, 1.f, &fz, nullptr)) return -1;
-  return (int)fz.nparts;
-}
-
-static int dgrad_bnbwd_entry(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
-                             float* dx, float beta, const void* dx_old, int old_bf16,
-                             const float* y, const float* z, const float* scale,
-                             const float* shift, const float* mean, int mask, void* parts,
-                             size_t parts_bytes, hipStream_t stream);
-
-TMR_API int tmr_conv2d_dgrad_bnbwd(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
-                                   float* dx, float beta, const float* y, const float* z,
-                                   const float* scale, const float* shift, const float* mean,
-                                   int mask, void* parts, size_t parts_bytes, hipStream_t stream) {
-  TMR_CHECK_ARG(d, "tmr_conv2d_dgrad_bnbwd: null descriptor");
-  // in place: a bf16 gradient (TMR_IO_G16) accumulates into its own bf16 values
-  return dgrad_bnbwd_entry(d, dy, w_krsc, dx, beta, nullptr, (d->io & TMR_IO_G16) ? 1 : 0, y, z,
-                           scale, shift, mean, mask, parts, parts_bytes, stream);
-}
-
-TMR_API int tmr_conv2d_dgrad_bnbwd_acc(const tmr_conv_desc* d, const float* dy,
-                                       const float* w_krsc, void* dx, float beta,
-                                       const void* dx_old, int old_bf16, const float* y,
-                                       const float* z, const float* scale, const float* shift,
-                                       const float* mean, int mask, void* parts,
-                                       size_t parts_bytes, hipStream_t stream) {
-  TMR_CHECK_ARG(d, "tmr_conv2d_dgrad_bnbwd_acc: null descriptor");
-  TMR_CHECK_ARG(beta != 0.f && dx_old && ((uintptr_t)dx_old & 15) == 0 &&
-                    (d->io & TMR_IO_G16) && (d->io & TMR_IO_WT_BF16),
-                "tmr_conv2d_dgrad_bnbwd_acc: needs beta != 0, a 16-B aligned old dx and a bf16 "
-                "output (TMR_IO_G16) on the bf16 LDS-DMA engine (TMR_IO_WT_BF16)");
-  return dgrad_bnbwd_entry(d, dy, w_krsc, (float*)dx, beta, dx_old, old_bf16 ? 1 : 0, y, z, scale,
-                           shift, mean, mask, parts, parts_bytes, stream);
+  long np = 0;
+  if (dgrad_bnbwd_run(d, nullptr, nullptr, nullptr, 1.f, fz, &np, nullptr)) return -1;
+  return (int)np;
 }
 
 static int dgrad_bnbwd_entry(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
@@ -661,61 +508,54 @@ static int dgrad_bnbwd_entry(const tmr_conv_desc* d, const float* dy, const floa
   const int np = tmr_conv2d_dgrad_bnbwd_parts(d);
   TMR_CHECK_ARG(np >= 0 && parts_bytes >= (size_t)np * d->c * sizeof(float2),
                 "tmr_conv2d_dgrad_bnbwd: parts buffer too small");
-  if (d3_dgrad(d)) {   // (the parts query above counted the direct kernel's rows)
+  if (const auto* f = direct_view(d, &DirectConv::dgrad)) {   // (np counted the direct kernel's rows)
     TMR_CHECK_ARG(!dx_old && !((d->io & TMR_IO_G16) && beta != 0.f),
                   "tmr_conv2d_dgrad_bnbwd: the direct 3x3 dgrad takes no old dx / "
                   "accumulating bf16 gradient");
-    return tmr_d3_dgrad_bnbwd(d->n, d->h, d->w, d->c, d->k, dy, w_krsc, dx,
-                              (d->io & TMR_IO_G16) ? 1 : 0, beta, y, z, scale, shift, mean, mask,
-                              parts, stream);
-  }
-  if (ngroups(d) > 1) {
-    tmr_conv_desc g;
-    if (group_split(d, g)) return 1;
-    for (int i = 0; i < d->groups; ++i) {
-      const long o = (long)i * g.c;
-      BnBwdFuse fz{};
-      fz.y = adv(y, o, esz_bn(d)); fz.z = adv(z, o, esz_bn(d));
-      fz.sc = scale ? scale + o : nullptr; fz.sh = shift ? shift + o : nullptr; fz.mean = mean + o;
-      fz.mask = mask;
-      fz.part = (float2*)parts + o;
-      fz.part_ld = d->c;
-      fz.old16 = 0;   // (beta != 0 with a bf16 dx is rejected above)
-      const int rc = dgrad_bnbwd_run(&g, adv(dy, (long)i * g.k, esz_dy(d)), adv(w_krsc, i * group_wsize(&g), esz_w(d)),
-                                     adv(dx, o, esz_dx(d)), beta, &fz, stream);
-      if (rc) return rc;
-    }
-    return 0;
+    return f->run(d, dy, w_krsc, dx, beta, y, z, scale, shift, mean, mask, parts, stream);
   }
   BnBwdFuse fz{};
   fz.y = y; fz.z = z; fz.sc = scale; fz.sh = shift; fz.mean = mean; fz.mask = mask;
   fz.part = (float2*)parts;
-  fz.part_ld = d->c;
+  fz.part_ld = d->c;   // (the total channels of a grouped dgrad)
   fz.old = dx_old;
+  // (a grouped dgrad has no old dx, and beta != 0 with a bf16 dx is rejected above)
   fz.old16 = beta != 0.f ? old_bf16 : 0;
-  return dgrad_bnbwd_run(d, dy, w_krsc, dx, beta, &fz, stream);
+  return dgrad_bnbwd_run(d, dy, w_krsc, dx, beta, fz, nullptr, stream);
+}
+
+TMR_API int tmr_conv2d_dgrad_bnbwd(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
+                                   float* dx, float beta, const float* y, const float* z,
+                                   const float* scale, const float* shift, const float* mean,
+                                   int mask, void* parts, size_t parts_bytes, hipStream_t stream) {
+  TMR_CHECK_ARG(d, "tmr_conv2d_dgrad_bnbwd: null descriptor");
+  // in place: a bf16 gradient (TMR_IO_G16) accumulates into its own bf16 values
+  return dgrad_bnbwd_entry(d, dy, w_krsc, dx, beta, nullptr, (d->io & TMR_IO_G16) ? 1 : 0, y, z,
+                           scale, shift, mean, mask, parts, parts_bytes, stream);
+}
+
+TMR_API int tmr_conv2d_dgrad_bnbwd_acc(const tmr_conv_desc* d, const float* dy,
+                                       const float* w_krsc, void* dx, float beta,
+                                       const void* dx_old, int old_bf16, const float* y,
+                                       const float* z, const float* scale, const float* shift,
+                                       const float* mean, int mask, void* parts,
+                                       size_t parts_bytes, hipStream_t stream) {
+  TMR_CHECK_ARG(d, "tmr_conv2d_dgrad_bnbwd_acc: null descriptor");
+  TMR_CHECK_ARG(beta != 0.f && dx_old && ((uintptr_t)dx_old & 15) == 0 &&
+                    (d->io & TMR_IO_G16) && (d->io & TMR_IO_WT_BF16),
+                "tmr_conv2d_dgrad_bnbwd_acc: needs beta != 0, a 16-B aligned old dx and a bf16 "
+                "output (TMR_IO_G16) on the bf16 LDS-DMA engine (TMR_IO_WT_BF16)");
+  return dgrad_bnbwd_entry(d, dy, w_krsc, (float*)dx, beta, dx_old, old_bf16 ? 1 : 0, y, z, scale,
+                           shift, mean, mask, parts, parts_bytes, stream);
 }
 
 TMR_API int tmr_conv2d_dgrad(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
                              float* dx, float beta, hipStream_t stream) {
   TMR_CHECK_ARG(d, "tmr_conv2d_dgrad: null descriptor");
-  if (ngroups(d) > 1) {
-    tmr_conv_desc g;
-    if (group_split(d, g)) return 1;
-    for (int i = 0; i < d->groups; ++i) {
-      const int rc = tmr_conv2d_dgrad(&g, adv(dy, (long)i * g.k, esz_dy(d)), adv(w_krsc, i * group_wsize(&g), esz_w(d)),
-                                      dx + (long)i * g.c, beta, stream);
-      if (rc) return rc;
-    }
-    return 0;
-  }
-  const int fc = frames_per_launch(d);
-  for (int f0 = 0; f0 < d->n; f0 += fc) {
-    const tmr_conv_desc c = chunk_desc(d, d->n - f0 < fc ? d->n - f0 : fc);
-    int rc = conv_dgrad_impl(&c, adv(dy, f0 * y_frame(d), esz_dy(d)), w_krsc, dx + f0 * x_frame(d), beta, stream);
-    if (rc) return rc;
-  }
-  return 0;
+  return for_slices(d, [&](const tmr_conv_desc& c, int g, int f0) {
+    return conv_dgrad_impl(&c, adv(dy, y_off(c, g, f0), esz_dy(d)), adv(w_krsc, w_off(c, g), esz_w(d)),
+                           dx + x_off(c, g, f0), beta, stream);
+  });
 }
 
 // the WGRAD view of a conv (no pointers, no split plan)
@@ -758,65 +598,31 @@ static int wgrad_plan(const tmr_conv_desc* d, int* splits, int* kchunk, long* sl
   return 0;
 }
 
+// the direct wgrad of a conv with c_real real input channels (0: any, the workspace query)
+static const DirectConv::Wgrad* direct_wgrad(const tmr_conv_desc* d, int c_real) {
+  const DirectConv::Wgrad* f = direct_view(d, &DirectConv::wgrad);
+  return f && (c_real == 0 || f->c_real == 0 || f->c_real == c_real) ? f : nullptr;
+}
+
 TMR_API size_t tmr_conv2d_wgrad_ws_bytes(const tmr_conv_desc* d) {
   if (!d || d->n <= 0 || d->k <= 0 || d->c <= 0 || d->r <= 0 || d->s <= 0) {
     tmr_set_error("tmr_conv2d_wgrad_ws_bytes: null or empty descriptor");
     return 0;
   }
-  tmr_conv_desc g = *d;
-  if (ngroups(d) > 1 && group_split(d, g)) return 0;   // one group's workspace, reused in turn
-  int sp, kc;
-  long slab;
-  // the plans of the two chunk sizes a launch runs (the largest, and the remainder): a smaller
-  // chunk can keep more splits (its chunk length rounds up less)
-  const int fc = frames_per_launch(&g);
-  const tmr_conv_desc c = chunk_desc(&g, fc < g.n ? fc : g.n);
-  wgrad_plan(&c, &sp, &kc, &slab);
-  size_t bytes = (size_t)sp * slab * sizeof(float);
-  if (g.n > fc && g.n % fc != 0) {
-    const tmr_conv_desc cr = chunk_desc(&g, g.n % fc);
-    wgrad_plan(&cr, &sp, &kc, &slab);
+  // one group's workspace, reused in turn: the largest plan of its frame chunks (a smaller chunk
+  // can keep more splits: its chunk length rounds up less)
+  size_t bytes = 0;
+  const auto plan = [&](const tmr_conv_desc& c, int, int) {
+    int sp, kc;
+    long slab;
+    wgrad_plan(&c, &sp, &kc, &slab);
     if ((size_t)sp * slab * sizeof(float) > bytes) bytes = (size_t)sp * slab * sizeof(float);
-  }
-  if (stem_geometry(d) && bytes < (size_t)kStemSlabs * kStemSlab * sizeof(float))
-    bytes = (size_t)kStemSlabs * kStemSlab * sizeof(float);
-  if (stem16_wgrad_geometry(d) && bytes < (size_t)kStem16Slabs * kStemSlab * sizeof(float))
-    bytes = (size_t)kStem16Slabs * kStemSlab * sizeof(float);
-  if (d3_wgrad(d) && bytes < tmr_d3_wgrad_ws_bytes(d->n, d->h, d->w, d->c, d->k))
-    bytes = tmr_d3_wgrad_ws_bytes(d->n, d->h, d->w, d->c, d->k);
-  if (d3s_wgrad(d) && bytes < tmr_d3s_wgrad_ws_bytes(d->n, d->ho))
-    bytes = tmr_d3s_wgrad_ws_bytes(d->n, d->ho);
-  return bytes;
-}
-
-static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* dy,
-                           float* dw_oihw, int c_real, float beta, float* ws, size_t ws_bytes,
-                           hipStream_t stream);
-
-// frame chunks accumulate into dw in chunk order (beta = 1 after the first): deterministic
-TMR_API int tmr_conv2d_wgrad(const tmr_conv_desc* d, const float* x, const float* dy,
-                             float* dw_oihw, int c_real, float beta, float* ws, size_t ws_bytes,
-                             hipStream_t stream) {
-  TMR_CHECK_ARG(d, "tmr_conv2d_wgrad: null descriptor");
-  if (ngroups(d) > 1) {   // c_real = real input channels per group; dw (k, c_real, r, s)
-    tmr_conv_desc g;
-    if (group_split(d, g)) return 1;
-    for (int i = 0; i < d->groups; ++i) {
-      const int rc = tmr_conv2d_wgrad(&g, adv(x, (long)i * g.c, esz_x(d)), adv(dy, (long)i * g.k, esz_dy(d)),
-                                      dw_oihw + (long)i * g.k * c_real * g.r * g.s, c_real,
-                                      beta, ws, ws_bytes, stream);
-      if (rc) return rc;
-    }
     return 0;
-  }
-  const int fc = frames_per_launch(d);
-  for (int f0 = 0; f0 < d->n; f0 += fc) {
-    const tmr_conv_desc c = chunk_desc(d, d->n - f0 < fc ? d->n - f0 : fc);
-    int rc = conv_wgrad_impl(&c, adv(x, f0 * x_frame(d), esz_x(d)), adv(dy, f0 * y_frame(d), esz_dy(d)), dw_oihw, c_real,
-                             f0 == 0 ? beta : 1.f, ws, ws_bytes, stream);
-    if (rc) return rc;
-  }
-  return 0;
+  };
+  if (for_slices(d, plan, true)) return 0;
+  if (const auto* f = direct_wgrad(d, 0))
+    if (bytes < f->ws_bytes(d)) bytes = f->ws_bytes(d);
+  return bytes;
 }
 
 static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* dy,
@@ -826,34 +632,12 @@ static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* 
   const int lc = ilog2_exact(d->c);
   TMR_CHECK_ARG(lc >= 2, "tmr_conv2d_wgrad: stored input channels %d must be a power of two >= 4", d->c);
   TMR_CHECK_ARG(c_real >= 1 && c_real <= d->c, "tmr_conv2d_wgrad: bad c_real %d", c_real);
-  const bool s16 = c_real == 3 && !(d->io & TMR_IO_ENGINE) && stem16_wgrad_geometry(d);
-  if (s16 || (c_real == 3 && stem_direct(d))) {
-    int ns = 0;
-    const int rc = s16 ? tmr_stem16_wgrad_slabs(d->n, d->h, d->w, d->ho, x, dy,
-                                                (d->io & TMR_IO_DY_BF16) ? 0 : 1, ws, ws_bytes,
-                                                &ns, stream)
-                       : tmr_stem_wgrad_slabs(d->n, d->h, d->w, d->ho, x, dy, ws, ws_bytes, &ns, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3(d->k, 1), dim3(256), 0, stream, ws, ns,
-                       kStemSlab, dw_oihw, 49, 4, 3, beta);
-    TMR_CHECK_LAUNCH("wgrad_reduce_taps_kernel");
-    return 0;
-  }
-  if (c_real == 3 && d3s_wgrad(d)) {
-    int ns = 0;
-    const int rc = tmr_d3s_wgrad_slabs(d->n, d->h, x, dy, ws, ws_bytes, &ns, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3(d->k, 1), dim3(256), 0, stream, ws, ns,
-                       (long)32 * 9 * 4, dw_oihw, 9, 4, 3, beta);
-    TMR_CHECK_LAUNCH("wgrad_reduce_taps_kernel");
-    return 0;
-  }
-  if (d3_wgrad(d)) {
-    int ns = 0;
-    const int rc = tmr_d3_wgrad_slabs(d->n, d->h, d->w, d->c, d->k, x, dy, ws, ws_bytes, &ns, stream);
+  if (const auto* f = direct_wgrad(d, c_real)) {   // the family's partial slabs, reduced here
+    DirectSlabs sl{};
+    const int rc = f->run(d, x, dy, ws, ws_bytes, &sl, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3(d->k, cdiv(c_real, 64)), dim3(256), 0, stream,
-                       ws, ns, (long)d->k * 9 * d->c, dw_oihw, 9, d->c, c_real, beta);
+                       ws, sl.n, sl.elems, dw_oihw, sl.taps, sl.cstored, c_real, beta);
     TMR_CHECK_LAUNCH("wgrad_reduce_taps_kernel");
     return 0;
   }
@@ -865,7 +649,6 @@ static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* 
                 (size_t)sp * slab * sizeof(float));
   GemmArgs a;
   wgrad_fill(d, a);
-  (void)lc;
   a.A = dy; a.B = x; a.C = ws; a.bias = nullptr;
   a.kchunk = kc; a.slab = slab;
   a.Cbytes = clamp_bytes(slab);
@@ -873,7 +656,7 @@ static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* 
   const int rc = launch_gemm<MODE_WGRAD>(a, al, sp, stream);
   if (rc) return rc;
   const int ntaps = d->r * d->s;
-  if (ntaps > 1 && ntaps <= 49) {
+  if (ntaps > 1 && ntaps <= kReduceTaps) {
     hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3(d->k, cdiv(c_real, 64)), dim3(256), 0,
                        stream, ws, sp, slab, dw_oihw, ntaps, d->c, c_real, beta);
     TMR_CHECK_LAUNCH("wgrad_reduce_taps_kernel");
@@ -886,6 +669,19 @@ static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* 
                      dw_oihw, d->k, ntaps, d->c, c_real, beta);
   TMR_CHECK_LAUNCH("wgrad_reduce_kernel");
   return 0;
+}
+
+// frame chunks accumulate into dw in chunk order (beta = 1 after the first): deterministic; the
+// groups reuse the workspace in turn (c_real = real input channels per group; dw (k, c_real, r, s))
+TMR_API int tmr_conv2d_wgrad(const tmr_conv_desc* d, const float* x, const float* dy,
+                             float* dw_oihw, int c_real, float beta, float* ws, size_t ws_bytes,
+                             hipStream_t stream) {
+  TMR_CHECK_ARG(d, "tmr_conv2d_wgrad: null descriptor");
+  return for_slices(d, [&](const tmr_conv_desc& c, int g, int f0) {
+    return conv_wgrad_impl(&c, adv(x, x_off(c, g, f0), esz_x(d)), adv(dy, y_off(c, g, f0), esz_dy(d)),
+                           dw_oihw + (long)g * c.k * c_real * c.r * c.s, c_real,
+                           f0 == 0 ? beta : 1.f, ws, ws_bytes, stream);
+  });
 }
 
 // Plain GEMMs on the same engine ---------------------------------------------

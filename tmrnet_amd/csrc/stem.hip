@@ -19,7 +19,7 @@
 //     the conv epilogue's statistics format, combined by tmr_bn_finalize -- with no cross-wave
 //     exchange, so a row needs a single barrier.
 #include "common.h"
-#include "tmr.h"
+#include "direct_conv.h"
 
 namespace {
 
@@ -279,44 +279,60 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad_k(const float* __restrict__
 
 }  // namespace
 
-// tmr_conv2d_fwd_bnstats for the stem geometry (gemm_conv.hip routes it here): x NHWC4 fp32
-// (n, h, w, 4) with the 4th channel ignored, w KRSC (64, 7, 7, 4) fp32, stride 2, pad 3, output
-// width 112; one BatchNorm partial row per wave of the grid (tmr_stem_stats_parts rows of 64).
-int tmr_stem_stats_parts(int n, int ho) {
-  const int rows = n * ho;
-  return 4 * (rows < GRID ? rows : GRID);
+// ---- host side: the family's entry in gemm_conv.hip's routing table (direct_conv.h) ----
+namespace {
+
+// x NHWC4 fp32 (n, h, w, 4) with the 4th channel ignored, w KRSC (64, 7, 7, 4) fp32, every operand
+// fp32; the patch image holds 2 * XHALF padded columns
+bool stem_serves(const tmr_conv_desc* d) {
+  return d->math == TMR_MATH_F32 && d->io == 0 && stem7_shape(d) && d->wo == SW &&
+         2 * XHALF >= d->w + 6;
 }
 
-int tmr_stem_fwd_bnstats(int n, int h, int w, int ho, const float* x, const float* w_krsc,
-                         float* y, void* stats, hipStream_t stream) {
-  TMR_CHECK_ARG(n > 0 && ho > 0 && (w + 6 - 7) / 2 + 1 == SW && 2 * XHALF >= w + 6,
-                "tmr_stem_fwd_bnstats: unsupported geometry %dx%d", h, w);
+// persistent: two workgroups per CU (LDS), each over a strided sequence of output rows (the
+// weights are staged once per workgroup)
+int stem_grid(const tmr_conv_desc* d) {
+  const int rows = d->n * d->ho;
+  return rows < GRID ? rows : GRID;
+}
+
+// one BatchNorm partial row (of 64) per wave of the grid
+int stem_parts(const tmr_conv_desc* d) { return 4 * stem_grid(d); }
+
+int stem_fwd(const tmr_conv_desc* d, const void* x, const void* w_krsc, void* y, void* stats,
+             hipStream_t stream) {
   TMR_CHECK_ARG((((uintptr_t)x | (uintptr_t)w_krsc) & 15) == 0,
                 "tmr_stem_fwd_bnstats: x / w must be 16-B aligned");
-  // persistent: two workgroups per CU (LDS), each over a strided sequence of output rows (the
-  // weights are staged once per workgroup)
-  const int rows = n * ho;
-  const int grid = rows < GRID ? rows : GRID;
-  hipLaunchKernelGGL(stem_fwd_k, dim3(grid), dim3(256), 0, stream, x, w_krsc, y,
-                     (float4*)stats, h, w, ho, rows);
+  hipLaunchKernelGGL(stem_fwd_k, dim3(stem_grid(d)), dim3(256), 0, stream, (const float*)x,
+                     (const float*)w_krsc, (float*)y, (float4*)stats, d->h, d->w, d->ho,
+                     d->n * d->ho);
   TMR_CHECK_LAUNCH("stem_fwd");
   return 0;
 }
 
-// Stem weight gradient (gemm_conv.hip routes the fp32 stem here): partial slabs of the engine's
-// wgrad layout (64 x 49 x 4 floats, channel 3 not written) into ws, one per workgroup; *nslabs
-// = their number (the caller reduces them).
-int tmr_stem_wgrad_slabs(int n, int h, int w, int ho, const float* x, const float* dy, float* ws,
-                         size_t ws_bytes, int* nslabs, hipStream_t stream) {
-  TMR_CHECK_ARG(n > 0 && ho > 0 && (w + 6 - 7) / 2 + 1 == SW && 2 * XHALF >= w + 6,
-                "tmr_stem_wgrad: unsupported geometry %dx%d", h, w);
+// Weight gradient: partial slabs of the engine's wgrad layout (64 x 49 x 4 floats, channel 3 not
+// written), one per workgroup
+constexpr long SLAB = 64 * 49 * 4;
+size_t stem_ws_bytes(const tmr_conv_desc*) { return (size_t)GRID * SLAB * sizeof(float); }
+
+int stem_wgrad(const tmr_conv_desc* d, const void* x, const void* dy, float* ws, size_t ws_bytes,
+               DirectSlabs* slabs, hipStream_t stream) {
   TMR_CHECK_ARG(((uintptr_t)x & 15) == 0, "tmr_stem_wgrad: x must be 16-B aligned");
-  const int rows = n * ho;
-  const int grid = rows < GRID ? rows : GRID;
-  TMR_CHECK_ARG(ws && ws_bytes >= (size_t)grid * 64 * 49 * 4 * sizeof(float),
+  const int grid = stem_grid(d);
+  TMR_CHECK_ARG(ws && ws_bytes >= (size_t)grid * SLAB * sizeof(float),
                 "tmr_stem_wgrad: workspace too small (%zu)", ws_bytes);
-  hipLaunchKernelGGL(stem_wgrad_k, dim3(grid), dim3(256), 0, stream, x, dy, ws, h, w, ho, rows);
+  hipLaunchKernelGGL(stem_wgrad_k, dim3(grid), dim3(256), 0, stream, (const float*)x,
+                     (const float*)dy, ws, d->h, d->w, d->ho, d->n * d->ho);
   TMR_CHECK_LAUNCH("stem_wgrad");
-  *nslabs = grid;
+  *slabs = {grid, SLAB, 49, 4};
   return 0;
+}
+
+}  // namespace
+
+const DirectConv& tmr_direct_stem() {
+  static const DirectConv f = {{stem_serves, stem_parts, stem_fwd},
+                               {},
+                               {stem_serves, 3, stem_ws_bytes, stem_wgrad}};
+  return f;
 }

@@ -19,7 +19,7 @@
 //     double, fixed row order), one partial row per wave of the grid (4 * grid rows, not 4 per
 //     output row: ADVICE r3).
 #include "common.h"
-#include "tmr.h"
+#include "direct_conv.h"
 
 namespace {
 
@@ -380,46 +380,70 @@ __global__ __launch_bounds__(256, 3) void stem16_wgrad_k(const float* __restrict
 
 }  // namespace
 
-int tmr_stem16_wgrad_slabs(int n, int h, int w, int ho, const float* x, const void* dy, int dy32,
-                           float* ws, size_t ws_bytes, int* nslabs, hipStream_t stream) {
-  TMR_CHECK_ARG(n > 0 && ho > 0 && (w + 6 - 7) / 2 + 1 == SW && w + 6 <= 230 &&
-                    (h + 6 - 7) / 2 + 1 == ho,
-                "tmr_stem16_wgrad: unsupported geometry %dx%d", h, w);
-  TMR_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy) & 15) == 0, "tmr_stem16_wgrad: x / dy must be 16-B aligned");
-  const int rows = n * ho;
-  const int grid = rows < GRID16 ? rows : GRID16;
-  TMR_CHECK_ARG(ws && ws_bytes >= (size_t)grid * 64 * 49 * 4 * sizeof(float),
-                "tmr_stem16_wgrad: workspace too small (%zu)", ws_bytes);
-  if (dy32)
-    hipLaunchKernelGGL(stem16_wgrad_k<true>, dim3(grid), dim3(256), 0, stream, x, dy, ws, h, w, ho,
-                       rows);
-  else
-    hipLaunchKernelGGL(stem16_wgrad_k<false>, dim3(grid), dim3(256), 0, stream, x, dy, ws, h, w, ho,
-                       rows);
-  TMR_CHECK_LAUNCH("stem16_wgrad");
-  *nslabs = grid;
-  return 0;
+// ---- host side: the family's entry in gemm_conv.hip's routing table (direct_conv.h) ----
+namespace {
+
+// bf16 math on the NHWC4 fp32 input; the patch row (XROW) holds 230 padded columns
+bool stem16_shape(const tmr_conv_desc* d) {
+  return d->math == TMR_MATH_BF16 && stem7_shape(d) && d->wo == SW && d->w + 6 <= 230;
+}
+// forward: bf16 KRSC weights (64, 7, 7, 4), y (n, ho, 112, 64) bf16 with the statistics of the
+// rounded values
+bool stem16_fwd_serves(const tmr_conv_desc* d) {
+  return stem16_shape(d) && d->io == (TMR_IO_W_BF16 | TMR_IO_Y_BF16);
+}
+// wgrad: dy bf16 or fp32 (both storages of the bf16-math step take this kernel, so they stay
+// bit-identical)
+bool stem16_wgrad_serves(const tmr_conv_desc* d) {
+  return stem16_shape(d) && (d->io == TMR_IO_DY_BF16 || d->io == 0);
 }
 
-// Partial statistics rows of tmr_stem16_fwd_bnstats: 4 per workgroup of its grid
-int tmr_stem16_stats_parts(int n, int ho) {
-  const int rows = n * ho;
-  return 4 * (rows < GRID16 ? rows : GRID16);
+// persistent workgroups, each over a strided sequence of output rows
+int stem16_grid(const tmr_conv_desc* d) {
+  const int rows = d->n * d->ho;
+  return rows < GRID16 ? rows : GRID16;
 }
 
-// x NHWC4 fp32 (n, h, w, 4), the 4th channel ignored; w KRSC (64, 7, 7, cp) bf16 (cp = 4 or 8);
-// y (n, ho, 112, 64) bf16; stats: tmr_stem16_stats_parts rows of 64 float4 (n, mean, M2, 0).
-int tmr_stem16_fwd_bnstats(int n, int h, int w, int ho, const float* x, const void* w_krsc, int cp,
-                           void* y, void* stats, hipStream_t stream) {
-  TMR_CHECK_ARG(n > 0 && ho > 0 && (w + 6 - 7) / 2 + 1 == SW && w + 6 <= 230 &&
-                    (h + 6 - 7) / 2 + 1 == ho && (cp == 4 || cp == 8),
-                "tmr_stem16_fwd_bnstats: unsupported geometry %dx%d (cp %d)", h, w, cp);
+// 4 partial statistics rows (of 64 float4: n, mean, M2, 0) per workgroup
+int stem16_parts(const tmr_conv_desc* d) { return 4 * stem16_grid(d); }
+
+int stem16_fwd(const tmr_conv_desc* d, const void* x, const void* w_krsc, void* y, void* stats,
+               hipStream_t stream) {
   TMR_CHECK_ARG((((uintptr_t)x | (uintptr_t)y) & 15) == 0 && ((uintptr_t)w_krsc & 1) == 0,
                 "tmr_stem16_fwd_bnstats: x / y must be 16-B aligned");
-  const int rows = n * ho;
-  const int grid = rows < GRID16 ? rows : GRID16;
-  hipLaunchKernelGGL(stem16_fwd_k, dim3(grid), dim3(256), 0, stream, x, (const __bf16*)w_krsc, cp,
-                     (__bf16*)y, (float4*)stats, h, w, ho, rows);
+  hipLaunchKernelGGL(stem16_fwd_k, dim3(stem16_grid(d)), dim3(256), 0, stream, (const float*)x,
+                     (const __bf16*)w_krsc, d->c, (__bf16*)y, (float4*)stats, d->h, d->w, d->ho,
+                     d->n * d->ho);
   TMR_CHECK_LAUNCH("stem16_fwd");
   return 0;
+}
+
+// partial slabs of the engine's wgrad layout (64 x 49 x 4 floats), one per workgroup
+constexpr long SLAB = 64 * 49 * 4;
+size_t stem16_ws_bytes(const tmr_conv_desc*) { return (size_t)GRID16 * SLAB * sizeof(float); }
+
+int stem16_wgrad(const tmr_conv_desc* d, const void* x, const void* dy, float* ws, size_t ws_bytes,
+                 DirectSlabs* slabs, hipStream_t stream) {
+  TMR_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy) & 15) == 0, "tmr_stem16_wgrad: x / dy must be 16-B aligned");
+  const int grid = stem16_grid(d), rows = d->n * d->ho;
+  TMR_CHECK_ARG(ws && ws_bytes >= (size_t)grid * SLAB * sizeof(float),
+                "tmr_stem16_wgrad: workspace too small (%zu)", ws_bytes);
+  if (!(d->io & TMR_IO_DY_BF16))   // fp32 dy
+    hipLaunchKernelGGL(stem16_wgrad_k<true>, dim3(grid), dim3(256), 0, stream, (const float*)x, dy,
+                       ws, d->h, d->w, d->ho, rows);
+  else
+    hipLaunchKernelGGL(stem16_wgrad_k<false>, dim3(grid), dim3(256), 0, stream, (const float*)x, dy,
+                       ws, d->h, d->w, d->ho, rows);
+  TMR_CHECK_LAUNCH("stem16_wgrad");
+  *slabs = {grid, SLAB, 49, 4};
+  return 0;
+}
+
+}  // namespace
+
+const DirectConv& tmr_direct_stem16() {
+  static const DirectConv f = {{stem16_fwd_serves, stem16_parts, stem16_fwd},
+                               {},
+                               {stem16_wgrad_serves, 3, stem16_ws_bytes, stem16_wgrad}};
+  return f;
 }
