@@ -213,7 +213,9 @@ int tmr_clip_augment(const uint8_t* frames, const tmr_clip_aug* params, int32_t*
 /* ---------------- batch norm + ReLU + residual (bn.hip) ---------------------
  * Replaces nn.BatchNorm2d (train mode, batch statistics, eps, momentum) + ReLU +
  * the bottleneck residual add of torchvision resnet50.  ws: double workspace of
- * tmr_bn_ws_bytes(rows, c) bytes. */
+ * tmr_bn_ws_bytes(rows, c) bytes.  The entry points that reduce over the rows of y themselves
+ * (tmr_bn_fwd_stats, tmr_bn_bwd*, tmr_bn_bwd_maxpool*, tmr_bn_bwd_parts_ds; not the ones that only
+ * combine partials) take c / 4 <= 64 or c a multiple of 256 and refuse any other channel count. */
 size_t tmr_bn_ws_bytes(int rows, int c);
 /* batch stats of y -> save_mean, save_invstd, scale=gamma*invstd, shift=beta-mean*scale;
  * running stats updated in place (unbiased var), PyTorch semantics */

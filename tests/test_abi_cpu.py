@@ -95,6 +95,38 @@ def test_argument_errors_raise_with_message(built):
     assert _lib.query("tmr_lstm_ws_bytes", 64, 10, 2048, 512) > 0
 
 
+def test_bn_reductions_refuse_uncovered_channel_counts(built):
+    """The BatchNorm reductions run (c/4) / 64 blocks of 64 channel threads (make_plan, bn.hip): a
+    channel count such as 320 would leave channels 256..319 without partials, so every entry point
+    that reduces that way refuses it by name -- before the workspace check, with null operands and
+    before any launch -- as tmr_bn_fwd_stats does."""
+    from tmrnet_amd import _lib
+    N = None
+    c = 320
+    pool = (1, 4, 4, 2, 2)      # n, h, w, ho, wo of a valid MaxPool2d(3, 2, 1)
+    cases = [
+        ("tmr_bn_fwd_stats", (N, 64, c, N, N, N, N, 0.1, 1e-5, N, N, N, N, N, 0, N)),
+        ("tmr_bn_bwd", (*[N] * 12, 64, c, 0, N, 0, N)),
+        ("tmr_bn_bwd_x", (*[N] * 12, 64, c, 0, N, 0, 0, N)),
+        ("tmr_bn_bwd_x", (*[N] * 12, 64, c, 1, N, 0, 1, N)),
+        ("tmr_bn_bwd_a16", (*[N] * 12, 64, c, 0, N, 0, N)),
+        ("tmr_bn_bwd_g16", (*[N] * 8, 64, c, N, 0, N)),
+        ("tmr_bn_bwd_maxpool", (N, N, *pool, *[N] * 9, c, N, 0, N)),
+        ("tmr_bn_bwd_maxpool_x", (N, N, *pool, *[N] * 9, c, N, 0, 0, N)),
+        ("tmr_bn_bwd_maxpool_x", (N, N, *pool, *[N] * 9, c, N, 0, 1, N)),
+        ("tmr_bn_bwd_maxpool_a16", (N, N, *pool, *[N] * 9, c, N, 0, N)),
+        ("tmr_bn_bwd_parts_ds", (N, N, N, 3, *[N] * 13, 64, c, 0, N, 0, N)),
+        ("tmr_bn_bwd_parts_ds", (N, N, N, 3, *[N] * 13, 64, c, 1, N, 0, N)),
+    ]
+    for name, args in cases:
+        with pytest.raises(RuntimeError, match="unsupported channel count 320"):
+            _lib.call(name, *args)
+    # the counts the plan covers still get past that check (to the workspace one)
+    for ok in (4, 12, 24, 64, 256, 2048):
+        with pytest.raises(RuntimeError, match="workspace too small"):
+            _lib.call("tmr_bn_bwd_x", *[N] * 12, 64, ok, 0, N, 0, 0, N)
+
+
 def test_stem_entry_points_host_checks(built):
     """The direct stem's host-side contract (no GPU work): the wgrad workspace query covers the
     direct kernel's 512 partial slabs at the stem geometry (direct or on the engine), and

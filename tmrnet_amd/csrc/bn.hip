@@ -39,6 +39,14 @@ Plan make_plan(int rows, int c) {
   return p;
 }
 
+// make_plan's grid covers cblocks * cthreads channel groups: every c / 4 up to 64 and every
+// multiple of 64 above.  Any other count (c = 320) would leave channels without partials, so the
+// entry points that reduce with a Plan refuse it.
+bool plan_covers(int c) {
+  const int c4 = c / 4;
+  return c4 > 0 && c4 % (c4 < 64 ? c4 : 64) == 0;
+}
+
 // layout of the double workspace: [nrb][c][2] partials, then float coeffs [3][c]
 size_t ws_need(int rows, int c) {
   Plan p = make_plan(rows, c);
@@ -1148,9 +1156,9 @@ TMR_API int tmr_bn_fwd_stats(const float* y, int rows, int c, const float* gamma
                              hipStream_t stream) {
   TMR_CHECK_ARG(c % 4 == 0 && c >= 4, "tmr_bn_fwd_stats: channels %d must be a multiple of 4", c);
   TMR_CHECK_ARG(rows > 0, "tmr_bn_fwd_stats: empty input");
+  TMR_CHECK_ARG(plan_covers(c), "tmr_bn_fwd_stats: unsupported channel count %d", c);
   TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "tmr_bn_fwd_stats: workspace too small");
   Plan p = make_plan(rows, c);
-  TMR_CHECK_ARG((c / 4) % p.cthreads == 0, "tmr_bn_fwd_stats: unsupported channel count %d", c);
   float4* part = (float4*)ws;
   hipLaunchKernelGGL(bn_stats_partial, dim3(p.nrb, p.cblocks), dim3(NT), 0, stream, y, rows, c,
                      p.rpb, p.cthreads, part);
@@ -1379,6 +1387,7 @@ TMR_API int tmr_bn_bwd_x(const float* dz, const float* y, const float* z, const 
                          hipStream_t stream) {
   TMR_CHECK_ARG(c % 4 == 0 && c >= 4, "tmr_bn_bwd: channels %d must be a multiple of 4", c);
   TMR_CHECK_ARG(rows > 0, "tmr_bn_bwd: empty input");
+  TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd: unsupported channel count %d", c);
   TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "tmr_bn_bwd: workspace too small");
   TMR_CHECK_ARG(!relu || z || (scale && shift),
                 "tmr_bn_bwd: relu backward needs the saved output z or the forward scale/shift");
@@ -1451,6 +1460,7 @@ TMR_API int tmr_bn_bwd_maxpool_x(const float* dyp, const uint8_t* argmax, int n,
                                  const float* save_invstd, const float* gamma, void* dyv,
                                  float* dgamma, float* dbeta, int c, void* ws, size_t ws_bytes,
                                  int out_bf16, hipStream_t stream) {
+  TMR_CHECK_ARG(c >= 4 && plan_covers(c), "tmr_bn_bwd_maxpool: unsupported channel count %d", c);
   TMR_CHECK_ARG(dyv, "tmr_bn_bwd_maxpool: null dy");
   return bn_bwd_maxpool_impl(dyp, argmax, n, h, w, ho, wo, y, scale, shift, save_mean,
                              save_invstd, gamma, dyv, dgamma, dbeta, c, ws, ws_bytes, out_bf16,
@@ -1469,6 +1479,7 @@ static int bn_bwd_maxpool_impl(const float* dyp, const uint8_t* argmax, int n, i
   TMR_CHECK_ARG(ho == (h + 2 - 3) / 2 + 1 && wo == (w + 2 - 3) / 2 + 1,
                 "tmr_bn_bwd_maxpool: pooled %dx%d is not MaxPool2d(3,2,1) of %dx%d", ho, wo, h, w);
   const int rows = (int)rows_l;
+  TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd_maxpool: unsupported channel count %d", c);
   TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "tmr_bn_bwd_maxpool: workspace too small");
   PoolGeo pg;
   pg.dyp = dyp; pg.am = (const uchar4*)argmax;
@@ -1625,6 +1636,7 @@ TMR_API int tmr_bn_bwd_a16(const float* dz, const void* y, const void* z, const 
                            hipStream_t stream) {
   TMR_CHECK_ARG(c % 4 == 0 && c >= 4, "tmr_bn_bwd_a16: channels %d must be a multiple of 4", c);
   TMR_CHECK_ARG(rows > 0, "tmr_bn_bwd_a16: empty input");
+  TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd_a16: unsupported channel count %d", c);
   TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "tmr_bn_bwd_a16: workspace too small");
   TMR_CHECK_ARG(!relu || z || (scale && shift),
                 "tmr_bn_bwd_a16: relu backward needs the saved output z or the forward scale/shift");
@@ -1684,6 +1696,7 @@ TMR_API int tmr_bn_bwd_g16(const void* dz, const void* y, const float* save_mean
   TMR_CHECK_ARG(c % 8 == 0 && c >= 8 && rows > 0, "tmr_bn_bwd_g16: bad shape rows=%d c=%d", rows, c);
   TMR_CHECK_ARG((((uintptr_t)dz | (uintptr_t)y | (uintptr_t)dy) & 15) == 0,
                 "tmr_bn_bwd_g16: dz / y / dy must be 16-B aligned");
+  TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd_g16: unsupported channel count %d", c);
   TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "tmr_bn_bwd_g16: workspace too small");
   Plan p = make_plan(rows, c);
   double* part = (double*)ws;
@@ -1825,6 +1838,7 @@ TMR_API int tmr_bn_bwd_parts_ds(const void* g, const void* y, const void* parts,
                                 int bf16, void* ws, size_t ws_bytes, hipStream_t stream) {
   TMR_CHECK_ARG(c % 8 == 0 && c >= 8 && rows > 0 && nparts > 0,
                 "tmr_bn_bwd_parts_ds: bad shape rows=%d c=%d parts=%d", rows, c, nparts);
+  TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd_parts_ds: unsupported channel count %d", c);
   TMR_CHECK_ARG(g && y && parts && yd && dy && dyd && mean && invstd && gamma && mean_d && invstd_d &&
                     gamma_d, "tmr_bn_bwd_parts_ds: null operand");
   TMR_CHECK_ARG((((uintptr_t)g | (uintptr_t)y | (uintptr_t)yd | (uintptr_t)dy | (uintptr_t)dyd) & 15) == 0,
@@ -1886,6 +1900,7 @@ TMR_API int tmr_bn_bwd_maxpool_a16(const float* dyp, const uint8_t* argmax, int 
   TMR_CHECK_ARG(ho == (h + 2 - 3) / 2 + 1 && wo == (w + 2 - 3) / 2 + 1,
                 "tmr_bn_bwd_maxpool_a16: pooled %dx%d is not MaxPool2d(3,2,1) of %dx%d", ho, wo, h, w);
   const int rows = (int)rows_l;
+  TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd_maxpool_a16: unsupported channel count %d", c);
   TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "tmr_bn_bwd_maxpool_a16: workspace too small");
   PoolGeo pg;
   pg.dyp = dyp; pg.am = (const uchar4*)argmax;
