@@ -150,6 +150,24 @@ size_t tmr_conv2d_wgrad_ws_bytes(const tmr_conv_desc* d);
 /* dw_oihw[k, c_real, r, s] = beta*dw + sum_m dy[m,k] * im2col(x)[m,(r,s,c)] */
 int tmr_conv2d_wgrad(const tmr_conv_desc* d, const float* x, const float* dy, float* dw_oihw,
                      int c_real, float beta, float* ws, size_t ws_bytes, hipStream_t stream);
+/* tmr_conv2d_wgrad with the BatchNorm-backward apply folded into its dy operand (fp32 LDS-DMA
+ * engine): the wgrad reads the masked gradient g and the conv output y (both shaped like dy),
+ * forms dy = fmaf(A, g, fmaf(B, y, C)) per channel from coef = [A | B | C] (3*k floats,
+ * tmr_bn_bwd_parts_x with dy == NULL) as it loads, reduces dw from it, and writes dy to dy_out
+ * once for the dgrad that follows.  dy_out and dw are bit-identical to tmr_bn_bwd_parts followed
+ * by tmr_conv2d_wgrad; the workspace is tmr_conv2d_wgrad_ws_bytes(d).  dy_out must not overlap g
+ * or y.  Served: fp32 math, fp32 operands, groups <= 1, one frame chunk, dense 16-B aligned
+ * tensors, k % 8 == 0, a wgrad of the engine (not a direct kernel) on a tile config that has the
+ * form (64x64, 64x256, 128x128; not 256x256).  tmr_conv2d_wgrad_bnbwd_ok reports 1 when (d and
+ * the non-NULL operands given) are served, else 0 -- the caller then keeps the two calls; the
+ * fused call itself fails on an unserved case, it never falls back.
+ * tmr_wgrad_bnbwd_launches: fused launches of this process so far (test instrumentation). */
+int tmr_conv2d_wgrad_bnbwd_ok(const tmr_conv_desc* d, const void* x, const void* g, const void* y,
+                              const void* dy_out);
+int tmr_conv2d_wgrad_bnbwd(const tmr_conv_desc* d, const float* x, const float* g, const float* y,
+                           const float* coef, float* dy_out, float* dw_oihw, int c_real,
+                           float beta, float* ws, size_t ws_bytes, hipStream_t stream);
+long tmr_wgrad_bnbwd_launches(void);
 /* tmr_conv2d_dgrad_bnbwd with the beta operand read from dx_old (fp32, or bf16 when old_bf16)
  * instead of dx, and dx written as bf16 (TMR_IO_G16, bf16 math on the LDS-DMA engine): the
  * Bottleneck's conv1 dgrad adding into the residual stream's gradient -- the sum of the identity
@@ -286,6 +304,13 @@ int tmr_bn_bwd_parts_x(const float* g, const float* y, const void* parts, int np
                        const float* save_mean, const float* save_invstd, const float* gamma,
                        void* dy, float* dgamma, float* dbeta, int rows, int c, void* ws,
                        size_t ws_bytes, int out_bf16, hipStream_t stream);
+/* tmr_bn_bwd_parts_x with dy == NULL (g and y are then not read and may be NULL) runs the
+ * reduction only: dgamma, dbeta, and the per-channel coefficients of dy = A*g + B*y + C, which
+ * stay in the caller's workspace as 3*c floats [A | B | C] at byte offset
+ * tmr_bn_parts_coef_offset(nparts, c) (> 0; 16-B aligned when ws is and c % 8 == 0) for the
+ * caller to apply -- tmr_conv2d_wgrad_bnbwd.  The workspace must stay untouched until that
+ * consumer has run on the same stream. */
+size_t tmr_bn_parts_coef_offset(int nparts, int c);
 int tmr_bn_bwd_x(const float* dz, const float* y, const float* z, const float* scale,
                  const float* shift, const float* save_mean, const float* save_invstd,
                  const float* gamma, void* dy, float* dres, float* dgamma, float* dbeta, int rows,

@@ -61,6 +61,10 @@ SIGNATURES = {
     "tmr_conv2d_dgrad_bnbwd": [DP, P, P, P, F, P, P, P, P, P, I, P, SZ, P],
     "tmr_conv2d_wgrad_ws_bytes": [DP],
     "tmr_conv2d_wgrad": [DP, P, P, P, I, F, P, SZ, P],
+    "tmr_conv2d_wgrad_bnbwd_ok": [DP, P, P, P, P],
+    "tmr_conv2d_wgrad_bnbwd": [DP, P, P, P, P, P, P, I, F, P, SZ, P],
+    "tmr_wgrad_bnbwd_launches": [],
+    "tmr_bn_parts_coef_offset": [I, I],
     "tmr_conv2d_dgrad_bnbwd_acc": [DP, P, P, P, F, P, I, P, P, P, P, P, I, P, SZ, P],
     "tmr_bn_apply_x": [P, P, P, P, P, I, I, I, I, P],
     "tmr_bn_bwd_parts_x": [P, P, P, I, P, P, P, P, P, P, I, I, P, SZ, I, P],
@@ -195,6 +199,8 @@ _RESTYPES = {
     "tmr_clear_error": None,
     "tmr_conv2d_wgrad_ws_bytes": SZ,
     "tmr_dgrad_ws_launches": L,
+    "tmr_wgrad_bnbwd_launches": L,
+    "tmr_bn_parts_coef_offset": SZ,
     "tmr_resize_tmp_bytes": SZ,
     "tmr_margin_ws_bytes": SZ,
     "tmr_jpeg_ws_bytes": SZ,

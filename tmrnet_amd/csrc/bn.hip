@@ -1187,6 +1187,14 @@ TMR_API size_t tmr_bn_parts_ws_bytes(int nparts, int c) {
   return slab_ws_bytes(nparts, c) + (size_t)3 * c * sizeof(float) + 64;
 }
 
+TMR_API size_t tmr_bn_parts_coef_offset(int nparts, int c) {
+  if (nparts <= 0 || c <= 0) {
+    tmr_set_error("tmr_bn_parts_coef_offset: bad size (parts %d, channels %d)", nparts, c);
+    return 0;
+  }
+  return slab_ws_bytes(nparts, c);
+}
+
 TMR_API int tmr_bn_finalize_ws(const void* partials, int nparts, int c, const float* gamma,
                                const float* beta, float* running_mean, float* running_var,
                                float momentum, float eps, float* save_mean, float* save_invstd,
@@ -1550,6 +1558,9 @@ TMR_API int tmr_bn_bwd_parts_x(const float* g, const float* y, const void* parts
                      (const double*)slabs, sp.nslabs, rows, c, save_mean, save_invstd, gamma,
                      dgamma, dbeta, coef);
   TMR_CHECK_LAUNCH("bn_bwd_final_slabs");
+  // coefficients only (tmr_bn_bwd_maxpool's convention): the caller applies them -- the fused
+  // wgrad, tmr_conv2d_wgrad_bnbwd, reads them at ws + tmr_bn_parts_coef_offset(nparts, c)
+  if (!dyv) return 0;
   const long n4 = (long)rows * c / 4;
   if (out_bf16)
     hipLaunchKernelGGL((bn_bwd_apply<0, false, __bf16, float>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, g,

@@ -535,8 +535,21 @@ constexpr int occ16() {
 }
 
 // the body of one workgroup: output tile `bid` (m-major over the n-tiles), reduction split `split`
+//
+// BNW (fp32 WGRAD only; gemm16_wgrad_bnbwd_kernel): the A operand dY is produced here from the
+// masked gradient g (GemmArgs::A) and the conv output y (GemmArgs::bn_y) of the BatchNorm whose
+// backward precedes this wgrad: dy = fmaf(A, g, fmaf(B, y, C)) with the per-channel coefficients
+// of tmr_bn_bwd_parts (GemmArgs::bn_sc = [A | B | C], M floats each) -- bn_bwd_apply8_k's
+// expression, so the values are its values.  g is staged by LDS-DMA exactly as dY would be; each
+// lane loads the y bytes of its own 16-B pieces into registers beside the DMA of the same k-tile
+// and, after its vmcnt wait and before the barrier that publishes the tile, rewrites its landed
+// pieces in place (a lane's own pieces are ordered for its ds_read by that wait alone).  Rows at
+// or past the split's kend and channels past M become 0, as the DMA's zero fill.  The workgroups
+// of n-tile 0 also store their pieces to dY (GemmArgs::Cold): every (m-tile, split) owns its rows
+// x channels, so each element is written once.  Same k order, split plan and epilogue: dW is
+// bit-identical to the wgrad on the materialised dY.
 template <int MODE, int BM, int BN, int WM, int WN, int TAPV, int PIPE, int F32, int NST, int EPF = 0,
-          int INF16 = 0>
+          int INF16 = 0, int BNW = 0>
 __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, const int split) {
   constexpr uint32_t ES = F32 ? 4u : 2u;   // element bytes
   constexpr int EPC = 16 / ES;             // elements per 16-B chunk
@@ -555,6 +568,10 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
   using Frag = typename std::conditional<F32 != 0, f32x4_t, bf16x8>::type;
   constexpr int EPI = WM * BN * 2 * 4;
   static_assert(NST == 2 || (NST == 1 && MODE != MODE_WGRAD), "one-stage form: FWD / DGRAD");
+  static_assert(!BNW || (MN && F32 != 0 && PIPE == 1), "dY-producing form: the fp32 WGRAD view");
+  // ... a lane's pieces then all cover the same 4 channels (one coefficient set per lane): piece
+  // q starts 64 * NW * q / CPRA k-rows further, an even count, so neither chunk nor swizzle moves
+  static_assert(!BNW || ((64 * NW) % (2 * (BM / 4)) == 0), "dY-producing form: fixed piece columns");
   // the DGRAD view's LDS-staged BN-backward epilogue stages the whole tile at once where it fits
   // 70 KB (every dgrad tile but 256x256: a few KB over the two k-tile stages), so the
   // accumulators are dead before its global loads start; else whole wave row-blocks per chunk
@@ -626,6 +643,22 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
       akr[q] = k;
       acok[q] = i < a.M;
       aco[q] = (uint32_t)i * ES;
+    }
+  }
+  // BNW: y and dY descriptors (g's extent), this lane's coefficients, the y pieces in flight
+  __amdgpu_buffer_rsrc_t rY = rA, rD = rA;
+  f32x4_t cfA = {0.f, 0.f, 0.f, 0.f}, cfB = cfA, cfC = cfA;
+  f32x4_t ypc[BNW ? NIA : 1];
+  bool dyw = false;   // this workgroup writes dY (n-tile 0)
+  if constexpr (BNW != 0) {
+    rY = make_rsrc(a.bn_y, a.Abytes);
+    rD = make_rsrc(reinterpret_cast<const float*>(a.Cold), a.Abytes);
+    dyw = n0 == 0;
+    if (acok[0]) {   // M % 4 == 0: the piece's 4 channels are in range together
+      const int i = (int)(aco[0] / ES);
+      cfA = *reinterpret_cast<const f32x4_t*>(a.bn_sc + i);
+      cfB = *reinterpret_cast<const f32x4_t*>(a.bn_sc + a.M + i);
+      cfC = *reinterpret_cast<const f32x4_t*>(a.bn_sc + 2 * a.M + i);
     }
   }
   // B: FWD weight rows / DGRAD transposed-weight rows (row byte offset, chunk), WGRAD X columns
@@ -740,6 +773,8 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
         const bool ok = acok[q] && m < kend;
         const uint32_t off = (uint32_t)m * (uint32_t)a.ldb * ES + aco[q];
         glds16(rA, As + 1024 * (wave + NW * q), ok ? off : OOB);
+        if constexpr (BNW != 0)
+          ypc[q] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rY, ok ? off : OOB, 0, 0));
       }
       // WGRAD B[k=m][j=(tap,c)] = X[src(m, tap)][c]
 #pragma unroll
@@ -879,6 +914,39 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
     }
   };
 
+  // BNW: this lane's landed g pieces of k-tile kt (LDS buffer buf) -> dY in place, after the
+  // lane's own vmcnt wait and before the publishing barrier.  The n-tile 0 workgroups store the
+  // pieces to the dY tensor after that barrier (bnw_store): the barrier's fence drains vmcnt, so
+  // stores issued before it would put their latency in front of every k-tile; issued after it
+  // they retire under the tile's MFMAs, before the next iteration's vmcnt(0).
+  f32x4_t dyo[BNW ? NIA : 1];
+  auto bnw_apply = [&](int kt, int buf) {
+    const int kb = kbeg + kt * BK;
+    unsigned char* As = smem + buf * STAGE;
+#pragma unroll
+    for (int q = 0; q < NIA; ++q) {
+      f32x4_t* pc = reinterpret_cast<f32x4_t*>(As + 1024 * (wave + NW * q) + 16 * lane);
+      const int m = kb + akr[q];
+      const bool ok = acok[q] && m < kend;
+      const f32x4_t gv = *pc, yv = ypc[q];
+      f32x4_t o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = ok ? fmaf(cfA[e], gv[e], fmaf(cfB[e], yv[e], cfC[e])) : 0.f;
+      *pc = o;
+      dyo[q] = o;
+    }
+  };
+  auto bnw_store = [&](int kt) {
+    const int kb = kbeg + kt * BK;
+#pragma unroll
+    for (int q = 0; q < NIA; ++q) {
+      const int m = kb + akr[q];
+      const bool ok = acok[q] && m < kend;
+      const uint32_t off = (uint32_t)m * (uint32_t)a.ldb * ES + aco[q];
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, dyo[q]), rD, ok ? off : OOB, 0, 0);
+    }
+  };
+
   // ---------------- main loop: two LDS stages ----------------
   // Iteration kt: wait for this wave's pieces of tile kt, barrier (every wave's pieces landed;
   // every wave finished reading the other buffer in iteration kt-1), issue tile kt+1 into the
@@ -908,10 +976,14 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
     stage(0, 0);
     for (int kt = 0; kt < ntiles; ++kt) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if constexpr (BNW != 0) bnw_apply(kt, kt & 1);
       __syncthreads();
       const int buf = kt & 1;
       Frag a0[TM], b0[TN], a1[TM], b1[TN];
       frags(buf, 0, a0, b0);
+      if constexpr (BNW != 0) {
+        if (dyw) bnw_store(kt);
+      }
       if (kt + 1 < ntiles) stage(kt + 1, buf ^ 1);
       frags(buf, 1, a1, b1);
       mfmas(a0, b0);
@@ -948,6 +1020,17 @@ void gemm16_kernel(const GemmArgs a) {
   int bid, split;
   xcd_work(bid, split);   // XCD-aware tile order (gemm_kernel.h)
   gemm16_body<MODE, BM, BN, WM, WN, TAPV, PIPE, F32, NST, EPF>(a, bid, split);
+}
+
+// The fp32 WGRAD view producing its dY operand from (g, y, BN-backward coefficients) on load
+// (gemm16_body's BNW form).  A kernel of its own name: the engine's other instantiations keep
+// their symbols and their code.
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(64 * WM * WN, (occ16<BM, BN, WM, WN, 2>()))
+void gemm16_wgrad_bnbwd_kernel(const GemmArgs a) {
+  int bid, split;
+  xcd_work(bid, split);
+  gemm16_body<MODE_WGRAD, BM, BN, WM, WN, 0, 1, 1, 2, 0, 0, 1>(a, bid, split);
 }
 
 // Tile w of a GemmPar launch -> (class, tile of that class).  The classes' tiles go out in

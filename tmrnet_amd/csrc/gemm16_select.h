@@ -145,6 +145,16 @@ extern template int launch_gemm16<MODE_DGRAD, 1>(const GemmArgs&, int, hipStream
 extern template int launch_gemm16<MODE_WGRAD, 0>(const GemmArgs&, int, hipStream_t);
 extern template int launch_gemm16<MODE_WGRAD, 1>(const GemmArgs&, int, hipStream_t);
 
+// The fp32 wgrad that produces its dY operand from (g, y, BN-backward coefficients) while loading
+// it (tmr_conv2d_wgrad_bnbwd; gemm16_kernel.h BNW, gemm16_wgrad_f32.hip): the tile configs that
+// have the form -- 64x64, 64x256 and 128x128 as 8 waves.  256x256 as 16 waves runs at 118 of its
+// 128 VGPRs and has no room for the y pieces and coefficients: those units keep the separate
+// apply pass (profiles/wgrad_bnbwd/).
+inline bool wgrad_bnbwd_cfg(int cfg) { return cfg == 4 || cfg == 5 || cfg == 7; }
+int launch_gemm16_wgrad_bnbwd(const GemmArgs& a, int splits, hipStream_t st);
+// fused launches so far (tmr_wgrad_bnbwd_launches)
+extern long g_wgrad_bnbwd_launches;
+
 // the bf16-activation inference forwards (tmr_conv2d_fwd_fused with TMR_IO_Y_BF16: bf16 residual
 // and y, epilogue_batched's INF16 form) of one tile config, in the launch form (one-stage, TAPV)
 // the same tile's other bf16 forwards take -- their accumulators are bit-identical.  Kernels of

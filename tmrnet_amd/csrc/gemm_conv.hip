@@ -625,6 +625,25 @@ TMR_API size_t tmr_conv2d_wgrad_ws_bytes(const tmr_conv_desc* d) {
   return bytes;
 }
 
+// the engine's split slabs (wgrad_plan) summed in split order into the OIHW gradient
+static int wgrad_reduce(const tmr_conv_desc* d, const float* ws, int sp, long slab, float* dw_oihw,
+                        int c_real, float beta, hipStream_t stream) {
+  const int ntaps = d->r * d->s;
+  if (ntaps > 1 && ntaps <= kReduceTaps) {
+    hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3(d->k, cdiv(c_real, 64)), dim3(256), 0,
+                       stream, ws, sp, slab, dw_oihw, ntaps, d->c, c_real, beta);
+    TMR_CHECK_LAUNCH("wgrad_reduce_taps_kernel");
+    return 0;
+  }
+  long total = (long)d->k * ntaps * c_real;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, stream, ws, sp, slab,
+                     dw_oihw, d->k, ntaps, d->c, c_real, beta);
+  TMR_CHECK_LAUNCH("wgrad_reduce_kernel");
+  return 0;
+}
+
 static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* dy,
                            float* dw_oihw, int c_real, float beta, float* ws, size_t ws_bytes,
                            hipStream_t stream) {
@@ -655,20 +674,7 @@ static int conv_wgrad_impl(const tmr_conv_desc* d, const float* x, const float* 
   bool al = aligned16(x) && aligned16(dy) && (d->k % 4 == 0) && a.lds % 4 == 0 && a.ldb % 4 == 0;
   const int rc = launch_gemm<MODE_WGRAD>(a, al, sp, stream);
   if (rc) return rc;
-  const int ntaps = d->r * d->s;
-  if (ntaps > 1 && ntaps <= kReduceTaps) {
-    hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3(d->k, cdiv(c_real, 64)), dim3(256), 0,
-                       stream, ws, sp, slab, dw_oihw, ntaps, d->c, c_real, beta);
-    TMR_CHECK_LAUNCH("wgrad_reduce_taps_kernel");
-    return 0;
-  }
-  long total = (long)d->k * ntaps * c_real;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, stream, ws, sp, slab,
-                     dw_oihw, d->k, ntaps, d->c, c_real, beta);
-  TMR_CHECK_LAUNCH("wgrad_reduce_kernel");
-  return 0;
+  return wgrad_reduce(d, ws, sp, slab, dw_oihw, c_real, beta, stream);
 }
 
 // frame chunks accumulate into dw in chunk order (beta = 1 after the first): deterministic; the
@@ -682,6 +688,76 @@ TMR_API int tmr_conv2d_wgrad(const tmr_conv_desc* d, const float* x, const float
                            dw_oihw + (long)g * c.k * c_real * c.r * c.s, c_real,
                            f0 == 0 ? beta : 1.f, ws, ws_bytes, stream);
   });
+}
+
+// The wgrad that produces its dy operand itself (gemm16_kernel.h, BNW): dy = A*g + B*y + C per
+// channel, the BatchNorm-backward apply of tmr_bn_bwd_parts folded into the load of the A operand;
+// dy_out is written once (from the n-tile 0 workgroups) for the dgrad that follows.
+// Why the fused form does not serve (d, operands), or nullptr when it does.  Null pointers are not
+// judged (the query before the tensors exist).
+static const char* wgrad_bnbwd_why(const tmr_conv_desc* d, int c_real, const void* x, const void* g,
+                                   const void* y, const void* dy_out) {
+  if (d->n <= 0 || d->k <= 0 || d->c <= 0 || d->r <= 0 || d->s <= 0) return "empty descriptor";
+  if (d->math != TMR_MATH_F32) return "fp32 math only";
+  if (d->io & (TMR_IO_X_BF16 | TMR_IO_DY_BF16)) return "a bf16 operand";
+  if (ngroups(d) > 1) return "grouped conv";
+  if (frames_per_launch(d) < d->n) return "frame-chunked tensors";
+  if (d->k % 8 != 0) return "output channels not a multiple of 8 (the 8-wide apply's domain)";
+  if (yld_of(d) != d->k) return "g / y / dy must be dense";
+  if (ilog2_exact(d->c) < 2) return "stored input channels must be a power of two >= 4";
+  if (direct_wgrad(d, c_real)) return "the wgrad runs on a direct kernel";
+  if ((((uintptr_t)x | (uintptr_t)g | (uintptr_t)y | (uintptr_t)dy_out) & 15) != 0)
+    return "operands must be 16-B aligned";
+  GemmArgs a;
+  wgrad_fill(d, a);
+  if (!use16(a, MODE_WGRAD)) return "not an LDS-DMA engine wgrad";
+  if (!wgrad_bnbwd_cfg(pick_cfg16(a.M, a.N, a.K, MODE_WGRAD, true)))
+    return "tile config without the fused form (256x256)";
+  return nullptr;
+}
+
+TMR_API int tmr_conv2d_wgrad_bnbwd_ok(const tmr_conv_desc* d, const void* x, const void* g,
+                                      const void* y, const void* dy_out) {
+  return d && !wgrad_bnbwd_why(d, 0, x, g, y, dy_out) ? 1 : 0;
+}
+
+long tmrg::g_wgrad_bnbwd_launches = 0;
+TMR_API long tmr_wgrad_bnbwd_launches(void) {
+  return __atomic_load_n(&g_wgrad_bnbwd_launches, __ATOMIC_RELAXED);
+}
+
+TMR_API int tmr_conv2d_wgrad_bnbwd(const tmr_conv_desc* d, const float* x, const float* g,
+                                   const float* y, const float* coef, float* dy_out,
+                                   float* dw_oihw, int c_real, float beta, float* ws,
+                                   size_t ws_bytes, hipStream_t stream) {
+  TMR_CHECK_ARG(d && x && g && y && coef && dy_out && dw_oihw, "tmr_conv2d_wgrad_bnbwd: null operand");
+  TMR_CHECK_ARG(c_real >= 1 && c_real <= d->c, "tmr_conv2d_wgrad_bnbwd: bad c_real %d", c_real);
+  const char* why = wgrad_bnbwd_why(d, c_real, x, g, y, dy_out);
+  TMR_CHECK_ARG(!why, "tmr_conv2d_wgrad_bnbwd: no fused form (%s); ask tmr_conv2d_wgrad_bnbwd_ok "
+                "and keep tmr_bn_bwd_parts + tmr_conv2d_wgrad", why);
+  TMR_CHECK_ARG(((uintptr_t)coef & 15) == 0, "tmr_conv2d_wgrad_bnbwd: coef must be 16-B aligned");
+  // n-tiles other than 0 read g after n-tile 0 may have written dy: no overlap
+  const size_t ybytes = (size_t)d->n * d->ho * d->wo * d->k * sizeof(float);
+  const auto apart = [&](const void* p) {
+    return (const char*)p + ybytes <= (const char*)dy_out || (const char*)dy_out + ybytes <= (const char*)p;
+  };
+  TMR_CHECK_ARG(apart(g) && apart(y), "tmr_conv2d_wgrad_bnbwd: dy_out overlaps g or y");
+  int sp, kc;
+  long slab;
+  wgrad_plan(d, &sp, &kc, &slab);
+  TMR_CHECK_ARG(ws && ws_bytes >= (size_t)sp * slab * sizeof(float),
+                "tmr_conv2d_wgrad_bnbwd: workspace too small (%zu < %zu)", ws_bytes,
+                (size_t)sp * slab * sizeof(float));
+  GemmArgs a;
+  wgrad_fill(d, a);
+  a.A = g; a.B = x; a.C = ws; a.bias = nullptr;
+  a.bn_y = y; a.bn_sc = coef; a.Cold = dy_out;
+  a.kchunk = kc; a.slab = slab;
+  a.Cbytes = clamp_bytes(slab);
+  const int rc = launch_gemm16_wgrad_bnbwd(a, sp, stream);
+  if (rc) return rc;
+  __atomic_fetch_add(&g_wgrad_bnbwd_launches, 1L, __ATOMIC_RELAXED);
+  return wgrad_reduce(d, ws, sp, slab, dw_oihw, c_real, beta, stream);
 }
 
 // Plain GEMMs on the same engine ---------------------------------------------

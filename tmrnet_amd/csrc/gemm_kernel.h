@@ -77,6 +77,9 @@ struct GemmArgs {
   // DGRAD epilogue fused with the backward of the BatchNorm(+ReLU) whose output gradient this
   // dgrad produces: C = relu-mask(C) (mask 1: bn_z > 0, 2: fmaf(bn_y, bn_sc, bn_sh) > 0) and
   // per-(m-tile, column) partials (sum g, sum g * (bn_y - bn_mean)) -> bn_part (float2)
+  // (the fp32 WGRAD that produces its dY operand, gemm16_kernel.h BNW, borrows three of these
+  // fields: A = the masked gradient g, bn_y = y, bn_sc = the coefficients [A | B | C] of
+  // dy = A*g + B*y + C, Cold = the dY tensor it writes)
   const float* bn_y;
   const float* bn_z;
   const float* bn_sc;

@@ -465,6 +465,63 @@ def conv_wgrad(x, dy, r, s, stride, pad, c_real=None, out=None, beta=0.0, pad_w=
     return out
 
 
+def bn_bwd_parts_coef(y, parts, nparts, mean, inv, gamma):
+    """The reduction half of bn_bwd_parts (tmr_bn_bwd_parts_x with no dy): -> (coef, dgamma,
+    dbeta), coef = the 3*c per-channel coefficients [A | B | C] of dy = A*g + B*y + C, a view
+    into this call's workspace, for conv_wgrad_bnbwd to apply."""
+    c = y.shape[-1]
+    rows = y.numel() // c
+    nb = query("tmr_bn_parts_ws_bytes", int(nparts), c)
+    off = query("tmr_bn_parts_coef_offset", int(nparts), c)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=y.device)
+    dgamma = _empty((c,), y); dbeta = _empty((c,), y)
+    call("tmr_bn_bwd_parts_x", None, None, parts, int(nparts), mean, inv, gamma, None, dgamma,
+         dbeta, rows, c, ws, ctypes.c_size_t(ws.numel() * 8), 0, stream_ptr())
+    return ws.view(f32)[off // 4: off // 4 + 3 * c], dgamma, dbeta
+
+
+def _wgrad_bnbwd_desc(x, g, r, s, stride, pad, math, groups):
+    n, h, w, c = x.shape
+    d = conv_desc(n, h, w, c, g.shape[3], r, s, stride, pad, None, math=math, io=_io(x, None, g),
+                  groups=groups)
+    d.x_ld = _nhwc_ld(x, "x")
+    d.y_ld = _nhwc_ld(g, "g")
+    return d
+
+
+def conv_wgrad_bnbwd_ok(x, g, y, r, s, stride, pad, math="fp32", groups=1):
+    """Whether conv_wgrad_bnbwd serves this unit (tmr_conv2d_wgrad_bnbwd_ok); if not the caller
+    keeps bn_bwd_parts + conv_wgrad."""
+    if math != "fp32" or not (x.dtype == g.dtype == y.dtype == f32) or g.shape != y.shape:
+        return False
+    if not (g.is_contiguous() and y.is_contiguous()):
+        return False
+    d = _wgrad_bnbwd_desc(x, g, r, s, stride, pad, math, groups)
+    return bool(query("tmr_conv2d_wgrad_bnbwd_ok", ctypes.byref(d), x, g, y, None))
+
+
+def conv_wgrad_bnbwd(x, g, y, coef, r, s, stride, pad, c_real=None, math="fp32"):
+    """conv_wgrad whose dy operand is produced on load from the masked gradient g, the conv output
+    y and bn_bwd_parts_coef's coefficients -> (dW (K, c_real, R, S), dy); the values of
+    bn_bwd_parts + conv_wgrad.  Only where conv_wgrad_bnbwd_ok says so (no fallback)."""
+    n, h, w, c = x.shape
+    k = g.shape[3]
+    c_real = c if c_real is None else c_real
+    d = _wgrad_bnbwd_desc(x, g, r, s, stride, pad, math, 1)
+    assert (d.ho, d.wo) == tuple(g.shape[1:3])
+    out = _empty((k, c_real, r, s), x)
+    dy = torch.empty_like(y)
+    ws_bytes = query("tmr_conv2d_wgrad_ws_bytes", ctypes.byref(d))
+    ws = torch.empty(max(1, (ws_bytes + 3) // 4), dtype=f32, device=x.device)
+    # the bytes of conv_wgrad, with y read beside g and dy written once
+    with _prof("conv_wgrad" + _SUFFIX[math], 2.0 * n * d.ho * d.wo * k * r * s * c_real,
+               (n, h, w, c, k, r, stride),
+               _esz(x) * n * h * w * c + 3 * 4 * n * d.ho * d.wo * k + 4 * k * r * s * c_real):
+        call("tmr_conv2d_wgrad_bnbwd", ctypes.byref(d), x, g, y, coef, dy, out, int(c_real), 0.0,
+             ws, ctypes.c_size_t(ws.numel() * 4), stream_ptr())
+    return out, dy
+
+
 def gemm_nt(a, b, bias=None, out=None, beta=0.0, M=None, N=None, K=None, lda=None, ldb=None,
             ldc=None):
     """out[M][N] = beta*out + a[M][K] @ b[N][K]^T (+bias)."""

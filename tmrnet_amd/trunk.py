@@ -130,6 +130,14 @@ R16 = os.environ.get("TMR_BF16_RESGRAD", "1") != "0"
 # 161.8 -> 161.5, profiles/r5/ds_dual/.  A module attribute for the bit-identity test.)
 DS_DUAL = True
 
+# fp32 step: a unit whose masked gradient comes from a fused dgrad (parts) lets its wgrad produce
+# dy = A*g + B*y + C while loading its dy operand (tmr_conv2d_wgrad_bnbwd) instead of a separate
+# BatchNorm-backward apply pass: the same dy and dW bit for bit, 12 instead of 16 B moved per dy
+# element (profiles/wgrad_bnbwd/).  Units the fused form does not serve (ops.conv_wgrad_bnbwd_ok:
+# the 256x256-tile wgrads, direct kernels) keep the two calls.  A module attribute for the
+# bit-identity test.
+WGRAD_BNBWD = True
+
 
 def _ds_dual(g, r3, rd):
     """DS_DUAL applies: g, y3 and y_ds of one dtype, which is also the dy dtype the separate passes
@@ -254,7 +262,7 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
 
 def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need_dx=True,
                  dres_inplace=False, parts=None, fuse_prev=None, pool=None, dy=None, g16=False,
-                 r16=False):
+                 r16=False, fold=False):
     """BN backward, wgrad, dgrad (optionally accumulated into dx_out) of one conv+BN unit.
 
     parts: dz was produced by a fused dgrad (conv_dgrad_bnbwd): it is already ReLU-masked and
@@ -270,10 +278,14 @@ def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need
     g16: the fused dgrad may store fuse_prev's masked gradient as bf16 (TMR_IO_G16) when that unit
     has no residual and the dgrad runs on the bf16 LDS-DMA engine (the bf16-activation step).
     r16: the same for fuse_prev a block output (R16): the dgrad adds into dx_out (bf16 in place,
-    or fp32 read and a new bf16 tensor returned)."""
+    or fp32 read and a new bf16 tensor returned).
+    fold: with parts, the fp32 wgrad may produce dy itself (WGRAD_BNBWD) where the library serves
+    the unit; the ResNet-50 trunk's units only."""
     conv, bn = rec["conv"], rec["bn"]
     s16 = _store16(rec["math"])   # dy feeds only this conv's dgrad / wgrad
     dy_given = dy is not None
+    dw = None
+    kr, ks = conv.weight.shape[2:]
     if dy_given:
         dres = None
     elif pool is not None:
@@ -281,6 +293,14 @@ def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need
         dy, dg, db = ops.bn_bwd_maxpool(pool[0], pool[1], rec["y"], rec["scale"], rec["shift"],
                                         rec["mean"], rec["inv"], bn.weight.detach(), bf16=s16)
         dres = None
+    elif (parts is not None and fold and WGRAD_BNBWD and rec["math"] == "fp32"
+          and rec.get("groups", 1) == 1
+          and ops.conv_wgrad_bnbwd_ok(rec["x"], dz, rec["y"], kr, ks, rec["stride"], rec["pad"])):
+        coef, dg, db = ops.bn_bwd_parts_coef(rec["y"], parts[0], parts[1], rec["mean"],
+                                             rec["inv"], bn.weight.detach())
+        dw, dy = ops.conv_wgrad_bnbwd(rec["x"], dz, rec["y"], coef, kr, ks, rec["stride"],
+                                      rec["pad"], c_real=rec["c_real"])
+        dres = dz if want_dres else None
     elif parts is not None:
         dy, dg, db = ops.bn_bwd_parts(dz, rec["y"], parts[0], parts[1], rec["mean"], rec["inv"],
                                       bn.weight.detach(), bf16=s16)
@@ -296,9 +316,9 @@ def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need
     x = rec["x"]
     k, c, r, s = conv.weight.shape
     grp = rec.get("groups", 1)
-    grads[conv.weight] = ops.conv_wgrad(x, dy, r, s, rec["stride"], rec["pad"],
-                                        c_real=rec["c_real"], math=rec["math"],
-                                        groups=grp)
+    grads[conv.weight] = dw if dw is not None else ops.conv_wgrad(
+        x, dy, r, s, rec["stride"], rec["pad"], c_real=rec["c_real"], math=rec["math"],
+        groups=grp)
     dx, fused = None, None
     if need_dx:
         hw = (x.shape[1], x.shape[2])
@@ -451,8 +471,9 @@ class TrunkFn(torch.autograd.Function):
                 del dy3
             else:
                 dz2, dres, fz2 = _conv_bn_bwd(r3, g, grads, want_dres=True, dres_inplace=True,
-                                              parts=pending, fuse_prev=r2, g16=True)
-            dz1, _, fz1 = _conv_bn_bwd(r2, dz2, grads, parts=fz2, fuse_prev=r1, g16=True)
+                                              parts=pending, fuse_prev=r2, g16=True, fold=True)
+            dz1, _, fz1 = _conv_bn_bwd(r2, dz2, grads, parts=fz2, fuse_prev=r1, g16=True,
+                                      fold=True)
             del dz2
             if has_ds:
                 # the strided downsample dgrad writes dx (its tap-less parity classes as zeros),
@@ -465,10 +486,10 @@ class TrunkFn(torch.autograd.Function):
                 else:
                     dx, _, _ = _conv_bn_bwd(rd, dres, grads)
                 dx, _, pending = _conv_bn_bwd(r1, dz1, grads, parts=fz1, dx_out=dx, dx_beta=1.0,
-                                              fuse_prev=prev3, r16=True)
+                                              fuse_prev=prev3, r16=True, fold=True)
             else:
                 dx, _, pending = _conv_bn_bwd(r1, dz1, grads, parts=fz1, dx_out=dres, dx_beta=1.0,
-                                              fuse_prev=prev3, r16=True)
+                                              fuse_prev=prev3, r16=True, fold=True)
             del dz1, brec, dres
             g = dx
             if ready is not None:   # this block's parameter grads are final: start their exchange
