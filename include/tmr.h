@@ -168,6 +168,24 @@ int tmr_conv2d_wgrad_bnbwd(const tmr_conv_desc* d, const float* x, const float* 
                            const float* coef, float* dy_out, float* dw_oihw, int c_real,
                            float beta, float* ws, size_t ws_bytes, hipStream_t stream);
 long tmr_wgrad_bnbwd_launches(void);
+/* The launch plan of one view of a conv (0 fwd, 1 dgrad, 2 wgrad): which engine and tile config the
+ * launch of the first (group, frame chunk) slice takes.  Host code only -- nothing is launched, no
+ * device is needed -- and answered by the selection functions the launches call, so tests can
+ * state which tile config a geometry exercises.  Operands are taken as 16-B aligned and as dense
+ * as x_ld / y_ld say.  d->io as the view's call would carry it (dgrad: TMR_IO_WT_F32 /
+ * TMR_IO_WT_BF16 select the LDS-DMA engine).  engine 0 means the direct kernel of
+ * tmr_conv2d_fwd_bnstats (view 0), tmr_conv2d_dgrad_bnbwd (view 1) or tmr_conv2d_wgrad (view 2);
+ * the other fields are then 0 and cfg -1. */
+typedef struct tmr_conv_tile {
+  int engine;         /* 0 direct kernel, 1 register-staged engine, 2 LDS-DMA engine */
+  int cfg;            /* row of the engine's tile table */
+  int bm, bn, waves;  /* that row: output tile rows x columns, waves per workgroup */
+  int tapv;           /* LDS-DMA engine: the k-tile walks several taps (fewer channels per tap) */
+  int splits, kchunk; /* wgrad: split-K slices and the reduction rows of each */
+  int classes;        /* dgrad: stride-parity classes with at least one tap; the tile fields
+                         describe the one with the most rows */
+} tmr_conv_tile;
+int tmr_conv2d_tile(const tmr_conv_desc* d, int view, tmr_conv_tile* out);
 /* tmr_conv2d_dgrad_bnbwd with the beta operand read from dx_old (fp32, or bf16 when old_bf16)
  * instead of dx, and dx written as bf16 (TMR_IO_G16, bf16 math on the LDS-DMA engine): the
  * Bottleneck's conv1 dgrad adding into the residual stream's gradient -- the sum of the identity

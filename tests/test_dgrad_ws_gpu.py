@@ -20,15 +20,9 @@ import torch
 
 from tmrnet_amd import ops
 from tmrnet_amd._lib import lib
+from tests._bits import pack_bits as _pack_bits
 
 pytestmark = pytest.mark.gpu
-
-
-def _pack_bits(m):
-    m = m.reshape(-1).to(torch.int64)
-    m = torch.cat([m, m.new_zeros((-m.numel()) % 32)]).view(-1, 32)
-    w = (m << torch.arange(32, dtype=torch.int64, device=m.device)).sum(1)
-    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
 
 
 def _launches():

@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from tmrnet_amd import ops
+from tests._bits import pack_bits as _pack_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -726,14 +727,6 @@ def test_weight_layout_sessions(dev, precision, backbone):
         assert torch.equal(res[True][1][n], res[False][1][n]), n
     for n in res[True][2]:
         assert torch.equal(res[True][2][n], res[False][2][n]), n
-
-
-def _pack_bits(m):
-    """(numel,) bool -> int32 words, element e = bit e % 32 of word e // 32."""
-    m = m.reshape(-1).to(torch.int64)
-    m = torch.cat([m, torch.zeros((-m.numel()) % 32, dtype=torch.int64)]).view(-1, 32)
-    w = (m << torch.arange(32, dtype=torch.int64)).sum(1)
-    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
 
 
 @pytest.mark.parametrize("rows,c", [(1000, 256), (77, 64), (3, 8), (101, 12), (5001, 512)])

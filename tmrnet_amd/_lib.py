@@ -29,6 +29,12 @@ class ConvDesc(ctypes.Structure):
 DP = ctypes.POINTER(ConvDesc)
 
 
+class ConvTile(ctypes.Structure):
+    """tmr_conv_tile: the launch plan of one conv view (tmr_conv2d_tile)."""
+    _fields_ = [(n, ctypes.c_int) for n in
+                ("engine", "cfg", "bm", "bn", "waves", "tapv", "splits", "kchunk", "classes")]
+
+
 _NL_FIELDS = ("w1", "b1", "w2", "b2", "w3", "b3", "ln_w", "ln_b", "w4", "b4")
 
 
@@ -64,6 +70,7 @@ SIGNATURES = {
     "tmr_conv2d_wgrad_bnbwd_ok": [DP, P, P, P, P],
     "tmr_conv2d_wgrad_bnbwd": [DP, P, P, P, P, P, P, I, F, P, SZ, P],
     "tmr_wgrad_bnbwd_launches": [],
+    "tmr_conv2d_tile": [DP, I, ctypes.POINTER(ConvTile)],
     "tmr_bn_parts_coef_offset": [I, I],
     "tmr_conv2d_dgrad_bnbwd_acc": [DP, P, P, P, F, P, I, P, P, P, P, P, I, P, SZ, P],
     "tmr_bn_apply_x": [P, P, P, P, P, I, I, I, I, P],

@@ -1163,17 +1163,24 @@ int launch16_cfg(const GemmArgs& a, bool tapv, dim3 grid, hipStream_t st) {
 
 template <int MODE, int F32>
 int launch16_switch(const GemmArgs& a, int cfg, bool tapv, dim3 grid, hipStream_t st) {
+  // (each case checks kCfgs16's row against the instantiation it launches)
+#define TMR_CFG16_CASE(I, BM, BN, WM, WN)                                                        \
+  case I:                                                                                        \
+    static_assert(kCfgs16[I].bm == BM && kCfgs16[I].bn == BN && kCfgs16[I].waves == WM * WN,     \
+                  "kCfgs16 row " #I);                                                            \
+    return launch16_cfg<MODE, BM, BN, WM, WN, F32>(a, tapv, grid, st);
   switch (cfg) {
-    case 1: return launch16_cfg<MODE, 256, 128, 4, 2, F32>(a, tapv, grid, st);
-    case 2: return launch16_cfg<MODE, 128, 128, 2, 2, F32>(a, tapv, grid, st);
-    case 3: return launch16_cfg<MODE, 256, 64, 4, 1, F32>(a, tapv, grid, st);
-    case 4: return launch16_cfg<MODE, 64, 256, 1, 4, F32>(a, tapv, grid, st);
-    case 7: return launch16_cfg<MODE, 128, 128, 4, 2, F32>(a, tapv, grid, st);
-    case 5: return launch16_cfg<MODE, 64, 64, 2, 2, F32>(a, tapv, grid, st);
-    case 0: return launch16_cfg<MODE, 256, 256, 2, 4, F32>(a, tapv, grid, st);
-    case 6: return launch16_cfg<MODE, 256, 256, 4, 4, F32>(a, tapv, grid, st);
+    TMR_CFG16_CASE(1, 256, 128, 4, 2)
+    TMR_CFG16_CASE(2, 128, 128, 2, 2)
+    TMR_CFG16_CASE(3, 256, 64, 4, 1)
+    TMR_CFG16_CASE(4, 64, 256, 1, 4)
+    TMR_CFG16_CASE(7, 128, 128, 4, 2)
+    TMR_CFG16_CASE(5, 64, 64, 2, 2)
+    TMR_CFG16_CASE(0, 256, 256, 2, 4)
+    TMR_CFG16_CASE(6, 256, 256, 4, 4)
     default: break;
   }
+#undef TMR_CFG16_CASE
   TMR_CHECK_ARG(false, "gemm16: no tile config %d", cfg);
   return 1;
 }
@@ -1218,10 +1225,7 @@ int launch_gemm16_t(const GemmArgs& a, int splits, hipStream_t st) {
   if (const int rc = check16<MODE, F32>(a, cfg)) return rc;
   dim3 grid(cdiv(a.M, c.bm) * cdiv(a.N, c.bn), splits, 1);
   if (grid.x == 0) return 0;
-  // a k-tile (64 bf16 / 32 fp32) spans several taps when the channels per tap are fewer (or not
-  // a multiple)
-  const int bk = f32 ? 32 : 64;
-  const bool tapv = MODE != MODE_WGRAD && a.ntaps > 1 && ((1 << a.log2C) % bk) != 0;
+  const bool tapv = tapv16(a, MODE, f32);
   if (MODE == MODE_WGRAD && (c.bm < 64 || c.bn < 64)) return -1;
   if constexpr (MODE == MODE_DGRAD) {   // the wave-specialised persistent form (gemm16_ws.h)
     const int rc = launch_dgrad_ws<F32>(a, cfg, st);
@@ -1244,12 +1248,11 @@ int launch_gemm16_par(const GemmArgs* as, int n, hipStream_t st) {
   static_assert(sizeof(GemmPar) <= 4096, "kernel argument size");
   if (n < 2 || n > PAR_MAX) return -1;
   const int cfg = pick_cfg16(as[0].M, as[0].N, as[0].K, MODE_DGRAD, f32);
-  const int bk = f32 ? 32 : 64;
   for (int i = 0; i < n; ++i) {
     const GemmArgs& a = as[i];
     if ((a.prec == TMR_MATH_F32) != f32 || !use16(a, MODE_DGRAD)) return -1;
     if (pick_cfg16(a.M, a.N, a.K, MODE_DGRAD, f32) != cfg) return -1;
-    if (a.ntaps > 1 && ((1 << a.log2C) % bk) != 0) return -1;   // the TAPV form
+    if (tapv16(a, MODE_DGRAD, f32)) return -1;   // the TAPV form
   }
   switch (cfg) {
     case 1: case 2: case 3: case 5: case 7: break;

@@ -8,10 +8,11 @@
 namespace tmrg {
 
 // ---------------------------------------------------------------- launch selection
-struct Cfg16 { int bm, bn; };
-constexpr Cfg16 kCfgs16[] = {{256, 256}, {256, 128}, {128, 128}, {256, 64}, {64, 256}, {64, 64},
-                              {256, 256},    // 6: 256x256 as 16 waves (4x4, 64x64 per wave)
-                              {128, 128}};   // 7: 128x128 as 8 waves (4x2, 32x64 per wave)
+struct Cfg16 { int bm, bn, waves; };   // (waves: checked against launch16_switch's instantiations)
+constexpr Cfg16 kCfgs16[] = {{256, 256, 8}, {256, 128, 8}, {128, 128, 4}, {256, 64, 4},
+                              {64, 256, 4}, {64, 64, 4},
+                              {256, 256, 16},    // 6: 256x256 as 16 waves (4x4, 64x64 per wave)
+                              {128, 128, 8}};    // 7: 128x128 as 8 waves (4x2, 32x64 per wave)
 
 // Eligibility: bf16 math, every operand bf16 in HBM (sab 3; DGRAD with the transposed weights),
 // 16-B pieces of 8 channels (channels per tap, row strides multiples of 8).
@@ -98,6 +99,13 @@ inline int pick_cfg16(long M, long N, long K, int mode, bool f32 = false) {
     }
   }
   return cfg;
+}
+
+// a k-tile (64 bf16 / 32 fp32) spans several taps when the channels per tap are fewer (or not a
+// multiple): the TAPV kernel form of launch_gemm16_t
+inline bool tapv16(const GemmArgs& a, int mode, bool f32) {
+  const int bk = f32 ? 32 : 64;
+  return mode != MODE_WGRAD && a.ntaps > 1 && ((1 << a.log2C) % bk) != 0;
 }
 
 // rows / columns of the output tile the launch for `a` will use (host planning: BN-partial rows,

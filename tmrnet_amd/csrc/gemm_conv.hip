@@ -340,8 +340,29 @@ struct BnBwdFuse {
   int old16;         // the beta operand is bf16
 };
 
+// The launch plan of one GEMM view (tmr_conv2d_tile): the engine and tile config launch_gemm<MODE>
+// takes for `a`, from the functions it calls.
+static void tile_of(const GemmArgs& a, int mode, tmr_conv_tile* t) {
+  const bool f32 = a.prec == TMR_MATH_F32;
+  if (use16(a, mode)) {
+    t->engine = 2;
+    t->cfg = pick_cfg16(a.M, a.N, a.K, mode, f32);
+    const Cfg16 c = kCfgs16[t->cfg];
+    t->bm = c.bm; t->bn = c.bn; t->waves = c.waves;
+    t->tapv = tapv16(a, mode, f32) ? 1 : 0;
+  } else {
+    t->engine = 1;
+    t->cfg = pick_cfg(a.M, a.N, a.K, mode);
+    const TileCfg c = kCfgs[t->cfg];
+    t->bm = c.bm; t->bn = c.bn; t->waves = c.waves;
+    t->tapv = 0;
+  }
+}
+
+// plan: launches nothing and describes the stride-parity classes in *plan (tmr_conv2d_tile)
 static int conv_dgrad_impl(const tmr_conv_desc* d, const float* dy, const float* w_krsc,
-                           float* dx, float beta, hipStream_t stream, BnBwdFuse* fz = nullptr) {
+                           float* dx, float beta, hipStream_t stream, BnBwdFuse* fz = nullptr,
+                           tmr_conv_tile* plan = nullptr) {
   TMR_CHECK_ARG(d->math == TMR_MATH_F32 || d->math == TMR_MATH_BF16, "tmr_conv2d: bad math mode %d", d->math);
   const int lk = ilog2_exact(d->k);
   TMR_CHECK_ARG(lk >= 2, "tmr_conv2d_dgrad: output channels %d must be a power of two >= 4", d->k);
@@ -362,6 +383,7 @@ static int conv_dgrad_impl(const tmr_conv_desc* d, const float* dy, const float*
   GemmArgs pend[PAR_MAX];
   bool pend_al[PAR_MAX];
   int npend = 0;
+  long best_m = -1;
   for (int ph = 0; ph < st; ++ph) {
     for (int pw = 0; pw < st; ++pw) {
       // valid kernel rows r with (ph + pad - r) % st == 0
@@ -396,6 +418,16 @@ static int conv_dgrad_impl(const tmr_conv_desc* d, const float* dy, const float*
       }
       a.Cbytes = clamp_bytes(span((long)d->n * d->h * d->w, a.ldc, d->c));
       a.oH = d->h; a.oW = d->w; a.osy = st; a.osx = st; a.oyc = ph; a.oxc = pw;
+      if (plan) {   // the non-empty classes; the tile of the largest (the first of equals)
+        if (a.K > 0) {
+          ++plan->classes;
+          if (a.M > best_m) {
+            best_m = a.M;
+            tile_of(a, MODE_DGRAD, plan);
+          }
+        }
+        continue;
+      }
       // nothing to add -- unless the fused BN backward must still see (mask, sum) these pixels
       if (a.K == 0 && beta == 1.f && !fz) continue;
       if (fz) {
@@ -758,6 +790,44 @@ TMR_API int tmr_conv2d_wgrad_bnbwd(const tmr_conv_desc* d, const float* x, const
   if (rc) return rc;
   __atomic_fetch_add(&g_wgrad_bnbwd_launches, 1L, __ATOMIC_RELAXED);
   return wgrad_reduce(d, ws, sp, slab, dw_oihw, c_real, beta, stream);
+}
+
+// The launch plan of one view of a conv: host code only, nothing is launched.  Each answer comes
+// from the function the launch itself calls (tile_of; conv_dgrad_impl's class walk; wgrad_plan), on
+// the first (group, frame chunk) slice.  Without operands the pointers count as 16-B aligned.
+TMR_API int tmr_conv2d_tile(const tmr_conv_desc* d, int view, tmr_conv_tile* out) {
+  TMR_CHECK_ARG(d && out, "tmr_conv2d_tile: null descriptor / result");
+  TMR_CHECK_ARG(view >= 0 && view <= 2, "tmr_conv2d_tile: view %d is not 0 (fwd), 1 (dgrad), 2 (wgrad)", view);
+  TMR_CHECK_ARG(d->n > 0 && d->k > 0 && d->c > 0 && d->r > 0 && d->s > 0 && d->stride > 0,
+                "tmr_conv2d_tile: empty descriptor");
+  *out = tmr_conv_tile{};
+  out->cfg = -1;
+  const bool direct = view == 0   ? direct_view(d, &DirectConv::fwd) != nullptr
+                      : view == 1 ? direct_view(d, &DirectConv::dgrad) != nullptr
+                                  : direct_wgrad(d, 0) != nullptr;
+  if (direct) return 0;   // engine 0
+  bool first = true;
+  return for_slices(d, [&](const tmr_conv_desc& c, int, int) -> int {
+    if (!first) return 0;
+    first = false;
+    GemmArgs a;
+    if (view == 0) {
+      bool al;
+      if (const int rc = conv_fwd_args(&c, nullptr, nullptr, nullptr, nullptr, 0.f, a, al)) return rc;
+      tile_of(a, MODE_FWD, out);
+    } else if (view == 1) {
+      if (const int rc = conv_dgrad_impl(&c, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, out))
+        return rc;
+    } else {
+      TMR_CHECK_ARG(c.math == TMR_MATH_F32 || c.math == TMR_MATH_BF16, "tmr_conv2d: bad math mode %d", c.math);
+      TMR_CHECK_ARG(ilog2_exact(c.c) >= 2, "tmr_conv2d_wgrad: stored input channels %d must be a power of two >= 4", c.c);
+      long slab;
+      wgrad_plan(&c, &out->splits, &out->kchunk, &slab);
+      wgrad_fill(&c, a);
+      tile_of(a, MODE_WGRAD, out);
+    }
+    return 0;
+  }, true);
 }
 
 // Plain GEMMs on the same engine ---------------------------------------------

@@ -1304,9 +1304,9 @@ int launch_cfg(const GemmArgs& a, int var, dim3 grid, hipStream_t st) {
 }
 
 // Tile configurations (BM, BN).  Selection keeps both tile dims useful.
-struct TileCfg { int bm, bn; };
-constexpr TileCfg kCfgs[] = {{128, 128}, {256, 64}, {64, 256}, {64, 64},
-                             {256, 128}, {128, 256}, {256, 256}, {256, 256}, {256, 128}};
+struct TileCfg { int bm, bn, waves; };   // (waves: checked against launch_gemm_t's instantiations)
+constexpr TileCfg kCfgs[] = {{128, 128, 4}, {256, 64, 4}, {64, 256, 4}, {64, 64, 4}, {256, 128, 8},
+                             {128, 256, 8}, {256, 256, 16}, {256, 256, 16}, {256, 128, 8}};
 constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 
 inline int env_int(const char* name, int dflt) {
@@ -1385,28 +1385,37 @@ int launch_gemm_t(const GemmArgs& a, bool al, int splits, hipStream_t st) {
   const TileCfg c = kCfgs[cfg];
   dim3 grid(cdiv(a.M, c.bm) * cdiv(a.N, c.bn), splits, 1);
   if (grid.x == 0) return 0;
+  // (each case checks kCfgs's row against the instantiation it launches)
+#define TMR_CFG_CASE(I, BM, BN, WM, WN, ...)                                                     \
+  case I:                                                                                        \
+    static_assert(kCfgs[I].bm == BM && kCfgs[I].bn == BN && kCfgs[I].waves == WM * WN,           \
+                  "kCfgs row " #I);                                                              \
+    return launch_cfg<MODE, BM, BN, WM, WN, __VA_ARGS__>(a, var, grid, st);
   if (a.prec == TMR_MATH_BF16) {
     switch (cfg) {
-      case 0: return launch_cfg<MODE, 128, 128, 2, 2, 32, 1>(a, var, grid, st);
-      case 1: return launch_cfg<MODE, 256, 64, 4, 1, 32, 1>(a, var, grid, st);
-      case 2: return launch_cfg<MODE, 64, 256, 1, 4, 32, 1>(a, var, grid, st);
-      case 3: return launch_cfg<MODE, 64, 64, 2, 2, 32, 1>(a, var, grid, st);
-      case 4: case 8: return launch_cfg<MODE, 256, 128, 4, 2, 32, 1>(a, var, grid, st);
-      case 5: return launch_cfg<MODE, 128, 256, 2, 4, 32, 1>(a, var, grid, st);
+      TMR_CFG_CASE(0, 128, 128, 2, 2, 32, 1)
+      TMR_CFG_CASE(1, 256, 64, 4, 1, 32, 1)
+      TMR_CFG_CASE(2, 64, 256, 1, 4, 32, 1)
+      TMR_CFG_CASE(3, 64, 64, 2, 2, 32, 1)
+      TMR_CFG_CASE(4, 256, 128, 4, 2, 32, 1)
+      TMR_CFG_CASE(8, 256, 128, 4, 2, 32, 1)
+      TMR_CFG_CASE(5, 128, 256, 2, 4, 32, 1)
+      TMR_CFG_CASE(6, 256, 256, 4, 4, 32, 1)
       default: return launch_cfg<MODE, 256, 256, 4, 4, 32, 1>(a, var, grid, st);
     }
   }
   switch (cfg) {
-    case 0: return launch_cfg<MODE, 128, 128, 2, 2, 16>(a, var, grid, st);
-    case 1: return launch_cfg<MODE, 256, 64, 4, 1, 16>(a, var, grid, st);
-    case 2: return launch_cfg<MODE, 64, 256, 1, 4, 16>(a, var, grid, st);
-    case 3: return launch_cfg<MODE, 64, 64, 2, 2, 16>(a, var, grid, st);
-    case 4: return launch_cfg<MODE, 256, 128, 4, 2, 16>(a, var, grid, st);
-    case 5: return launch_cfg<MODE, 128, 256, 2, 4, 16>(a, var, grid, st);
-    case 6: return launch_cfg<MODE, 256, 256, 4, 4, 16>(a, var, grid, st);
-    case 7: return launch_cfg<MODE, 256, 256, 4, 4, 32>(a, var, grid, st);
+    TMR_CFG_CASE(0, 128, 128, 2, 2, 16)
+    TMR_CFG_CASE(1, 256, 64, 4, 1, 16)
+    TMR_CFG_CASE(2, 64, 256, 1, 4, 16)
+    TMR_CFG_CASE(3, 64, 64, 2, 2, 16)
+    TMR_CFG_CASE(4, 256, 128, 4, 2, 16)
+    TMR_CFG_CASE(5, 128, 256, 2, 4, 16)
+    TMR_CFG_CASE(6, 256, 256, 4, 4, 16)
+    TMR_CFG_CASE(7, 256, 256, 4, 4, 32)
     default: return launch_cfg<MODE, 256, 128, 4, 2, 32>(a, var, grid, st);
   }
+#undef TMR_CFG_CASE
 }
 
 // per-view launchers (gemm_fwd.hip / gemm_dgrad.hip / gemm_wgrad.hip)

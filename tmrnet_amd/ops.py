@@ -12,7 +12,7 @@ import weakref
 import numpy as np
 import torch
 
-from ._lib import call, query, stream_ptr, ConvDesc
+from ._lib import call, query, stream_ptr, ConvDesc, ConvTile
 from . import health
 import ctypes
 
@@ -191,6 +191,22 @@ def conv_desc(n, h, w, c, k, r, s, stride, pad, pad_w=None, x_ld=0, y_ld=0, math
         io |= IO_TILES
     return ConvDesc(n, h, w, c, k, r, s, stride, pad, ho, wo, pad_w, x_ld, y_ld, MATH[math],
                     MAX_FRAMES, io, groups if groups > 1 else 0)
+
+
+VIEWS = {"fwd": 0, "dgrad": 1, "wgrad": 2}
+
+
+def conv_tile(n, h, w, c, k, r, s, stride, pad, view, math="fp32", io=0, x_ld=0, y_ld=0,
+              groups=1):
+    """The launch plan of one view ("fwd" / "dgrad" / "wgrad") of a conv (tmr_conv2d_tile): a dict
+    of engine (0 direct kernel, 1 register-staged, 2 LDS-DMA), cfg, bm, bn, waves, tapv, splits,
+    kchunk, classes.  Host code only: needs no GPU.  io as the view's call carries it (the dgrad's
+    IO_WT32 / IO_WT select the LDS-DMA engine)."""
+    d = conv_desc(n, h, w, c, k, r, s, stride, pad, x_ld=x_ld, y_ld=y_ld, math=math, io=io,
+                  groups=groups)
+    t = ConvTile()
+    query("tmr_conv2d_tile", ctypes.byref(d), VIEWS[view], ctypes.byref(t))
+    return {f: getattr(t, f) for f, _ in ConvTile._fields_}
 
 
 def _req_op(t, name):
