@@ -158,9 +158,9 @@ int tmr_conv2d_wgrad(const tmr_conv_desc* d, const float* x, const float* dy, fl
  * by tmr_conv2d_wgrad; the workspace is tmr_conv2d_wgrad_ws_bytes(d).  dy_out must not overlap g
  * or y.  Served: fp32 math, fp32 operands, groups <= 1, one frame chunk, dense 16-B aligned
  * tensors, k % 8 == 0, a wgrad of the engine (not a direct kernel) on a tile config that has the
- * form (64x64, 64x256, 128x128; not 256x256).  tmr_conv2d_wgrad_bnbwd_ok reports 1 when (d and
- * the non-NULL operands given) are served, else 0 -- the caller then keeps the two calls; the
- * fused call itself fails on an unserved case, it never falls back.
+ * form (64x64, 64x256, 128x128 as 8 waves, 256x256 as 16 waves).  tmr_conv2d_wgrad_bnbwd_ok
+ * reports 1 when (d and the non-NULL operands given) are served, else 0 -- the caller then keeps
+ * the two calls; the fused call itself fails on an unserved case, it never falls back.
  * tmr_wgrad_bnbwd_launches: fused launches of this process so far (test instrumentation). */
 int tmr_conv2d_wgrad_bnbwd_ok(const tmr_conv_desc* d, const void* x, const void* g, const void* y,
                               const void* dy_out);
@@ -435,6 +435,15 @@ int tmr_bn_bwd_parts_ds(const void* g, const void* y, const void* parts, int npa
                         const float* save_mean_ds, const float* save_invstd_ds,
                         const float* gamma_ds, void* dy_ds, float* dgamma_ds, float* dbeta_ds,
                         int rows, int c, int bf16, void* ws, size_t ws_bytes, hipStream_t stream);
+/* tmr_bn_bwd_parts_ds with bf16 = 0 and dy and / or dy_ds NULL: both reductions run (dgamma, dbeta
+ * of both BNs), a NULL output is not written, and the other one is written by a single-output
+ * apply pass (12 B per element, the same fmaf sequence: the values of the full call).  With dy NULL
+ * y is not read and may be NULL.  Each BN's coefficients of dy = A*g + B*y + C stay in the caller's
+ * workspace as 3*c floats [A | B | C] at byte offset tmr_bn_bwd_parts_ds_coef_offset(nparts, rows,
+ * c, which) -- which 0: bn3, 1: the downsample BN; > 0, 16-B aligned when ws is -- for
+ * tmr_conv2d_wgrad_bnbwd to apply; the workspace must stay untouched until that consumer has run
+ * on the same stream. */
+size_t tmr_bn_bwd_parts_ds_coef_offset(int nparts, int rows, int c, int which);
 int tmr_bn_bwd_maxpool_a16(const float* dyp, const uint8_t* argmax, int n, int h, int w, int ho,
                            int wo, const void* y, const float* scale, const float* shift,
                            const float* save_mean, const float* save_invstd, const float* gamma,

@@ -95,6 +95,7 @@ SIGNATURES = {
     "tmr_weight_layouts_epb": [],
     "tmr_weight_layouts_multi": [P, I, I, P],
     "tmr_bn_bwd_parts_ds_ws_bytes": [I, I, I],
+    "tmr_bn_bwd_parts_ds_coef_offset": [I, I, I, I],
     "tmr_bn_bwd_parts_ds": [P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P, SZ, P],
     "tmr_bn_bwd_maxpool_a16": [P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P, I, P, SZ, P],
     "tmr_maxpool2d_fwd_bn_a16": [P, P, P, P, P, I, I, I, I, I, I, P],
@@ -214,6 +215,7 @@ _RESTYPES = {
     "tmr_bn_ws_bytes": SZ,
     "tmr_bn_parts_ws_bytes": SZ,
     "tmr_bn_bwd_parts_ds_ws_bytes": SZ,
+    "tmr_bn_bwd_parts_ds_coef_offset": SZ,
     "tmr_sgd_chunk": ctypes.c_int64,
     "tmr_nl_attn_ws_bytes": SZ,
     "tmr_nlblock_saved_bytes": SZ,

@@ -1841,6 +1841,19 @@ TMR_API size_t tmr_bn_bwd_parts_ds_ws_bytes(int nparts, int rows, int c) {
   return (tmr_bn_parts_ws_bytes(nparts, c) + 255) / 256 * 256 + ws_need(rows, c);
 }
 
+// where tmr_bn_bwd_parts_ds leaves its coefficient blocks (3 * c floats [A | B | C] each) in the
+// caller's workspace: which 0 = bn3's, 1 = the downsample BN's (tmr_bn_parts_coef_offset's twin)
+TMR_API size_t tmr_bn_bwd_parts_ds_coef_offset(int nparts, int rows, int c, int which) {
+  if (nparts <= 0 || rows <= 0 || c < 8 || c % 8 || !plan_covers(c) || (which != 0 && which != 1)) {
+    tmr_set_error("tmr_bn_bwd_parts_ds_coef_offset: bad size (parts %d, rows %d, channels %d, "
+                  "which %d)", nparts, rows, c, which);
+    return 0;
+  }
+  if (which == 0) return slab_ws_bytes(nparts, c);
+  const Plan p = make_plan(rows, c);
+  return (tmr_bn_parts_ws_bytes(nparts, c) + 255) / 256 * 256 + (size_t)p.nrb * c * 2 * sizeof(double);
+}
+
 TMR_API int tmr_bn_bwd_parts_ds(const void* g, const void* y, const void* parts, int nparts,
                                 const float* mean, const float* invstd, const float* gamma,
                                 void* dy, float* dgamma, float* dbeta, const void* yd,
@@ -1850,8 +1863,13 @@ TMR_API int tmr_bn_bwd_parts_ds(const void* g, const void* y, const void* parts,
   TMR_CHECK_ARG(c % 8 == 0 && c >= 8 && rows > 0 && nparts > 0,
                 "tmr_bn_bwd_parts_ds: bad shape rows=%d c=%d parts=%d", rows, c, nparts);
   TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd_parts_ds: unsupported channel count %d", c);
-  TMR_CHECK_ARG(g && y && parts && yd && dy && dyd && mean && invstd && gamma && mean_d && invstd_d &&
+  // dy / dy_ds may be NULL (fp32 only): that output's apply is the caller's -- the wgrad that
+  // produces its dy operand (tmr_conv2d_wgrad_bnbwd) from the coefficient block this call leaves
+  // at tmr_bn_bwd_parts_ds_coef_offset.  y is read by bn3's apply alone: NULL with dy.
+  TMR_CHECK_ARG(g && parts && yd && (y || !dy) && mean && invstd && gamma && mean_d && invstd_d &&
                     gamma_d, "tmr_bn_bwd_parts_ds: null operand");
+  TMR_CHECK_ARG((dy && dyd) || !bf16,
+                "tmr_bn_bwd_parts_ds: the coefficient-only and single-output forms are fp32 only");
   TMR_CHECK_ARG((((uintptr_t)g | (uintptr_t)y | (uintptr_t)yd | (uintptr_t)dy | (uintptr_t)dyd) & 15) == 0,
                 "tmr_bn_bwd_parts_ds: g / y / y_ds / dy / dy_ds must be 16-B aligned");
   const size_t a_bytes = (tmr_bn_parts_ws_bytes(nparts, c) + 255) / 256 * 256;
@@ -1887,6 +1905,18 @@ TMR_API int tmr_bn_bwd_parts_ds(const void* g, const void* y, const void* parts,
                      invstd_d, gamma_d, dgamma_d, dbeta_d, coefd);
   TMR_CHECK_LAUNCH("bn_bwd_final");
   const long n8 = (long)rows * c / 8;
+  if (!dy || !dyd) {
+    // one output: the single-output apply on that unit's coefficient block (12 B per element;
+    // bn_bwd_apply_ds8's fmaf sequence, so the values of the dual pass); none: coefficients only
+    if (dy)
+      hipLaunchKernelGGL((bn_bwd_apply8_k<float, float, float>), dim3(ew_blocks(n8)), dim3(NT), 0,
+                         stream, (const float*)g, (const float*)y, coef, (float*)dy, n8, c / 8);
+    else if (dyd)
+      hipLaunchKernelGGL((bn_bwd_apply8_k<float, float, float>), dim3(ew_blocks(n8)), dim3(NT), 0,
+                         stream, (const float*)g, (const float*)yd, coefd, (float*)dyd, n8, c / 8);
+    TMR_CHECK_LAUNCH("bn_bwd_apply");
+    return 0;
+  }
   if (bf16)
     hipLaunchKernelGGL(bn_bwd_apply_ds8<__bf16>, dim3(ew_blocks(n8 / 2)), dim3(NT), 0, stream,
                        (const __bf16*)g, (const __bf16*)y, (const __bf16*)yd, coef, coefd,

@@ -548,6 +548,11 @@ constexpr int occ16() {
 // of n-tile 0 also store their pieces to dY (GemmArgs::Cold): every (m-tile, split) owns its rows
 // x channels, so each element is written once.  Same k order, split plan and epilogue: dW is
 // bit-identical to the wgrad on the materialised dY.
+// BNW = 2 (gemm16_wgrad_bnbwd16_kernel: the 256x256 sixteen-wave tile, 118 of 128 VGPRs as a plain
+// wgrad): the same values from fewer registers.  The m-tile's coefficients sit in 3 * BM floats of
+// LDS behind the two stages and are read per k-tile inside the transform, where no operand
+// fragment is live; the dY store re-reads the lane's own transformed pieces from LDS after the
+// barrier instead of holding them across it.  Only the y pieces in flight stay in registers.
 template <int MODE, int BM, int BN, int WM, int WN, int TAPV, int PIPE, int F32, int NST, int EPF = 0,
           int INF16 = 0, int BNW = 0>
 __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, const int split) {
@@ -580,7 +585,8 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
   constexpr int SMEM1 = STAGE > EPI ? (STAGE > LDSNEED ? STAGE : LDSNEED) : (EPI > LDSNEED ? EPI : LDSNEED);
   constexpr int SMEM2 = 2 * STAGE > EPI ? 2 * STAGE : EPI;
   constexpr int SMEM = NST == 1 ? SMEM1 : (SMEM2 > LDSNEED ? SMEM2 : LDSNEED);
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM];
+  constexpr int CFBYTES = BNW == 2 ? 3 * BM * 4 : 0;   // BNW 2: [A | B | C] of this m-tile
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM + CFBYTES];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -654,7 +660,16 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
     rY = make_rsrc(a.bn_y, a.Abytes);
     rD = make_rsrc(reinterpret_cast<const float*>(a.Cold), a.Abytes);
     dyw = n0 == 0;
-    if (acok[0]) {   // M % 4 == 0: the piece's 4 channels are in range together
+    if constexpr (BNW == 2) {
+      // (channels past M: zeros, and bnw_apply's `ok` is false there anyway)
+      for (int idx = tid; idx < 3 * (BM / 4); idx += 64 * NW) {
+        const int part = idx / (BM / 4), i = m0 + 4 * (idx % (BM / 4));
+        f32x4_t v = {0.f, 0.f, 0.f, 0.f};
+        if (i < a.M) v = *reinterpret_cast<const f32x4_t*>(a.bn_sc + (size_t)part * a.M + i);
+        reinterpret_cast<f32x4_t*>(smem + SMEM)[idx] = v;
+      }
+      __syncthreads();   // the first transform runs before the main loop's first barrier
+    } else if (acok[0]) {   // M % 4 == 0: the piece's 4 channels are in range together
       const int i = (int)(aco[0] / ES);
       cfA = *reinterpret_cast<const f32x4_t*>(a.bn_sc + i);
       cfB = *reinterpret_cast<const f32x4_t*>(a.bn_sc + a.M + i);
@@ -694,6 +709,16 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
       bkr[q] = k;
     }
   }
+
+  // BNW 2: the 256x256 tile has no register to spare, and with whole k-rows per piece (64 * NW
+  // chunks = KQA / KQB rows, even counts) a lane's pieces differ only in their k-row: piece q's
+  // state is piece 0's, KQ * q rows further
+  constexpr bool FOLDQ = BNW == 2;
+  constexpr int KQA = 64 * NW / CPRA, KQB = 64 * NW / CPRB;
+  static_assert(!FOLDQ || (KQA * CPRA == 64 * NW && KQB * CPRB == 64 * NW && KQA % 2 == 0 && KQB % 2 == 0),
+                "folded piece state: whole, even k-row counts per piece");
+  auto akr_of = [&](int q) { return FOLDQ ? akr[0] + KQA * q : akr[q]; };
+  auto bkr_of = [&](int q) { return FOLDQ ? bkr[0] + KQB * q : bkr[q]; };
 
   // ---------------- stage one k-tile into LDS buffer `buf` ----------------
   auto stage = [&](int kt, int buf) {
@@ -769,9 +794,10 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
       // WGRAD A[k=m][i=co] = dY[m][co]
 #pragma unroll
       for (int q = 0; q < NIA; ++q) {
-        const int m = kb + akr[q];
-        const bool ok = acok[q] && m < kend;
-        const uint32_t off = (uint32_t)m * (uint32_t)a.ldb * ES + aco[q];
+        const int qs = FOLDQ ? 0 : q;
+        const int m = kb + akr_of(q);
+        const bool ok = acok[qs] && m < kend;
+        const uint32_t off = (uint32_t)m * (uint32_t)a.ldb * ES + aco[qs];
         glds16(rA, As + 1024 * (wave + NW * q), ok ? off : OOB);
         if constexpr (BNW != 0)
           ypc[q] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rY, ok ? off : OOB, 0, 0));
@@ -779,16 +805,17 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
       // WGRAD B[k=m][j=(tap,c)] = X[src(m, tap)][c]
 #pragma unroll
       for (int q = 0; q < NIB; ++q) {
-        const int m = kb + bkr[q];
+        const int qs = FOLDQ ? 0 : q;
+        const int m = kb + bkr_of(q);
         const uint32_t mm = m < kend ? (uint32_t)m : 0u;
         const uint32_t n = fdiv(mm, a.dHW);
         const uint32_t rem = mm - n * a.dHW.d;
         const uint32_t y = fdiv(rem, a.dW);
         const uint32_t x = rem - y * a.dW.d;
-        const int ys = (int)y * a.sy + bdy[q], xs = (int)x * a.sx + bdx[q];
-        const bool ok = m < kend && bok[q] && (unsigned)ys < (unsigned)a.Hs &&
+        const int ys = (int)y * a.sy + bdy[qs], xs = (int)x * a.sx + bdx[qs];
+        const bool ok = m < kend && bok[qs] && (unsigned)ys < (unsigned)a.Hs &&
                         (unsigned)xs < (unsigned)a.Ws;
-        const uint32_t off = (uint32_t)(((int)n * a.Hs + ys) * a.Ws + xs) * (uint32_t)a.lds * ES + bco[q];
+        const uint32_t off = (uint32_t)(((int)n * a.Hs + ys) * a.Ws + xs) * (uint32_t)a.lds * ES + bco[qs];
         glds16(rB, Bs + 1024 * (wave + NW * q), ok ? off : OOB);
       }
     }
@@ -919,32 +946,43 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
   // pieces to the dY tensor after that barrier (bnw_store): the barrier's fence drains vmcnt, so
   // stores issued before it would put their latency in front of every k-tile; issued after it
   // they retire under the tile's MFMAs, before the next iteration's vmcnt(0).
-  f32x4_t dyo[BNW ? NIA : 1];
+  f32x4_t dyo[BNW == 1 ? NIA : 1];
   auto bnw_apply = [&](int kt, int buf) {
     const int kb = kbeg + kt * BK;
     unsigned char* As = smem + buf * STAGE;
 #pragma unroll
     for (int q = 0; q < NIA; ++q) {
       f32x4_t* pc = reinterpret_cast<f32x4_t*>(As + 1024 * (wave + NW * q) + 16 * lane);
-      const int m = kb + akr[q];
-      const bool ok = acok[q] && m < kend;
+      const int m = kb + akr_of(q);
+      const bool ok = acok[FOLDQ ? 0 : q] && m < kend;
       const f32x4_t gv = *pc, yv = ypc[q];
       f32x4_t o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = ok ? fmaf(cfA[e], gv[e], fmaf(cfB[e], yv[e], cfC[e])) : 0.f;
       *pc = o;
-      dyo[q] = o;
+      if constexpr (BNW == 1) dyo[q] = o;
     }
   };
   auto bnw_store = [&](int kt) {
     const int kb = kbeg + kt * BK;
+    const unsigned char* As = smem + (kt & 1) * STAGE;
 #pragma unroll
     for (int q = 0; q < NIA; ++q) {
-      const int m = kb + akr[q];
-      const bool ok = acok[q] && m < kend;
-      const uint32_t off = (uint32_t)m * (uint32_t)a.ldb * ES + aco[q];
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, dyo[q]), rD, ok ? off : OOB, 0, 0);
+      const int m = kb + akr_of(q);
+      const bool ok = acok[FOLDQ ? 0 : q] && m < kend;
+      const uint32_t off = (uint32_t)m * (uint32_t)a.ldb * ES + aco[FOLDQ ? 0 : q];
+      f32x4_t o;
+      if constexpr (BNW == 1) o = dyo[q];
+      else o = *reinterpret_cast<const f32x4_t*>(As + 1024 * (wave + NW * q) + 16 * lane);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, o), rD, ok ? off : OOB, 0, 0);
     }
+  };
+
+  // BNW 2: this lane's chunk of the m-tile's coefficients, from LDS, per k-tile -- issued in front
+  // of the vmcnt wait (they do not depend on the tile), dead again once the transform is done
+  auto bnw_coefs = [&]() {
+    const f32x4_t* cf = reinterpret_cast<const f32x4_t*>(smem + SMEM) + ((int)(aco[0] / 16) - m0 / 4);
+    cfA = cf[0]; cfB = cf[BM / 4]; cfC = cf[2 * (BM / 4)];
   };
 
   // ---------------- main loop: two LDS stages ----------------
@@ -975,6 +1013,7 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& a, const int bid, co
     // before the previous k-step's MFMAs; MFMA clusters at raised priority
     stage(0, 0);
     for (int kt = 0; kt < ntiles; ++kt) {
+      if constexpr (BNW == 2) bnw_coefs();
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if constexpr (BNW != 0) bnw_apply(kt, kt & 1);
       __syncthreads();
@@ -1031,6 +1070,17 @@ void gemm16_wgrad_bnbwd_kernel(const GemmArgs a) {
   int bid, split;
   xcd_work(bid, split);
   gemm16_body<MODE_WGRAD, BM, BN, WM, WN, 0, 1, 1, 2, 0, 0, 1>(a, bid, split);
+}
+
+// The same for the 256x256 sixteen-wave tile (gemm16_body's BNW = 2: coefficients in LDS, the dY
+// store re-read from LDS), again under a name of its own.
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(64 * WM * WN, (occ16<BM, BN, WM, WN, 2>()))
+void gemm16_wgrad_bnbwd16_kernel(const GemmArgs a) {
+  static_assert(WM * WN == 16, "the sixteen-wave form");
+  int bid, split;
+  xcd_work(bid, split);
+  gemm16_body<MODE_WGRAD, BM, BN, WM, WN, 0, 1, 1, 2, 0, 0, 2>(a, bid, split);
 }
 
 // Tile w of a GemmPar launch -> (class, tile of that class).  The classes' tiles go out in

@@ -155,10 +155,10 @@ extern template int launch_gemm16<MODE_WGRAD, 1>(const GemmArgs&, int, hipStream
 
 // The fp32 wgrad that produces its dY operand from (g, y, BN-backward coefficients) while loading
 // it (tmr_conv2d_wgrad_bnbwd; gemm16_kernel.h BNW, gemm16_wgrad_f32.hip): the tile configs that
-// have the form -- 64x64, 64x256 and 128x128 as 8 waves.  256x256 as 16 waves runs at 118 of its
-// 128 VGPRs and has no room for the y pieces and coefficients: those units keep the separate
-// apply pass (profiles/wgrad_bnbwd/).
-inline bool wgrad_bnbwd_cfg(int cfg) { return cfg == 4 || cfg == 5 || cfg == 7; }
+// have the form -- 64x64, 64x256, 128x128 as 8 waves, and 256x256 as 16 waves in a form of its own
+// (118 of 128 VGPRs as a plain wgrad: coefficients in LDS, nothing held across the barrier;
+// profiles/wgrad_bnbwd_ds/).
+inline bool wgrad_bnbwd_cfg(int cfg) { return cfg == 4 || cfg == 5 || cfg == 6 || cfg == 7; }
 int launch_gemm16_wgrad_bnbwd(const GemmArgs& a, int splits, hipStream_t st);
 // fused launches so far (tmr_wgrad_bnbwd_launches)
 extern long g_wgrad_bnbwd_launches;

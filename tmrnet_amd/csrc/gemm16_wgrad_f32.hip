@@ -25,6 +25,7 @@ int launch_gemm16_wgrad_bnbwd(const GemmArgs& a, int splits, hipStream_t st) {
   switch (cfg) {
     case 4: hipLaunchKernelGGL((gemm16_wgrad_bnbwd_kernel<64, 256, 1, 4>), grid, dim3(256), 0, st, a); break;
     case 5: hipLaunchKernelGGL((gemm16_wgrad_bnbwd_kernel<64, 64, 2, 2>), grid, dim3(256), 0, st, a); break;
+    case 6: hipLaunchKernelGGL((gemm16_wgrad_bnbwd16_kernel<256, 256, 4, 4>), grid, dim3(1024), 0, st, a); break;
     case 7: hipLaunchKernelGGL((gemm16_wgrad_bnbwd_kernel<128, 128, 4, 2>), grid, dim3(512), 0, st, a); break;
     default: break;
   }

@@ -744,7 +744,7 @@ static const char* wgrad_bnbwd_why(const tmr_conv_desc* d, int c_real, const voi
   wgrad_fill(d, a);
   if (!use16(a, MODE_WGRAD)) return "not an LDS-DMA engine wgrad";
   if (!wgrad_bnbwd_cfg(pick_cfg16(a.M, a.N, a.K, MODE_WGRAD, true)))
-    return "tile config without the fused form (256x256)";
+    return "tile config without the fused form";
   return nullptr;
 }
 

@@ -412,11 +412,17 @@ def bn_bwd_maxpool(dyp, am, y, scale, shift, mean, inv, gamma, bf16=False):
     return dy, dgamma, dbeta
 
 
-def bn_bwd_parts_ds(g, y, parts, nparts, mean, inv, gamma, yd, mean_d, inv_d, gamma_d):
+def bn_bwd_parts_ds(g, y, parts, nparts, mean, inv, gamma, yd, mean_d, inv_d, gamma_d,
+                    fold3=False, foldd=False):
     """BN backward of a downsample block's bn3 (from the fused dgrad's partials, g already
     masked) and of its downsample BN (a reduction pass over g and y_ds), with one apply pass that
     reads g once -> (dy, dgamma, dbeta, dy_ds, dgamma_ds, dbeta_ds); the values of bn_bwd_parts +
-    bn_bwd.  g, y, y_ds all fp32 or all bf16 (the dy's take their dtype)."""
+    bn_bwd.  g, y, y_ds all fp32 or all bf16 (the dy's take their dtype).
+    fold3 / foldd (fp32): that unit's wgrad produces its dy itself (conv_wgrad_bnbwd) -- the same
+    entry point with that output NULL; the result is then bn_bwd_parts_ds_coef's."""
+    if fold3 or foldd:
+        return bn_bwd_parts_ds_coef(g, y, parts, nparts, mean, inv, gamma, yd, mean_d, inv_d,
+                                    gamma_d, apply3=not fold3, applyd=not foldd)
     c = y.shape[-1]
     rows = y.numel() // c
     t = y.dtype
@@ -433,6 +439,37 @@ def bn_bwd_parts_ds(g, y, parts, nparts, mean, inv, gamma, yd, mean_d, inv_d, ga
          inv_d, gamma_d, dyd, dgd, dbd, rows, c, int(t == BF16), ws, ctypes.c_size_t(ws.numel() * 8),
          stream_ptr())
     return dy, dg, db, dyd, dgd, dbd
+
+
+def bn_bwd_parts_ds_coef(g, y, parts, nparts, mean, inv, gamma, yd, mean_d, inv_d, gamma_d,
+                         apply3=False, applyd=False):
+    """bn_bwd_parts_ds (fp32) with the apply left to conv_wgrad_bnbwd: both reductions, then at
+    most one single-output apply pass -> (coef, dgamma, dbeta, coef_ds, dgamma_ds, dbeta_ds, dy,
+    dy_ds).  coef / coef_ds: each BN's 3*c coefficients [A | B | C] of dy = A*g + B*y + C, views
+    into this call's workspace; dy / dy_ds: written only where apply3 / applyd asks (else None),
+    with the values of the full call."""
+    c = y.shape[-1]
+    rows = y.numel() // c
+    if not (g.dtype == y.dtype == yd.dtype == f32 and g.shape == y.shape == yd.shape
+            and g.is_contiguous() and y.is_contiguous() and yd.is_contiguous()):
+        raise RuntimeError("bn_bwd_parts_ds_coef: g, y and y_ds must be contiguous fp32 tensors of "
+                           "one shape")
+    if apply3 and applyd:
+        raise RuntimeError("bn_bwd_parts_ds_coef: both outputs are bn_bwd_parts_ds")
+    nb = query("tmr_bn_bwd_parts_ds_ws_bytes", int(nparts), rows, c)
+    off3 = query("tmr_bn_bwd_parts_ds_coef_offset", int(nparts), rows, c, 0)
+    offd = query("tmr_bn_bwd_parts_ds_coef_offset", int(nparts), rows, c, 1)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=y.device)
+    dy = torch.empty_like(y) if apply3 else None
+    dyd = torch.empty_like(yd) if applyd else None
+    dg, db = _empty((c,), mean), _empty((c,), mean)
+    dgd, dbd = _empty((c,), mean), _empty((c,), mean)
+    call("tmr_bn_bwd_parts_ds", g, y, parts, int(nparts), mean, inv, gamma, dy, dg, db, yd, mean_d,
+         inv_d, gamma_d, dyd, dgd, dbd, rows, c, 0, ws, ctypes.c_size_t(ws.numel() * 8),
+         stream_ptr())
+    wf = ws.view(f32)
+    return (wf[off3 // 4: off3 // 4 + 3 * c], dg, db, wf[offd // 4: offd // 4 + 3 * c], dgd, dbd,
+            dy, dyd)
 
 
 def bn_bwd_parts(g, y, parts, nparts, mean, inv, gamma, bf16=False):

@@ -133,10 +133,36 @@ DS_DUAL = True
 # fp32 step: a unit whose masked gradient comes from a fused dgrad (parts) lets its wgrad produce
 # dy = A*g + B*y + C while loading its dy operand (tmr_conv2d_wgrad_bnbwd) instead of a separate
 # BatchNorm-backward apply pass: the same dy and dW bit for bit, 12 instead of 16 B moved per dy
-# element (profiles/wgrad_bnbwd/).  Units the fused form does not serve (ops.conv_wgrad_bnbwd_ok:
-# the 256x256-tile wgrads, direct kernels) keep the two calls.  A module attribute for the
-# bit-identity test.
+# element (profiles/wgrad_bnbwd/, profiles/wgrad_bnbwd_ds/ for the 256x256 tile's form).  Units
+# the fused form does not serve (ops.conv_wgrad_bnbwd_ok: direct kernels, misaligned or chunked
+# operands) keep the two calls.  A module attribute for the bit-identity test.
 WGRAD_BNBWD = True
+
+# fp32 step, downsample blocks: the same fold for bn3 and the downsample BN, which share the
+# block's masked gradient g.  tmr_bn_bwd_parts_ds then runs its two reductions only (or one
+# single-output apply for a unit the fused wgrad does not take), and each served unit's wgrad
+# produces its own dy from (g, its y, its coefficients): dy3, dy_ds, both dW and the four BN
+# gradients bit for bit (profiles/wgrad_bnbwd_ds/).  WGRAD_BNBWD_DS_MIN: dy elements from which a
+# block takes the route.  Per launch, at 640 and at 40 frames of 224x224, the fold won on every
+# block of 8.0e6 elements and more (0.02-0.83 ms) and broke even at 4.0e6 (l4.0 at 40 frames:
+# 0.331 against 0.323 ms); below that nothing was measured and the dual apply stays.  Module
+# attributes for the bit-identity test.
+WGRAD_BNBWD_DS = True
+WGRAD_BNBWD_DS_MIN = 8_000_000
+
+
+def _ds_fold(g, r3, rd):
+    """Which of a downsample block's two units (bn3's conv3, the downsample conv) let their wgrad
+    produce dy (WGRAD_BNBWD_DS) -> (fold3, foldd)."""
+    if not (WGRAD_BNBWD and WGRAD_BNBWD_DS and g.dtype == torch.float32
+            and r3["math"] == "fp32" and rd["math"] == "fp32" and g.numel() >= WGRAD_BNBWD_DS_MIN):
+        return False, False
+
+    def ok(rec):
+        kr, ks = rec["conv"].weight.shape[2:]
+        return (rec.get("groups", 1) == 1 and
+                ops.conv_wgrad_bnbwd_ok(rec["x"], g, rec["y"], kr, ks, rec["stride"], rec["pad"]))
+    return ok(r3), ok(rd)
 
 
 def _ds_dual(g, r3, rd):
@@ -262,7 +288,7 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
 
 def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need_dx=True,
                  dres_inplace=False, parts=None, fuse_prev=None, pool=None, dy=None, g16=False,
-                 r16=False, fold=False):
+                 r16=False, fold=False, gcoef=None):
     """BN backward, wgrad, dgrad (optionally accumulated into dx_out) of one conv+BN unit.
 
     parts: dz was produced by a fused dgrad (conv_dgrad_bnbwd): it is already ReLU-masked and
@@ -280,13 +306,20 @@ def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need
     r16: the same for fuse_prev a block output (R16): the dgrad adds into dx_out (bf16 in place,
     or fp32 read and a new bf16 tensor returned).
     fold: with parts, the fp32 wgrad may produce dy itself (WGRAD_BNBWD) where the library serves
-    the unit; the ResNet-50 trunk's units only."""
+    the unit; the ResNet-50 trunk's units only.
+    gcoef: (g, coef) in place of dy -- the caller ran the BN backward's reductions
+    (ops.bn_bwd_parts_ds_coef) and the fused wgrad produces dy from the masked gradient g, this
+    unit's y and its coefficients; only wgrad and dgrad run here."""
     conv, bn = rec["conv"], rec["bn"]
     s16 = _store16(rec["math"])   # dy feeds only this conv's dgrad / wgrad
-    dy_given = dy is not None
+    dy_given = dy is not None or gcoef is not None
     dw = None
     kr, ks = conv.weight.shape[2:]
-    if dy_given:
+    if gcoef is not None:
+        dw, dy = ops.conv_wgrad_bnbwd(rec["x"], gcoef[0], rec["y"], gcoef[1], kr, ks, rec["stride"],
+                                      rec["pad"], c_real=rec["c_real"])
+        dres = None
+    elif dy_given:
         dres = None
     elif pool is not None:
         # the stem: maxpool backward + ReLU mask + BN backward without writing dz
@@ -457,18 +490,27 @@ class TrunkFn(torch.autograd.Function):
             # the previous block's last unit: its BN output gradient is this block's dx
             prev3 = blocks[-1][1][-1] if blocks else None
             # g (owned here) becomes the masked pre-ReLU gradient = the identity-branch grad
-            dyd = None
+            dyd = gcd = None
             if (has_ds and _ds_dual(g, r3, rd) and pending is not None):
                 # (g came masked from the next block's fused dgrad)
-                dy3, dg3, db3, dyd, dgd, dbd = ops.bn_bwd_parts_ds(
-                    g, r3["y"], pending[0], pending[1], r3["mean"], r3["inv"],
-                    r3["bn"].weight.detach(), rd["y"], rd["mean"], rd["inv"],
-                    rd["bn"].weight.detach())
+                bargs = (g, r3["y"], pending[0], pending[1], r3["mean"], r3["inv"],
+                         r3["bn"].weight.detach(), rd["y"], rd["mean"], rd["inv"],
+                         rd["bn"].weight.detach())
+                f3, fd = _ds_fold(g, r3, rd)
+                gc3 = None
+                if f3 or fd:
+                    # the served units' wgrads produce their dy themselves (g outlives both: dres)
+                    c3, dg3, db3, cd, dgd, dbd, dy3, dyd = ops.bn_bwd_parts_ds(
+                        *bargs, fold3=f3, foldd=fd)
+                    gc3 = (g, c3) if f3 else None
+                    gcd = (g, cd) if fd else None
+                else:
+                    dy3, dg3, db3, dyd, dgd, dbd = ops.bn_bwd_parts_ds(*bargs)
                 grads[r3["bn"].weight], grads[r3["bn"].bias] = dg3, db3
                 grads[rd["bn"].weight], grads[rd["bn"].bias] = dgd, dbd
-                dz2, _, fz2 = _conv_bn_bwd(r3, None, grads, fuse_prev=r2, g16=True, dy=dy3)
+                dz2, _, fz2 = _conv_bn_bwd(r3, None, grads, fuse_prev=r2, g16=True, dy=dy3, gcoef=gc3)
                 dres = g
-                del dy3
+                del dy3, gc3
             else:
                 dz2, dres, fz2 = _conv_bn_bwd(r3, g, grads, want_dres=True, dres_inplace=True,
                                               parts=pending, fuse_prev=r2, g16=True, fold=True)
@@ -480,9 +522,9 @@ class TrunkFn(torch.autograd.Function):
                 # the stride-1 conv1 dgrad accumulates into it with the fused BN backward
                 # (measured 51.1 vs 51.6 ms of dgrads per C2 step against the other order,
                 # profiles/r3/bench_r4f/)
-                if dyd is not None:
-                    dx, _, _ = _conv_bn_bwd(rd, None, grads, dy=dyd)
-                    del dyd
+                if dyd is not None or gcd is not None:
+                    dx, _, _ = _conv_bn_bwd(rd, None, grads, dy=dyd, gcoef=gcd)
+                    del dyd, gcd
                 else:
                     dx, _, _ = _conv_bn_bwd(rd, dres, grads)
                 dx, _, pending = _conv_bn_bwd(r1, dz1, grads, parts=fz1, dx_out=dx, dx_beta=1.0,
