@@ -547,6 +547,60 @@ int tmr_jpeg_reconstruct(const int16_t* coef, const uint16_t* qt, int f, int h, 
                          int sampling, uint8_t* ws, size_t ws_bytes, uint8_t* out,
                          const int32_t* out_index, int out_frames, hipStream_t stream);
 
+/* Entropy decode on the device (jpeg_host.cpp packs, jpeg_entropy.hip decodes; opt-in).
+ * Host: the scan of a status-0 file without a restart interval, packed for the kernel --
+ *   bits    the entropy-coded segment with the byte stuffing removed (FF 00 -> FF), up to the
+ *           marker that ends it, zero-padded to desc->bits_bytes = (bytes + 8) rounded up to 16;
+ *   tables  the distinct Huffman tables the scan names, desc->ntables of them, in the decoder's
+ *           own form (9-bit first-level lut, one-lookup fast entries, canonical maxcode / valoff);
+ *   desc    bit count, block grids, MCU layout, which table each component uses, and the offsets
+ *           bits_off / tables_off that the caller says the two blocks have in its batch buffer.
+ * bits_cap >= TMR_JPEG_SCAN_CAP(len) and tables_cap >= TMR_JPEG_MAX_TABLES * sizeof(tmr_jpeg_huff)
+ * always suffice; a smaller buffer that the file does not fit is refused (3) before anything is
+ * written.  Status as above, and TMR_JPEG_HOST_PASS: decodable, but by tmr_jpeg_entropy_decode
+ * only (the file has a restart interval).  With bits, tables and desc all null the call packs
+ * nothing and returns the status a full call would (info is filled as by the probe). */
+#define TMR_JPEG_HOST_PASS 4
+#define TMR_JPEG_MAX_TABLES 6
+#define TMR_JPEG_SCAN_CAP(len) ((((size_t)(len) + 8) + 15) & ~(size_t)15)
+typedef struct tmr_jpeg_huff {
+  uint16_t lut[512];   /* (length << 8) | symbol for codes of <= 9 bits, else 0 */
+  int32_t fast[512];   /* AC: value * 256 + run * 16 + (length + value bits), else 0 */
+  int32_t maxcode[18]; /* largest code of each length, -1 where there is none */
+  int32_t valoff[17];  /* index of a length's first symbol minus its first code */
+  int32_t nsym;
+  uint8_t sym[256];
+} tmr_jpeg_huff;
+typedef struct tmr_jpeg_scan_desc {
+  uint64_t bits_off, tables_off; /* byte offsets in the batch buffer, multiples of 16 */
+  uint32_t nbits;                /* bits of entropy-coded data (a multiple of 8) */
+  uint32_t bits_bytes;           /* bytes written at bits_off, padding included */
+  int32_t ntables;
+  int32_t ncomp, sampling, width, height;
+  int32_t blocks_w[3], blocks_h[3];
+  int32_t mcu_blocks;  /* blocks per MCU: 1, 3 or 6 */
+  uint8_t slot_comp[8]; /* component of each block of an MCU, in scan order */
+  uint8_t dc_table[4], ac_table[4]; /* per component: index into the frame's tables */
+  uint32_t reserved[2];
+} tmr_jpeg_scan_desc;
+int tmr_jpeg_scan_pack(const uint8_t* data, size_t len, tmr_jpeg_info* info, uint8_t* bits,
+                       size_t bits_cap, uint64_t bits_off, tmr_jpeg_huff* tables, size_t tables_cap,
+                       uint64_t tables_off, tmr_jpeg_scan_desc* desc);
+/* Device (jpeg_entropy.hip): f frames of one size and sampling class; desc (f descriptors) and
+ * buf (the batch buffer their offsets point into, buf_bytes long) in device memory.  Writes coef =
+ * f x coef_bytes in exactly tmr_jpeg_entropy_decode's layout (every entry) and status[f]:
+ * 0 = the coefficients equal the host decoder's bit for bit; 1 = the scan ran out of data, 2 = bad
+ * code, run past 63 or DC size > 11 (the host decoder refuses the same scans), 3 = the descriptor
+ * does not fit the arguments; coefficients of a non-zero status are unspecified.  One workgroup
+ * per frame runs a self-synchronising decode over subsequences of sub_bits bits (0: the default,
+ * 1024; else a multiple of 32, >= 64); max_bits bounds every frame's nbits and sizes the
+ * workspace: first f uint32 round counts, then the per-subsequence states. */
+size_t tmr_jpeg_entropy_ws_bytes(int f, uint32_t max_bits, int sub_bits);
+int tmr_jpeg_entropy_decode_device(const tmr_jpeg_scan_desc* desc, const uint8_t* buf,
+                                   size_t buf_bytes, int f, int h, int w, int sampling,
+                                   uint32_t max_bits, int sub_bits, int16_t* coef, int32_t* status,
+                                   void* ws, size_t ws_bytes, hipStream_t stream);
+
 /* ---------------- pooling (pool_layout.hip) --------------------------------------- */
 /* MaxPool2d(3,2,1) of share.maxpool (train_only_non-local_pretrained.py:207), NHWC */
 int tmr_maxpool2d_fwd(const float* x, float* y, uint8_t* argmax, int n, int h, int w, int c,

@@ -6,6 +6,8 @@ Variants, each at every --workers count:
   threads    decode_frames: pil_loader (:96-99) in a thread pool into a pinned batch
   processes  DecodePool: pil_loader in worker processes into a pinned shared-memory batch
   device     tmrnet_amd.jpeg.DeviceJpegDecoder: entropy decode in threads, the rest in jpeg.hip
+  device_entropy  the same with entropy="device": the threads only pack the scans, the Huffman
+             decode runs in jpeg_entropy.hip
 `processes` and `device` submit batch i + 1 before they take batch i (their submit / result
 pairs), `threads` has no such pair and runs batch after batch.
 
@@ -13,8 +15,11 @@ Protocol (DESIGN.md §18's): one warm-up of every variant, then --rounds rounds 
 variants run alternately, all in this process tree; per variant the median frames/s to the resized
 device batch and spread = (max - min) / median.  `device` also reports its host pass alone
 (entropy decode into pinned memory, no copy, no kernels) and the time of the reconstruction
-kernels per frame from device events.  The last line compares `device` with `processes` at the
-largest worker count of the same run.
+kernels per frame from device events; `device_entropy` splits that time into the entropy and the
+reconstruction kernels and adds the median and maximum number of re-decode rounds a frame needed.
+The last lines compare `device` and `device_entropy` with `processes`, and `device_entropy` with
+`device`, at the largest worker count of the same run.  --out appends every line to a file
+(profiles/jpeg_decode/entropy.jsonl holds the run DESIGN.md §25 quotes).
 
 Synthetic JPEGs (smooth colour field + noise, quality 95, written to a temp dir) at Cholec80's
 native 854x480 and at a pre-resized 250x250.  One JSON line per (size, variant, workers)."""
@@ -56,9 +61,10 @@ class Variant:
         self.pool = self.dec = None
         if mode == "processes":
             self.pool = frames.DecodePool(workers=nw)
-        elif mode == "device":
+        elif mode in ("device", "device_entropy"):
             from tmrnet_amd.jpeg import DeviceJpegDecoder
-            self.dec = DeviceJpegDecoder(workers=nw, device=dev)
+            self.dec = DeviceJpegDecoder(workers=nw, device=dev,
+                                         entropy="device" if mode == "device_entropy" else "host")
 
     def _finish(self, dev_batch):
         if tuple(dev_batch.shape[1:3]) == tuple(self.frames.RESIZE):
@@ -92,8 +98,17 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--workers", default="8,16")
     ap.add_argument("--sizes", default="854x480,250x250")
-    ap.add_argument("--modes", default="threads,processes,device")
+    ap.add_argument("--modes", default="threads,processes,device,device_entropy")
+    ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     args = ap.parse_args()
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench: the resized batch lives on the device; no GPU is visible")
@@ -136,27 +151,37 @@ def main():
                             hp.append(args.frames / (time.perf_counter() - t0))
                         rec["host_pass_frames_per_s"] = round(float(np.median(hp)), 1)
                         rec["upload_bytes_per_frame"] = nbytes // args.frames
-                        v.dec.kernel_events = []
+                        v.dec.kernel_events, v.dec.entropy_events, v.dec.entropy_rounds = [], [], []
                         for _ in range(args.rounds):
                             v.dec.decode(paths)
                         torch.cuda.synchronize()
                         ms = [a.elapsed_time(b) for a, b in v.dec.kernel_events]
                         v.dec.kernel_events = None
                         rec["kernels_us_per_frame"] = round(1e3 * float(np.median(ms)) / args.frames, 3)
+                        if v.dec.entropy_events:
+                            ems = [a.elapsed_time(b) for a, b in v.dec.entropy_events]
+                            e_us = 1e3 * float(np.median(ems)) / args.frames
+                            rec["entropy_kernels_us_per_frame"] = round(e_us, 3)
+                            rec["reconstruct_kernels_us_per_frame"] = round(
+                                rec["kernels_us_per_frame"] - e_us, 3)
+                            rec["rounds_median"] = float(np.median(v.dec.entropy_rounds))
+                            rec["rounds_max"] = int(max(v.dec.entropy_rounds))
+                        rec["entropy_device_frames"] = v.dec.stats["entropy_device"]
                         rec["device_frames"] = v.dec.stats["device"]
                         rec["fallback_frames"] = v.dec.stats["fallback"]
                     summary[(v.mode, v.nw)] = rec
-                    print(json.dumps(rec), flush=True)
+                    emit(rec)
                 top = max(workers)
-                a, b = summary.get(("device", top)), summary.get(("processes", top))
-                if a and b:
-                    gain = 100 * (a["frames_per_s"] / b["frames_per_s"] - 1)
-                    noise = max(a["spread_pct"], b["spread_pct"])
-                    print(json.dumps({"stage": "frames-from-files", "size": size, "workers": top,
-                                      "device_over_processes_pct": round(gain, 2),
-                                      "larger_spread_pct": noise,
-                                      "verdict": "gain" if gain > noise else
-                                                 ("loss" if -gain > noise else "no difference")}), flush=True)
+                for x, y in (("device", "processes"), ("device_entropy", "processes"),
+                             ("device_entropy", "device")):
+                    a, b = summary.get((x, top)), summary.get((y, top))
+                    if a and b:
+                        gain = 100 * (a["frames_per_s"] / b["frames_per_s"] - 1)
+                        noise = max(a["spread_pct"], b["spread_pct"])
+                        emit({"stage": "frames-from-files", "size": size, "workers": top,
+                              "%s_over_%s_pct" % (x, y): round(gain, 2), "larger_spread_pct": noise,
+                              "verdict": "gain" if gain > noise else
+                                         ("loss" if -gain > noise else "no difference")})
             finally:
                 for v in variants:
                     v.close()

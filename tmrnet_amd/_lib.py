@@ -53,6 +53,30 @@ class JpegInfo(ctypes.Structure):
 
 JP = ctypes.POINTER(JpegInfo)
 
+
+class JpegHuff(ctypes.Structure):
+    """tmr_jpeg_huff: one Huffman table in the form the device entropy decoder reads."""
+    _fields_ = [("lut", ctypes.c_uint16 * 512), ("fast", ctypes.c_int32 * 512),
+                ("maxcode", ctypes.c_int32 * 18), ("valoff", ctypes.c_int32 * 17),
+                ("nsym", ctypes.c_int32), ("sym", ctypes.c_uint8 * 256)]
+
+
+class JpegScanDesc(ctypes.Structure):
+    """tmr_jpeg_scan_desc: one frame's packed scan (tmr_jpeg_scan_pack)."""
+    _fields_ = [("bits_off", ctypes.c_uint64), ("tables_off", ctypes.c_uint64),
+                ("nbits", ctypes.c_uint32), ("bits_bytes", ctypes.c_uint32),
+                ("ntables", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("sampling", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("blocks_w", ctypes.c_int32 * 3), ("blocks_h", ctypes.c_int32 * 3),
+                ("mcu_blocks", ctypes.c_int32), ("slot_comp", ctypes.c_uint8 * 8),
+                ("dc_table", ctypes.c_uint8 * 4), ("ac_table", ctypes.c_uint8 * 4),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+JPEG_HOST_PASS = 4       # tmr_jpeg_scan_pack: decodable, but by the host entropy pass only
+JPEG_MAX_TABLES = 6
+U32 = ctypes.c_uint32
+
 # name -> argtypes (restype is int unless listed in _RESTYPES)
 SIGNATURES = {
     "tmr_abi_version": [],
@@ -116,6 +140,9 @@ SIGNATURES = {
     "tmr_jpeg_entropy_decode": [P, SZ, JP, P, SZ],
     "tmr_jpeg_ws_bytes": [I, I, I, I],
     "tmr_jpeg_reconstruct": [P, P, I, I, I, I, P, SZ, P, P, I, P],
+    "tmr_jpeg_scan_pack": [P, SZ, JP, P, SZ, U64, P, SZ, U64, P],
+    "tmr_jpeg_entropy_ws_bytes": [I, U32, I],
+    "tmr_jpeg_entropy_decode_device": [P, P, SZ, I, I, I, I, U32, I, P, P, P, SZ, P],
     "tmr_gemm_nt": [I, I, I, P, I, P, I, P, P, I, F, P],
     "tmr_gemm_nn": [I, I, I, P, I, P, I, P, I, F, P],
     "tmr_gemm_tn": [I, I, I, P, I, P, I, P, I, F, P],
@@ -212,6 +239,7 @@ _RESTYPES = {
     "tmr_resize_tmp_bytes": SZ,
     "tmr_margin_ws_bytes": SZ,
     "tmr_jpeg_ws_bytes": SZ,
+    "tmr_jpeg_entropy_ws_bytes": SZ,
     "tmr_bn_ws_bytes": SZ,
     "tmr_bn_parts_ws_bytes": SZ,
     "tmr_bn_bwd_parts_ds_ws_bytes": SZ,

@@ -386,6 +386,93 @@ TMR_JPEG_API int tmr_jpeg_probe(const uint8_t* data, size_t len, tmr_jpeg_info* 
   return fail(kBad, who, "truncated: no marker ends the scan data");
 }
 
+// The scan packed for the device entropy decoder (jpeg_entropy.hip): the same header parse, then
+// a byte copy that drops the stuffed zeros and stops where Bits::refill stops -- at a marker, at
+// a lone 0xFF in the last byte, or at the end of the input.
+TMR_JPEG_API int tmr_jpeg_scan_pack(const uint8_t* data, size_t len, tmr_jpeg_info* info,
+                                    uint8_t* bits, size_t bits_cap, uint64_t bits_off,
+                                    tmr_jpeg_huff* tables, size_t tables_cap, uint64_t tables_off,
+                                    tmr_jpeg_scan_desc* desc) {
+  static const char who[] = "tmr_jpeg_scan_pack";
+  Header hd;
+  int rc = probe(data, len, who, &hd, info);
+  if (rc) return rc;
+  if (hd.restart)
+    return fail(TMR_JPEG_HOST_PASS, who, "restart interval: this file keeps the host entropy pass");
+  if (!bits && !tables && !desc) return kOk;   // a query: the status alone, nothing packed
+  if (!bits || !tables || !desc) return fail(kArgs, who, "null output");
+  if ((bits_off & 15) || (tables_off & 15)) return fail(kArgs, who, "offsets must be multiples of 16");
+
+  // the distinct tables the scan names, in order of first use
+  const Huff* used[TMR_JPEG_MAX_TABLES];
+  int ntab = 0;
+  uint8_t dc_ix[4] = {0, 0, 0, 0}, ac_ix[4] = {0, 0, 0, 0};
+  for (int c = 0; c < hd.ncomp; ++c) {
+    for (int kind = 0; kind < 2; ++kind) {
+      const Huff* t = kind ? &hd.ac[hd.comp[c].ta] : &hd.dc[hd.comp[c].td];
+      int at = 0;
+      while (at < ntab && used[at] != t) ++at;
+      if (at == ntab) used[ntab++] = t;   // <= 2 per component, <= 3 components
+      (kind ? ac_ix : dc_ix)[c] = (uint8_t)at;
+    }
+  }
+  // unstuffing only shrinks: the raw length bounds the packed one before anything is written
+  size_t n = 0;
+  for (size_t pos = hd.scan; pos < len; ++pos, ++n) {
+    if (data[pos] != 0xFF) continue;
+    if (pos + 1 < len && data[pos + 1] == 0) {
+      ++pos;
+      continue;
+    }
+    break;
+  }
+  const size_t padded = TMR_JPEG_SCAN_CAP(n);
+  if ((uint64_t)n * 8 > 0xffffffffu) return fail(kUnsupported, who, "scan longer than 2^32 bits");
+  if (bits_cap < padded) return fail(kArgs, who, "bit buffer too small");
+  if (tables_cap < (size_t)ntab * sizeof(tmr_jpeg_huff)) return fail(kArgs, who, "table buffer too small");
+
+  size_t o = 0;
+  for (size_t pos = hd.scan; o < n; ++pos) {
+    const uint8_t b = data[pos];   // pos < len: the count above walked the same bytes
+    bits[o++] = b;
+    if (b == 0xFF) ++pos;
+  }
+  memset(bits + n, 0, padded - n);
+
+  for (int t = 0; t < ntab; ++t) {
+    const Huff& h = *used[t];
+    tmr_jpeg_huff* d = tables + t;
+    memset(d, 0, sizeof(*d));
+    memcpy(d->lut, h.lut, sizeof(d->lut));
+    memcpy(d->fast, h.fast, sizeof(d->fast));
+    memcpy(d->maxcode, h.maxcode, sizeof(d->maxcode));
+    memcpy(d->valoff + 1, h.valoff + 1, 16 * sizeof(int32_t));
+    d->nsym = h.nsym;
+    memcpy(d->sym, h.sym, (size_t)h.nsym);
+  }
+
+  memset(desc, 0, sizeof(*desc));
+  desc->bits_off = bits_off;
+  desc->tables_off = tables_off;
+  desc->nbits = (uint32_t)(n * 8);
+  desc->bits_bytes = (uint32_t)padded;
+  desc->ntables = ntab;
+  desc->ncomp = info->ncomp;
+  desc->sampling = info->sampling;
+  desc->width = info->width;
+  desc->height = info->height;
+  int slots = 0;
+  for (int c = 0; c < hd.ncomp; ++c) {
+    desc->blocks_w[c] = info->blocks_w[c];
+    desc->blocks_h[c] = info->blocks_h[c];
+    desc->dc_table[c] = dc_ix[c];
+    desc->ac_table[c] = ac_ix[c];
+    for (int i = 0; i < hd.comp[c].h * hd.comp[c].v; ++i) desc->slot_comp[slots++] = (uint8_t)c;
+  }
+  desc->mcu_blocks = slots;   // 1, 3 or 6: classify() admits no other sampling
+  return kOk;
+}
+
 TMR_JPEG_API int tmr_jpeg_entropy_decode(const uint8_t* data, size_t len, tmr_jpeg_info* info,
                                          int16_t* coef, size_t coef_bytes) {
   static const char who[] = "tmr_jpeg_entropy_decode";

@@ -12,6 +12,15 @@ takes a batch's coefficients and quantisation tables to HBM, where ``tmr_jpeg_re
 Files outside the decoder's scope (progressive, 4:2:2, CMYK, PNG, ...: ``probe`` status 2) are
 decoded by ``pil_loader`` into their place in the batch, so a batch may mix both kinds and every
 frame still equals ``pil_loader``'s; a malformed file (status 1) raises.
+
+``DeviceJpegDecoder(entropy="device")`` (opt-in) moves the Huffman decode to the device as well:
+the host only parses the headers and packs each scan (``tmr_jpeg_scan_pack``: the entropy-coded
+bytes without their stuffing, the file's Huffman tables, a descriptor), the upload is the
+compressed scan, and ``tmr_jpeg_entropy_decode_device`` (jpeg_entropy.hip) writes the coefficients
+in device memory.  Files with a restart interval keep the host entropy pass inside the same batch.
+On this route ``result()`` reads one status word per frame back -- one small copy and one stream
+synchronise per batch, which the default route does not have; a frame with a non-zero status goes
+through the host entropy pass, which raises with its message.
 """
 import ctypes
 import io
@@ -53,8 +62,12 @@ def _align(n, a=16):
     return (n + a - 1) // a * a
 
 
+_DESC = ctypes.sizeof(_lib.JpegScanDesc)
+_TABLES = _lib.JPEG_MAX_TABLES * ctypes.sizeof(_lib.JpegHuff)
+
+
 class _Frame:
-    __slots__ = ("name", "data", "info", "rgb", "shape")
+    __slots__ = ("name", "data", "info", "rgb", "shape", "dev")
 
 
 class JpegJob:
@@ -80,17 +93,30 @@ class DeviceJpegDecoder:
     ``result()`` gives the same tensor: the host pass of batch i + 1 overlaps the step on batch i.
     Two batches may be in flight (two pinned buffers); a buffer is not written again before the
     copy and the kernels that read it have finished.  ``stats`` counts the frames decoded on the
-    device and those that fell back to PIL."""
+    device (``"device"``) and those that fell back to PIL (``"fallback"``), and of the former
+    those whose entropy decode ran on the device (``"entropy_device"``) and on the host
+    (``"entropy_host"``).  `entropy` = "host" (default) or "device" selects where the Huffman
+    decode runs (module docstring); `sub_bits` is the device decoder's subsequence length
+    (0: its default)."""
 
-    def __init__(self, workers=16, device="cuda"):
+    def __init__(self, workers=16, device="cuda", entropy="host", sub_bits=0):
+        if entropy not in ("host", "device"):
+            raise RuntimeError("DeviceJpegDecoder: entropy must be 'host' or 'device', got %r" % (entropy,))
+        sub_bits = int(sub_bits)
+        if sub_bits != 0 and (sub_bits < 64 or sub_bits % 32):
+            raise RuntimeError("DeviceJpegDecoder: sub_bits=%d is neither 0 nor a multiple of 32 >= 64"
+                               % sub_bits)
+        self.entropy, self.sub_bits = entropy, sub_bits
         self.workers = max(1, min(MAX_WORKERS, int(workers)))
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("DeviceJpegDecoder: a cuda device is required, got %s" % (self.device,))
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        self.stats = {"device": 0, "fallback": 0}
+        self.stats = {"device": 0, "fallback": 0, "entropy_device": 0, "entropy_host": 0}
         self.kernel_events = None    # a list: (start, end) events around each batch's kernels
+        self.entropy_events = []     # with kernel_events: (start, end) around the entropy kernels
+        self.entropy_rounds = []     # with kernel_events: re-decode rounds each frame needed
         self._pool = ThreadPoolExecutor(max_workers=self.workers)
         self._coord = ThreadPoolExecutor(max_workers=2)
         self._host = [None, None]    # pinned uint8 buffers
@@ -103,6 +129,7 @@ class DeviceJpegDecoder:
     def _load(item):
         fr = _Frame()
         fr.rgb = None
+        fr.dev = False
         if isinstance(item, (bytes, bytearray, memoryview)):
             fr.name, fr.data = "<bytes>", bytes(item)
         else:
@@ -122,6 +149,18 @@ class DeviceJpegDecoder:
                 fr.rgb = np.asarray(pil_loader(item))
             fr.info = None
             fr.shape = fr.rgb.shape[:2]
+        return fr
+
+    def _load_packable(self, item):
+        """_load, and whether the device entropy decoder takes the file (no restart interval)."""
+        fr = self._load(item)
+        if fr.info is not None:
+            rc = _lib.lib().tmr_jpeg_scan_pack(fr.data, len(fr.data), ctypes.byref(fr.info), None, 0, 0,
+                                               None, 0, 0, None)
+            if rc not in (0, _lib.JPEG_HOST_PASS):
+                raise RuntimeError("tmr_jpeg_scan_pack failed (%d): %s: %s"
+                                   % (rc, fr.name, _lib.lib().tmr_last_error().decode()))
+            fr.dev = rc == 0
         return fr
 
     def _buffer(self, slot, nbytes):
@@ -151,19 +190,33 @@ class DeviceJpegDecoder:
         return [y for f in futures if not f.cancelled() for y in f.result()]
 
     def _host_pass(self, slot, items):
-        frames = self._map(self._load, items)
+        frames = self._map(self._load if self.entropy == "host" else self._load_packable, items)
         h, w = frames[0].shape
         for fr in frames:
             if fr.shape != (h, w):
                 raise RuntimeError("DeviceJpegDecoder: %s is %s, expected %s" % (fr.name, fr.shape, (h, w)))
-        # one buffer: per sampling class its frames' coefficients, tables and output indices; then
-        # the fallback frames' RGB and indices
+        # one buffer: per sampling class its frames' coefficients (host entropy pass) or packed
+        # scans (device entropy pass: descriptors, Huffman tables, bits), quantisation tables and
+        # output indices; then the fallback frames' RGB and indices
         groups, at = [], 0
-        for s in sorted({fr.info.sampling for fr in frames if fr.info is not None}):
-            idx = [i for i, fr in enumerate(frames) if fr.info is not None and fr.info.sampling == s]
+        classes = sorted({(fr.info.sampling, not fr.dev) for fr in frames if fr.info is not None})
+        for s, on_host in classes:
+            idx = [i for i, fr in enumerate(frames)
+                   if fr.info is not None and fr.info.sampling == s and fr.dev != on_host]
             cb = int(frames[idx[0]].info.coef_bytes)
-            g = {"sampling": s, "idx": idx, "coef_bytes": cb, "coef": at}
-            at += cb * len(idx)
+            g = {"sampling": s, "idx": idx, "coef_bytes": cb, "entropy": "host" if on_host else "device"}
+            if on_host:
+                g["coef"] = at
+                at += cb * len(idx)
+            else:
+                g["desc"] = at
+                at += _DESC * len(idx)
+                g["tables"] = at
+                at += _TABLES * len(idx)
+                g["bits"] = []
+                for i in idx:
+                    g["bits"].append(at)
+                    at += _align(len(frames[i].data) + 8)
             g["qt"] = at
             at += 384 * len(idx)
             g["index"] = at
@@ -181,9 +234,21 @@ class DeviceJpegDecoder:
         fn = _lib.lib().tmr_jpeg_entropy_decode
         last_error = _lib.lib().tmr_last_error
 
+        pack = _lib.lib().tmr_jpeg_scan_pack
+
         def decode_one(job):
             g, j, i = job
             fr = frames[i]
+            if g["entropy"] == "device":
+                o, t = g["bits"][j], g["tables"] + j * _TABLES
+                rc = pack(fr.data, len(fr.data), ctypes.byref(fr.info), base + o,
+                          _align(len(fr.data) + 8), o, base + t, _TABLES, t, base + g["desc"] + j * _DESC)
+                if rc != 0:
+                    raise RuntimeError("tmr_jpeg_scan_pack failed (%d): %s: %s"
+                                       % (rc, fr.name, last_error().decode()))
+                q = g["qt"] + 384 * j
+                arr[q:q + 384] = np.frombuffer(fr.info.qt, dtype=np.uint8)
+                return
             rc = fn(fr.data, len(fr.data), ctypes.byref(fr.info), base + g["coef"] + j * g["coef_bytes"],
                     g["coef_bytes"])
             if rc != 0:
@@ -198,6 +263,11 @@ class DeviceJpegDecoder:
             arr[o:o + 4 * len(g["idx"])] = np.asarray(g["idx"], dtype=np.int32).view(np.uint8)
             jobs += [(g, j, i) for j, i in enumerate(g["idx"])]
         self._map(decode_one, jobs)
+        for g in groups:
+            if g["entropy"] == "device":   # word 4 of a descriptor: its bit count
+                d = arr[g["desc"]:g["desc"] + _DESC * len(g["idx"])].view(np.uint32)
+                g["max_bits"] = int(d.reshape(len(g["idx"]), _DESC // 4)[:, 4].max())
+        plan["frames"] = frames
         for j, i in enumerate(fb):
             o = plan["fb_rgb"] + j * h * w * 3
             arr[o:o + h * w * 3] = frames[i].rgb.reshape(-1)
@@ -216,11 +286,34 @@ class DeviceJpegDecoder:
             if self.kernel_events is not None:
                 timed = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 timed[0].record(torch.cuda.current_stream(self.device))
+            # the entropy kernels of every device group first, then the reconstruction
+            dev_groups = [g for g in plan["groups"] if g["entropy"] == "device"]
+            status = rounds = None
+            if dev_groups:
+                status = torch.empty(sum(len(g["idx"]) for g in dev_groups), dtype=torch.int32,
+                                     device=self.device)
+                rounds, so = [], 0
+                for g in dev_groups:
+                    f = len(g["idx"])
+                    g["coef_dev"] = torch.empty(f * g["coef_bytes"], dtype=torch.uint8, device=self.device)
+                    nb = query("tmr_jpeg_entropy_ws_bytes", f, g["max_bits"], self.sub_bits)
+                    ews = torch.empty(nb, dtype=torch.uint8, device=self.device)
+                    call("tmr_jpeg_entropy_decode_device", ctypes.c_void_p(base + g["desc"]), dbuf,
+                         ctypes.c_size_t(plan["bytes"]), f, h, w, g["sampling"], g["max_bits"],
+                         self.sub_bits, g["coef_dev"], status[so:so + f], ews, ctypes.c_size_t(nb),
+                         stream_ptr(self.device))
+                    rounds.append(ews[:4 * f].view(torch.int32))
+                    so += f
+                if self.kernel_events is not None:
+                    mid = torch.cuda.Event(enable_timing=True)
+                    mid.record(torch.cuda.current_stream(self.device))
+                    self.entropy_events.append((timed[0], mid))
             for g in plan["groups"]:
                 f = len(g["idx"])
                 nb = query("tmr_jpeg_ws_bytes", f, h, w, g["sampling"])
                 ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
-                call("tmr_jpeg_reconstruct", ctypes.c_void_p(base + g["coef"]),
+                coef = g.pop("coef_dev") if g["entropy"] == "device" else ctypes.c_void_p(base + g["coef"])
+                call("tmr_jpeg_reconstruct", coef,
                      ctypes.c_void_p(base + g["qt"]), f, h, w, g["sampling"], ws,
                      ctypes.c_size_t(nb), out, ctypes.c_void_p(base + g["index"]), n,
                      stream_ptr(self.device))
@@ -235,9 +328,36 @@ class DeviceJpegDecoder:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
             self._busy[slot] = ev
+            if dev_groups:
+                self._check_status(plan, dev_groups, status.cpu())   # the route's one synchronise
+                if self.kernel_events is not None:
+                    self.entropy_rounds += torch.cat(rounds).cpu().tolist()
+        on_device = sum(len(g["idx"]) for g in dev_groups)
+        self.stats["entropy_device"] += on_device
+        self.stats["entropy_host"] += n - len(fb) - on_device
         self.stats["device"] += n - len(fb)
         self.stats["fallback"] += len(fb)
         return out
+
+    @staticmethod
+    def _check_status(plan, dev_groups, status):
+        """A frame the device entropy decoder refused goes through the host's, which refuses the
+        same scans and says why; a scan only one of them refuses is a bug in one of them."""
+        if not bool(status.any()):
+            return
+        order = [i for g in dev_groups for i in g["idx"]]
+        for i, st in zip(order, status.tolist()):
+            if st == 0:
+                continue
+            fr = plan["frames"][i]
+            coef = np.empty(int(fr.info.coef_bytes) // 2, dtype=np.int16)
+            rc = _lib.lib().tmr_jpeg_entropy_decode(fr.data, len(fr.data), ctypes.byref(fr.info),
+                                                    coef.ctypes.data, coef.nbytes)
+            if rc != 0:
+                raise RuntimeError("tmr_jpeg_entropy_decode failed (%d): %s: %s"
+                                   % (rc, fr.name, _lib.lib().tmr_last_error().decode()))
+            raise RuntimeError("DeviceJpegDecoder: the device entropy decoder refused %s (status %d) "
+                               "but the host decoder accepts it: a bug, not a fallback" % (fr.name, st))
 
     def submit(self, items):
         items = list(items)
@@ -258,8 +378,9 @@ class DeviceJpegDecoder:
         return self.submit(items).result()
 
     def host_pass(self, items):
-        """The host pass alone, for measurement: files read and entropy-decoded into a pinned
-        buffer, nothing copied or launched.  Returns the bytes a batch uploads."""
+        """The host pass alone, for measurement: files read and entropy-decoded (or, with
+        entropy="device", packed) into a pinned buffer, nothing copied or launched.  Returns the
+        bytes a batch uploads."""
         job = self.submit(items)
         try:
             return job._future.result()["bytes"]
