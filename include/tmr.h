@@ -117,9 +117,10 @@ int tmr_conv2d_fwd(const tmr_conv_desc* d, const float* x, const float* w_krsc,
  * and the eval scripts): y = [relu](fmaf(conv(x, w_krsc), scale[k], shift[k]) + residual),
  * the same arithmetic as tmr_conv2d_fwd followed by tmr_bn_apply, without the y round trip.
  * scale/shift from tmr_bn_eval_params; residual (NHWC like y) may be NULL, must not alias y.
- * TMR_IO_Y_BF16 (with TMR_IO_X_BF16 | TMR_IO_W_BF16, TMR_MATH_BF16; no groups): y and residual
+ * TMR_IO_Y_BF16 (with TMR_IO_X_BF16 | TMR_IO_W_BF16, TMR_MATH_BF16): y and residual
  * are bf16 tensors -- the same arithmetic in fp32 on the widened residual, rounded once (RNE) at
- * the store; scale/shift stay fp32.  The bf16-activation inference contract. */
+ * the store; scale/shift stay fp32.  The bf16-activation inference contract.  A grouped conv
+ * (d->groups) runs one launch per group on channel slices; scale/shift/residual cover all k. */
 int tmr_conv2d_fwd_fused(const tmr_conv_desc* d, const float* x, const float* w_krsc,
                          const float* scale, const float* shift, const float* residual, float* y,
                          int relu, hipStream_t stream);
@@ -678,6 +679,24 @@ int tmr_splat_bwd_apply_bn(const float* dout, const void* y, const float* scale,
 /* tmr_avgpool2d_fwd on bf16 activations: fp32 sums of the bf16 inputs, the output rounded */
 int tmr_avgpool2d_fwd_a16(const void* x, void* y, int n, int h, int w, int c, int ho, int wo,
                           int k, int s, int p, int count_include_pad, hipStream_t stream);
+
+/* Split attention of the bf16-activation inference trunk (eval mode; resnest_inf.hip): x2 is the
+ * grouped fused unit's stored output relu(bn0(conv)), bf16 [n][h][w][2c].
+ *   attn_inf: att[n][r*c+j] = softmax over the radix pair of fc2(relu(bn1(fc1(gap) + b1)) + b2 in
+ *             one launch: gap [n][c] fp32, w1 [inter][c], b1 / scale1 / shift1 [inter] (the eval
+ *             BatchNorm from tmr_bn_eval_params), w2 [2c][inter], b2 [2c], all fp32;
+ *             c 64 / 128 / 256 / 512, inter = c/2; gap, w1, w2 16-B aligned.
+ *   combine_a16: out[n,ho,wo,j] = bf16(pool(att_0*x2[..,j] + att_1*x2[..,c+j])) computed in fp32 and
+ *             rounded once; pool_stride 0: no pool (ho = h), 1 or 2: AvgPool2d(3, pool_stride, 1)
+ *             with count_include_pad (ho = (h - 1)/pool_stride + 1).  With a pool the window sums
+ *             S_r of each radix half are taken first (att is constant over a frame) and weighted
+ *             once: (att_0*S_0 + att_1*S_1) / 9, the same value in exact arithmetic.  c a multiple of 8; x2, att
+ *             and out 16-B aligned. */
+int tmr_splat_attn_inf(const float* gap, const float* w1, const float* b1, const float* scale1,
+                       const float* shift1, const float* w2, const float* b2, float* att, int n,
+                       int c, int inter, hipStream_t stream);
+int tmr_splat_combine_a16(const void* x2, const float* att, void* out, int n, int h, int w, int c,
+                          int pool_stride, hipStream_t stream);
 
 /* ---------------- misc (head.hip) ------------------------------------------ */
 /* out[j] = beta*out[j] + sum_i x[i*ld + j]   (Linear bias grads) */

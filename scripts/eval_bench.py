@@ -9,7 +9,7 @@ Variants (run alternately in one process, `--rounds` rounds after one warm-up of
      timed on `--per-clip-batches` batches, its clips/s is that sample's)
   b  ``evaluate_split`` fp32
   c  ``evaluate_split`` bf16 math, fp32 activations
-  d  ``evaluate_split`` bf16 math, activations="bf16"
+  d  ``evaluate_split`` bf16 math, activations="bf16" (``--backbone resnest50``: "bf16-resnest")
 Timing: device events around each run, then a synchronise.  One JSON line per variant (median
 clips/s and encoded frames/s over the rounds, min / max as the spread) and a summary line with
 the ratios b/a (expectation: near T * N_clips / N_frames) and d/c.
@@ -45,7 +45,7 @@ def kernel_table(path, top):
             ns[fam] += float(r["TotalDurationNs"])
             calls[fam] += int(r["Calls"])
     tot = sum(ns.values())
-    print("%.1f ms of kernels in the profiled run" % (tot / 1e6))
+    print("%.1f ms of kernels in the profiled run, %d launches" % (tot / 1e6, sum(calls.values())))
     print()
     print("| kernel family | ms | share | launches |")
     print("|---|---:|---:|---:|")
@@ -57,6 +57,7 @@ def kernel_table(path, top):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--geometry", choices=sorted(GEOMETRY), default="A")
+    ap.add_argument("--backbone", choices=("resnet50", "resnest50"), default="resnet50")
     ap.add_argument("--videos", type=int, default=2)
     ap.add_argument("--frames", type=int, default=1500)
     ap.add_argument("--variants", default="a,b,c,d")
@@ -89,7 +90,8 @@ def main():
     for prec, users in (("fp32", {"a", "b"}), ("bf16", {"c", "d"})):
         if users & set(variants):
             torch.manual_seed(0)
-            models[prec] = tmrnet_amd.resnet_lstm(seq_len=T, precision=prec).to(dev).eval()
+            models[prec] = tmrnet_amd.resnet_lstm(seq_len=T, precision=prec,
+                                                  backbone=args.backbone).to(dev).eval()
 
     B = 64
     nb = max(1, min(args.per_clip_batches, len(valid) // B))
@@ -112,7 +114,7 @@ def main():
         return run
 
     runs = {"a": run_a, "b": split("fp32", "fp32"), "c": split("bf16", "fp32"),
-            "d": split("bf16", "bf16")}
+            "d": split("bf16", "bf16-resnest" if args.backbone == "resnest50" else "bf16")}
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -138,7 +140,8 @@ def main():
         clips, enc = count[v]
         cps = sorted(clips / s for s in secs[v])
         med[v] = float(np.median(cps))
-        lines.append({"geometry": args.geometry, "seq_len": T, "lfb_length": L, "variant": v,
+        lines.append({"geometry": args.geometry, "backbone": args.backbone, "seq_len": T,
+                      "lfb_length": L, "variant": v,
                       "name": NAMES[v], "clips": clips, "frames_encoded": enc,
                       "seconds": [round(s, 4) for s in secs[v]],
                       "clips_per_s": round(med[v], 1), "clips_per_s_min": round(cps[0], 1),
@@ -147,7 +150,7 @@ def main():
                       "spread_pct": round(100 * (cps[-1] - cps[0]) / med[v], 2),
                       "data": "synthetic (%d videos x %d uint8 250x250x3 frames in HBM, "
                               "random-init weights)" % (args.videos, args.frames)})
-    summary = {"geometry": args.geometry, "summary": True,
+    summary = {"geometry": args.geometry, "backbone": args.backbone, "summary": True,
                "expected_b_over_a": round(T * len(valid) / n_frames, 2),
                "b_over_a": round(med["b"] / med["a"], 2) if {"a", "b"} <= set(med) else "not measured",
                "d_over_c": round(med["d"] / med["c"], 3) if {"c", "d"} <= set(med) else "not measured"}

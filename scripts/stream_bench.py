@@ -1,7 +1,7 @@
 """Online recognition latency on one MI355X: what a live caller pays per pushed frame.
 
 Workload: `--streams` live videos of seeded uint8 250x250x3 frames (a pool resident in HBM, read
-round-robin), random-init fp32 ``resnet_lstm`` + ``resnet_lstm_LFB``.  Geometry A: T = 10, L = 40;
+round-robin), random-init ``resnet_lstm`` + ``resnet_lstm_LFB`` (`--backbone`, `--precision`).  Geometry A: T = 10, L = 40;
 B: T = 30, L = 300.  A tick is one new frame for every stream; the host synchronises after every
 tick, because an online caller reads each answer.
 
@@ -12,9 +12,11 @@ are full):
      (`--ticks-a` ticks a round: every frame is encoded T times by each model)
   b  ``OnlineRecognizer(window="steps")``
   c  ``OnlineRecognizer(window="kernel")``
+  d  ``OnlineRecognizer(window="kernel", activations=--activations)``: the bf16-activation trunk
+     of the backbone ("bf16" for resnet50, "bf16-resnest" for resnest50; needs --precision bf16)
 One JSON line per variant (median per-tick latency and ticks/s over the rounds' medians, spread =
 (max - min) / median), for (b) and (c) the phases of a tick (device events between the phases, one
-extra round), and a summary line with b/a and c/b.
+extra round), and a summary line with b/a, c/b and d/c.
 
 ``--kernel-table stats.csv`` instead prints the top-kernel table of a
 ``rocprofv3 --kernel-trace --stats`` run of one variant (``--variants c --rounds 1``).
@@ -32,7 +34,8 @@ sys.path.insert(0, os.path.join(ROOT, "scripts"))
 GEOMETRY = {"A": (10, 40), "B": (30, 300)}
 NAMES = {"a": "public modules on the last T frames, dense long_feature",
          "b": "OnlineRecognizer window=steps",
-         "c": "OnlineRecognizer window=kernel"}
+         "c": "OnlineRecognizer window=kernel",
+         "d": "OnlineRecognizer window=kernel, bf16 activations"}
 PHASES = ("input", "trunks", "projection", "recurrences", "head")
 
 
@@ -40,6 +43,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--geometry", choices=sorted(GEOMETRY), default="A")
     ap.add_argument("--streams", type=int, default=1)
+    ap.add_argument("--backbone", choices=("resnet50", "resnest50"), default="resnet50")
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--activations", default=None,
+                    help="variant d's activations (default: the backbone's bf16 value)")
     ap.add_argument("--variants", default="a,b,c")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--ticks", type=int, default=200)
@@ -67,8 +74,10 @@ def main():
     g = torch.Generator().manual_seed(1)
     pool = torch.randint(0, 256, (args.pool, S, 250, 250, 3), generator=g, dtype=torch.uint8).to(dev)
     torch.manual_seed(0)
-    model = tmrnet_amd.resnet_lstm(seq_len=T).to(dev).eval()
-    model_lfb = tmrnet_amd.resnet_lstm_LFB(seq_len=T).to(dev).eval()
+    kw = {"backbone": args.backbone, "precision": args.precision}
+    model = tmrnet_amd.resnet_lstm(seq_len=T, **kw).to(dev).eval()
+    model_lfb = tmrnet_amd.resnet_lstm_LFB(seq_len=T, **kw).to(dev).eval()
+    act_d = args.activations or ("bf16-resnest" if args.backbone == "resnest50" else "bf16")
 
     class ModulesLoop:
         """Variant a.  Bank rows are kept per stream in one device tensor that grows by a row a
@@ -97,8 +106,9 @@ def main():
             return preds
 
     class RecLoop:
-        def __init__(self, window):
-            self.rec = OnlineRecognizer(model, model_lfb, L, streams=S, window=window)
+        def __init__(self, window, activations="fp32"):
+            self.rec = OnlineRecognizer(model, model_lfb, L, streams=S, window=window,
+                                        activations=activations)
             self.n = 0
             for _ in range(T + L + 2):                                 # fill both rings
                 self.tick()
@@ -110,7 +120,8 @@ def main():
 
     loops = {}
     for v in variants:
-        loops[v] = ModulesLoop() if v == "a" else RecLoop("steps" if v == "b" else "kernel")
+        loops[v] = (ModulesLoop() if v == "a" else RecLoop("kernel", act_d) if v == "d"
+                    else RecLoop("steps" if v == "b" else "kernel"))
 
     def timed_round(v):
         """Per-tick host latency (push to answer on the host), seconds."""
@@ -162,7 +173,8 @@ def main():
     lines, mid = [], {}
     for v in variants:
         mid[v] = float(np.median(med[v]))
-        ln = {"geometry": args.geometry, "seq_len": T, "lfb_length": L, "streams": S,
+        ln = {"geometry": args.geometry, "backbone": args.backbone, "precision": args.precision,
+              "seq_len": T, "lfb_length": L, "streams": S,
               "variant": v, "name": NAMES[v], "ticks_per_round": ticks[v],
               "round_median_ms": [round(1e3 * m, 4) for m in med[v]],
               "round_p99_ms": [round(1e3 * m, 4) for m in p99[v]],
@@ -170,7 +182,7 @@ def main():
               "frames_per_s": round(S / mid[v], 1),
               "spread_pct": round(100 * (max(med[v]) - min(med[v])) / mid[v], 2),
               "data": "synthetic (%d uint8 250x250x3 frames per stream in HBM, random-init "
-                      "fp32 weights)" % args.pool}
+                      "weights)" % args.pool}
         if v != "a":
             ln["phase_ms"] = phase_round(v)
         lines.append(ln)
@@ -178,8 +190,10 @@ def main():
     def ratio(x, y):
         return round(mid[y] / mid[x], 3) if {x, y} <= set(mid) else "not measured"
 
-    lines.append({"geometry": args.geometry, "streams": S, "summary": True,
-                  "b_over_a_ticks_per_s": ratio("b", "a"), "c_over_b_ticks_per_s": ratio("c", "b")})
+    lines.append({"geometry": args.geometry, "backbone": args.backbone,
+                  "precision": args.precision, "streams": S, "summary": True,
+                  "b_over_a_ticks_per_s": ratio("b", "a"), "c_over_b_ticks_per_s": ratio("c", "b"),
+                  "d_over_c_ticks_per_s": ratio("d", "c")})
     for ln in lines:
         print(json.dumps(ln), flush=True)
     if args.out:

@@ -178,6 +178,8 @@ SIGNATURES = {
     "tmr_splat_bn0_coefs": [P, P, P, P, P, P, P, P, P, I, I, I, P],
     "tmr_splat_bwd_apply_bn": [P, P, P, P, P, P, P, P, P, I, I, I, I, P],
     "tmr_avgpool2d_fwd_a16": [P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "tmr_splat_attn_inf": [P, P, P, P, P, P, P, P, I, I, I, P],
+    "tmr_splat_combine_a16": [P, P, P, I, I, I, I, I, P],
     "tmr_fill_f32": [P, L, F, P],
     "tmr_seq_last": [P, P, I, I, I, P],
     "tmr_seq_last_bwd": [P, P, P, I, I, I, P],

@@ -133,7 +133,8 @@ class SplitEvaluator:
 
     model: a ``resnet_lstm`` (any backbone / TimeConv variant with activations="fp32"); bank: the
     split's ``LongFeatureBank``; weight: optional class weights of the criterion; activations:
-    "fp32", or "bf16" for the bf16-activation eval trunk (ResNet-50, precision "bf16").
+    "fp32", or "bf16" / "bf16-resnest" for the bf16-activation eval trunk of ResNet-50 /
+    ResNeSt-50 (precision "bf16"; lfb_build.check_activations).
     """
 
     def __init__(self, model, bank, weight=None, activations="fp32", frames_per_launch=640,

@@ -90,16 +90,31 @@ def _runs(idx):
 def check_activations(model, activations):
     """Validate the `activations` argument of the per-frame inference paths (LFBBuilder,
     evaluate.SplitEvaluator): "fp32", or "bf16" -- the bf16-activation eval trunk
-    (ResNet50Share.infer_act16), which exists for a ResNet-50 trunk of precision "bf16"."""
-    if activations not in ("fp32", "bf16"):
-        raise ValueError("activations must be 'fp32' or 'bf16', got %r" % (activations,))
+    (ResNet50Share.infer_act16), which exists for a ResNet-50 trunk of precision "bf16" -- or
+    "bf16-resnest", the bf16-activation eval trunk of ResNeSt-50 (ResNeSt50Share.infer_act16: a
+    contract of its own, split attention and two pools sit between the fused units), for a
+    ResNeSt-50 trunk of precision "bf16"."""
+    if activations not in ("fp32", "bf16", "bf16-resnest"):
+        raise ValueError("activations must be 'fp32', 'bf16' or 'bf16-resnest', got %r"
+                         % (activations,))
     if activations == "fp32":
         return
-    from . import trunk
+    from . import trunk, resnest
     share = model.share
+    if activations == "bf16-resnest":
+        if not isinstance(share, resnest.ResNeSt50Share):
+            raise ValueError("activations='bf16-resnest' exists for the ResNeSt-50 trunk only "
+                             "(got %s)" % type(share).__name__)
+        if share.precision != "bf16" or not trunk._full16(share.precision):
+            raise ValueError("activations='bf16-resnest' needs a ResNeSt-50 model of "
+                             "precision='bf16' with bf16-stored conv operands (got precision=%r)"
+                             % (share.precision,))
+        return
     if not isinstance(share, trunk.ResNet50Share):
+        hint = (" -- its bf16-activation trunk is activations='bf16-resnest'"
+                if isinstance(share, resnest.ResNeSt50Share) else "")
         raise ValueError("activations='bf16' exists for the ResNet-50 trunk only (%s evaluates "
-                         "with fp32 activations)" % type(share).__name__)
+                         "with fp32 activations%s)" % (type(share).__name__, hint))
     if share.precision != "bf16" or not trunk._full16(share.precision):
         raise ValueError("activations='bf16' needs a model of precision='bf16' with bf16-stored "
                          "conv operands (got precision=%r)" % (share.precision,))
@@ -115,7 +130,7 @@ def inference_mode(model, activations="fp32"):
     had = getattr(share, "infer_act16", None)
     model.eval()
     if had is not None:
-        share.infer_act16 = activations == "bf16"
+        share.infer_act16 = activations != "fp32"   # (check_activations matched it to the trunk)
     try:
         yield
     finally:
@@ -130,7 +145,8 @@ class LFBBuilder:
     frames: a uint8 (N_frames, Hin, Win, 3) tensor (device or host memory) holding every frame of
     the split in the reference's global frame order, or a callable ``loader(first, count)``
     returning such a tensor for frames [first, first + count) (e.g. a decoder).
-    activations: "fp32", or "bf16" for the bf16-activation eval trunk (check_activations).
+    activations: "fp32", or "bf16" / "bf16-resnest" for the bf16-activation eval trunk of
+    ResNet-50 / ResNeSt-50 (check_activations).
     """
 
     def __init__(self, model_lfb, frames_per_launch=640, clips_per_launch=8192,

@@ -237,11 +237,12 @@ def conv_fwd(x, w_krsc, stride, pad, bias=None, out=None, beta=0.0, c_real=None,
 
 
 def conv_fwd_fused(x, w_krsc, stride, pad, scale, shift, residual=None, relu=True, c_real=None,
-                   pad_w=None, math="fp32", y16=False):
+                   pad_w=None, math="fp32", y16=False, groups=1):
     """Inference conv + BN(running stats) [+ residual] [+ ReLU] in one launch:
     [relu](conv(x, w_krsc) * scale + shift + residual) -> (N,Ho,Wo,K).
     y16: bf16 activations (TMR_IO_Y_BF16) -- bf16 x, w and residual in, the result rounded once
-    (RNE) to a bf16 output."""
+    (RNE) to a bf16 output.  groups: a grouped conv (w_krsc (K, R, S, C/groups), torch's grouped
+    layout; one launch per group on channel slices); c_real is per group."""
     if y16:   # (checked before any library call)
         if x.dtype != BF16 or w_krsc.dtype != BF16 or math != "bf16":
             raise RuntimeError("conv_fwd_fused: y16 needs bf16 x and w and math='bf16'")
@@ -251,9 +252,9 @@ def conv_fwd_fused(x, w_krsc, stride, pad, scale, shift, residual=None, relu=Tru
     _req_op(x, "x"); _req_op(w_krsc, "w"); _req(scale, "scale"); _req(shift, "shift")
     n, h, w, c = x.shape
     k, r, s, c2 = w_krsc.shape
-    assert c == c2, (x.shape, w_krsc.shape)
+    assert c == c2 * groups, (x.shape, w_krsc.shape, groups)
     d = conv_desc(n, h, w, c, k, r, s, stride, pad, pad_w, math=math,
-                  io=_io(x, w_krsc) | (IO_Y if y16 else 0))
+                  io=_io(x, w_krsc) | (IO_Y if y16 else 0), groups=groups)
     out = _empty((n, d.ho, d.wo, k), x, dtype=BF16 if y16 else f32)
     if residual is not None:
         _req(residual, "residual", out.dtype)
@@ -261,10 +262,10 @@ def conv_fwd_fused(x, w_krsc, stride, pad, scale, shift, residual=None, relu=Tru
             raise RuntimeError("conv_fwd_fused: residual %s != output %s"
                                % (tuple(residual.shape), tuple(out.shape)))
     ysz = n * d.ho * d.wo * k
-    with _prof("conv_fwd" + _SUFFIX[math], 2.0 * ysz * r * s * (c_real or c),
+    with _prof("conv_fwd" + _SUFFIX[math], 2.0 * ysz * r * s * (c_real or c2),
                (n, h, w, c, k, r, stride),
                (2 if y16 else 4)
-               * (n * h * w * c + k * r * s * c + ysz * (2 if residual is not None else 1))):
+               * (n * h * w * c + k * r * s * c2 + ysz * (2 if residual is not None else 1))):
         call("tmr_conv2d_fwd_fused", ctypes.byref(d), x, w_krsc, scale, shift, residual, out,
              int(relu), stream_ptr())
     return out
@@ -1401,6 +1402,47 @@ def splat_bwd_apply_bn(dout, y2, scale, shift, mean, att, dgap, coef):
     call("tmr_splat_bwd_apply_bn", dout, y2, scale, shift, mean, att, dgap, coef, dy, n, h * w,
          c2 // 2, _act16(y2), stream_ptr())
     return dy
+
+
+def splat_attn_inf(gap, w1, b1, scale1, shift1, w2, b2):
+    """Eval-mode attention MLP of SplAtConv2d in one launch (tmr_splat_attn_inf): gap (n, C) ->
+    att (n, 2C) = r-softmax(fc2(relu(bn1(fc1(gap) + b1))) + b2); scale1 / shift1 from bn_eval_params."""
+    n, C = gap.shape
+    inter = w1.shape[0]
+    if tuple(w1.shape) != (inter, C) or tuple(w2.shape) != (2 * C, inter):
+        raise RuntimeError("splat_attn_inf: w1 %s / w2 %s vs gap %s"
+                           % (tuple(w1.shape), tuple(w2.shape), tuple(gap.shape)))
+    for t, name, numel in ((b1, "b1", inter), (scale1, "scale1", inter), (shift1, "shift1", inter),
+                           (b2, "b2", 2 * C)):
+        if _req(t, name).numel() != numel:
+            raise RuntimeError("splat_attn_inf: %s has %d elements, expected %d"
+                               % (name, t.numel(), numel))
+    att = _empty((n, 2 * C), gap)
+    call("tmr_splat_attn_inf", _req(gap, "gap"), _req(w1, "w1"), b1, scale1, shift1, _req(w2, "w2"),
+         b2, att, n, C, inter, stream_ptr())
+    return att
+
+
+def splat_combine_a16(x2, att, pool=0, out=None):
+    """Weighted sum of the radix halves of the stored bf16 x2 (n, h, w, 2C) in fp32, with pool = 1
+    or 2 the AvgPool2d(3, pool, 1) over it in the same pass, rounded once -> bf16 (n, ho, wo, C)
+    (tmr_splat_combine_a16)."""
+    _req(x2, "x2", BF16)
+    n, h, w, c2 = x2.shape
+    C = c2 // 2
+    if pool not in (0, 1, 2):
+        raise RuntimeError("splat_combine_a16: pool stride %r (0 = none, 1 or 2)" % (pool,))
+    if tuple(att.shape) != (n, c2):
+        raise RuntimeError("splat_combine_a16: att %s vs x2 %s" % (tuple(att.shape), tuple(x2.shape)))
+    ho, wo = ((h - 1) // pool + 1, (w - 1) // pool + 1) if pool else (h, w)
+    if out is None:
+        out = _empty((n, ho, wo, C), x2, dtype=BF16)
+    elif tuple(out.shape) != (n, ho, wo, C):
+        raise RuntimeError("splat_combine_a16: out %s, expected %s"
+                           % (tuple(out.shape), (n, ho, wo, C)))
+    call("tmr_splat_combine_a16", x2, _req(att, "att"), _req(out, "out", BF16), n, h, w, C, pool,
+         stream_ptr())
+    return out
 
 
 def avgpool2d_fwd(x, k, s, p, count_include_pad, ceil_mode):

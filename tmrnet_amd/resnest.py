@@ -20,7 +20,9 @@ autograd node, `ResNeStTrunkFn`, built on trunk.py's conv-unit engine (the ResNe
   * residual / branch gradients accumulate in the dgrad epilogues (beta = 1), each dgrad fused with
     the backward of the BatchNorm that produced its input (conv2's with bn1, conv1's with the
     previous block's bn3), so no PyTorch kernel sums gradients.
-Eval mode (and inference without grad) keeps the per-stage nodes below.
+Eval mode (and inference without grad) keeps the per-stage nodes below; with precision "bf16" and
+the opt-in switch ``infer_act16`` it runs the bf16-activation inference trunk instead
+(_features_infer16).
 
 Per-stage nodes (eval / legacy path), activations NHWC:
   * ConvBNActFn   -- (grouped) implicit-GEMM conv + BatchNorm (batch stats) + residual + ReLU
@@ -452,6 +454,59 @@ def _splat_bwd(sp, spl, r2, dout, grads):
     return ops.splat_bwd_apply_bn(dout, y2, r2["scale"], r2["shift"], r2["mean"], att, dgap, coef)
 
 
+def _features_infer16(share, x4):
+    """The bf16-activation inference trunk (eval mode, precision "bf16",
+    share.infer_act16): every stored activation bf16, rounded once where it is stored.  Fused conv
+    units (trunk._conv_bn y16: BN, residual and ReLU in the conv epilogue), the radix-2 grouped
+    3x3 as one grouped unit, the GAP in fp32, the attention MLP in one launch, and the weighted
+    sum -- with the avd pool of strided blocks -- in one pass over the stored x2."""
+    from .trunk import _conv_bn
+    mt = share.precision
+    ident = share.__dict__.setdefault("_infer16_identity", {})
+
+    def identity(k, like):   # BatchNorm y*1 + 0 of k channels (exact on stored values >= 0);
+        key = (k, like.device)   # constants, kept on the share: filled once per device
+        if key not in ident:
+            ident[key] = (torch.ones(k, dtype=torch.float32, device=like.device),
+                          torch.zeros(k, dtype=torch.float32, device=like.device))
+        return ident[key]
+
+    def unit(x, conv, bn, stride, pad, relu, residual=None, groups=1):
+        return _conv_bn(x, conv, bn, stride, pad, relu, False, residual=residual, math=mt,
+                        groups=groups, y16=True)
+
+    c = share.conv1
+    z = unit(ops.nhwc4_to_bf16x8(x4), c[0], c[1], 2, 1, True)
+    z = unit(z, c[3], c[4], 1, 1, True)
+    z = unit(z, c[6], share.bn1, 1, 1, True)
+    h, _ = ops.maxpool_fwd_bn(z, *identity(z.shape[-1], z))   # z >= 0: exact
+    for layer in (share.layer1, share.layer2, share.layer3, share.layer4):
+        for blk in layer:
+            sp = blk.conv2
+            z1 = unit(h, blk.conv1, blk.bn1, 1, 0, True)
+            x2 = unit(z1, sp.conv, sp.bn0, sp.stride, 1, True, groups=sp.radix)
+            C = x2.shape[-1] // 2
+            inter = sp.fc1.weight.shape[0]
+            # x2 is the stored relu(bn0(.)): the train step's GAP with an identity bn0 reads it
+            # unchanged (fmaf(y, 1, 0) = y, max(y, 0) = y for y >= 0, rounding a bf16 value = it)
+            gap = ops.splat_gap_bn(x2, *identity(2 * C, x2))
+            sc1, sh1 = ops.bn_eval_params(sp.bn1.weight.detach(), sp.bn1.bias.detach(),
+                                          sp.bn1.running_mean, sp.bn1.running_var, sp.bn1.eps)
+            att = ops.splat_attn_inf(gap, sp.fc1.weight.detach().reshape(inter, C),
+                                     sp.fc1.bias.detach(), sc1, sh1,
+                                     sp.fc2.weight.detach().reshape(2 * C, inter),
+                                     sp.fc2.bias.detach())
+            out = ops.splat_combine_a16(x2, att, pool=blk.avd_stride if blk.avd else 0)
+            idn = h
+            if blk.downsample is not None:
+                pool, dconv, dbn = blk.downsample[0], blk.downsample[1], blk.downsample[2]
+                if pool.kernel_size != 1:
+                    idn = ops.avgpool2d_fwd(h, pool.kernel_size, pool.stride, 0, False, True)
+                idn = unit(idn, dconv, dbn, 1, 0, False)
+            h = unit(out, blk.conv3, blk.bn3, 1, 0, True, residual=idn)
+    return ops.avgpool_fwd(h)
+
+
 def _trunk_node_ok(share):
     """The whole-trunk node covers fp32 math and bf16 math under the bf16-activation contract."""
     from .trunk import _act16
@@ -557,6 +612,9 @@ class ResNeSt50Share(nn.Sequential):
     def __init__(self, precision="fp32"):
         super().__init__()
         self.precision = precision
+        # eval mode, precision "bf16": store activations as bf16 (_features_infer16; opt-in, the
+        # inference paths set it through lfb_build.inference_mode)
+        self.infer_act16 = False
         self.add_module("conv1", nn.Sequential(
             nn.Conv2d(3, 32, 3, 2, 1, bias=False), nn.BatchNorm2d(32), nn.ReLU(inplace=True),
             nn.Conv2d(32, 32, 3, 1, 1, bias=False), nn.BatchNorm2d(32), nn.ReLU(inplace=True),
@@ -586,6 +644,11 @@ class ResNeSt50Share(nn.Sequential):
             # grad mode is off inside autograd.Function.forward: decide here whether to save
             keep = torch.is_grad_enabled() and any(p.requires_grad for p in params)
             return ResNeStTrunkFn.apply(x4, self, keep, *params)
+        from .trunk import _infer16
+        if _infer16(self):
+            with torch.no_grad(), ops.layout_session(self, ("resnest50", "infer16",
+                                                            self.precision)):
+                return _features_infer16(self, x4)
         c, mt = self.conv1, self.precision
         h = conv_bn_act(x4, c[0], c[1], 2, 1, True, c_real=3, math=mt)
         h = conv_bn_act(h, c[3], c[4], 1, 1, True, math=mt)

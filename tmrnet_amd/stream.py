@@ -133,7 +133,7 @@ class OnlineRecognizer:
 
     model: a ``resnet_lstm`` (any backbone, with or without TimeConv); model_lfb: the
     ``resnet_lstm_LFB`` that fills the bank; both of the same ``seq_len`` and on the same device.
-    activations: "fp32" or "bf16" (lfb_build.check_activations, for both models).
+    activations: "fp32", "bf16" or "bf16-resnest" (lfb_build.check_activations, for both models).
     window: "kernel" (tmr_lstm_window_fwd), "steps" (gather + LFBBuilder.recur) or "auto".
     gate_cap / bank_cap: ring sizes per stream (default T and lfb_length + 1).
     cut_margin: cut each frame's black margin before the resize, as the reference prepares its

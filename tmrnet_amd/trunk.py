@@ -213,8 +213,9 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
     inside the maxpool); ``branch`` = such a deferred (y, scale, shift) used as the residual.
     ``dual`` (block outputs under
     _full16): returns (z fp32, z bf16 copy).  ``groups``: a grouped conv
-    (train mode; ResNeSt's radix-2 3x3, tmr_conv_desc.groups).  ``y16`` (eval mode, bf16
-    activations: ResNet50Share.infer_act16): x and residual bf16, z rounded once to bf16."""
+    (train mode, or eval mode with y16; ResNeSt's radix-2 3x3, tmr_conv_desc.groups).  ``y16``
+    (eval mode, bf16 activations: the shares' infer_act16): x and residual bf16, z rounded once
+    to bf16."""
     w = conv.weight
     k, c, r, s = w.shape
     cs = x.shape[3]
@@ -223,8 +224,9 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
         wk = w.detach().contiguous().view(k, 1, 1, c)   # OIHW == KRSC for 1x1
     else:   # (grouped: torch's (K, C/G, R, S) -> stacked per-group KRSC blocks (K, R, S, C/G))
         wk = ops.weight_to_krsc(w.detach().contiguous(), cpad=cs // groups, bf16=s16)
-    if groups > 1 and not training:
-        raise RuntimeError("grouped convs run in the train-mode trunk only")
+    if groups > 1 and not training and not y16:
+        raise RuntimeError("grouped convs run in the train-mode trunk and the bf16-activation "
+                           "inference trunk (y16) only")
     if training:
         # batch statistics come out of the conv epilogue (no separate pass over y)
         y, stats, nparts = ops.conv_fwd_bnstats(x, wk, stride, pad, c_real=c * groups, math=math,
@@ -243,7 +245,7 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
         scale, shift = ops.bn_eval_params(bn.weight.detach(), bn.bias.detach(), bn.running_mean,
                                           bn.running_var, bn.eps)
         return ops.conv_fwd_fused(x, wk, stride, pad, scale, shift, residual, relu, c_real=c,
-                                  math=math, y16=y16)
+                                  math=math, y16=y16, groups=groups)
     # fp32 block outputs on the LDS-DMA path also record their ReLU mask as bits: the dgrad that
     # produces their gradient reads 1 bit instead of z's 4 bytes (mask 3)
     zbits = None
