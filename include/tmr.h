@@ -641,7 +641,9 @@ int tmr_center_cols(const float* x, int rows, int cols, float* center, float* xc
                     hipStream_t stream);
 /* y[i] += alpha * x[i] */
 int tmr_axpy(int n, float alpha, const float* x, float* y, hipStream_t stream);
-/* AvgPool2d(k, s, p) NHWC; divisor k*k (count_include_pad) or the number of valid cells */
+/* AvgPool2d(k, s, p) NHWC; divisor: count_include_pad -- the cells of the window inside the padded
+ * extent [-p, h+p) x [-p, w+p), nn.AvgPool2d's rule (k*k unless a ceil_mode output's window hangs
+ * over it); else the number of valid input cells */
 int tmr_avgpool2d_fwd(const float* x, float* y, int n, int h, int w, int c, int ho, int wo, int k,
                       int s, int p, int count_include_pad, hipStream_t stream);
 int tmr_avgpool2d_bwd(const float* dy, float* dx, int n, int h, int w, int c, int ho, int wo, int k,

@@ -27,7 +27,9 @@ pytestmark = pytest.mark.gpu
                                   (2, 56, 56, 256, 2, 2, 0, False, True),
                                   (3, 7, 7, 32, 3, 1, 1, True, False),
                                   (2, 15, 13, 8, 2, 2, 0, False, True),    # ragged + ceil
-                                  (2, 15, 13, 8, 3, 2, 1, True, False)])
+                                  (2, 15, 13, 8, 3, 2, 1, True, False),
+                                  (2, 5, 5, 8, 2, 2, 0, True, True),       # include-pad windows that
+                                  (2, 6, 6, 8, 3, 2, 1, True, True)])      # hang over the padded extent
 def test_avgpool2d(dev, case):
     n, h, w, c, k, s, p, incl, ceil = case
     g = torch.Generator().manual_seed(sum(case[:4]))
@@ -49,7 +51,9 @@ def test_avgpool2d(dev, case):
                                   (3, 7, 7, 32, 3, 1, 1, True, False),
                                   (2, 15, 13, 8, 2, 2, 0, False, True),
                                   (2, 15, 13, 8, 3, 2, 1, True, False),
-                                  (2, 14, 14, 512, 3, 2, 1, True, False)])
+                                  (2, 14, 14, 512, 3, 2, 1, True, False),
+                                  (2, 5, 5, 8, 2, 2, 0, True, True),
+                                  (2, 6, 6, 8, 3, 2, 1, True, True)])
 def test_avgpool2d_a16_exact(dev, case):
     """The bf16 AvgPool2d forward (ResNeSt's avd / avg_down under bf16 activations; the 3x3/2 and
     2x2/2 windows take the compile-time-window kernel, the rest the generic one) against the
@@ -72,7 +76,9 @@ def test_avgpool2d_a16_exact(dev, case):
             v = xf[:, iy.clamp(0, h - 1), ix.clamp(0, w - 1), :]
             acc = acc + torch.where(ok.view(1, ho, wo, 1), v, torch.zeros_like(v))
             cnt = cnt + ok.view(1, ho, wo, 1).float()
-    inv = (1.0 / torch.full_like(cnt, float(k * k))) if incl else 1.0 / cnt.clamp(min=1)
+    # count_include_pad: the window clipped to the padded extent [-p, h + p) x [-p, w + p)
+    full = ((oy + k).clamp(max=h + p) - oy) * ((ox + k).clamp(max=w + p) - ox)
+    inv = 1.0 / full.float().view(1, ho, wo, 1) if incl else 1.0 / cnt.clamp(min=1)
     ref = (acc * inv).to(torch.bfloat16)
     assert y.shape == ref.shape
     assert torch.equal(y.float(), ref.float())

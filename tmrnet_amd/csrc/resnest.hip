@@ -152,7 +152,14 @@ __global__ __launch_bounds__(NT) void splat_bwd_apply_k(const float* __restrict_
   }
 }
 
-// general AvgPool2d on NHWC: divisor = k*k (count_include_pad) or #valid input cells
+// cells of output o's window [o*s - p, o*s - p + k) inside the padded extent [-p, size + p): k
+// unless ceil_mode lets the last window hang over size + p (the count_include_pad divisor, per axis)
+__device__ __forceinline__ int padded_span(int o, int k, int s, int p, int size) {
+  return min(o * s - p + k, size + p) - (o * s - p);
+}
+
+// general AvgPool2d on NHWC: divisor = the window clipped to the padded extent (count_include_pad:
+// k*k unless ceil_mode lets the last window hang over h + p) or #valid input cells
 // IT: index type (uint32_t when the element groups fit 31 bits: 64-bit divisions cost
 // ~100 instructions per element; tmr_avgpool2d_* pick it)
 template <typename IT>
@@ -180,7 +187,8 @@ __global__ __launch_bounds__(NT) void avgpool2d_fwd_k(const float* __restrict__ 
         ++cnt;
       }
     }
-    const float inv = 1.0f / (float)(incl ? k * k : (cnt > 0 ? cnt : 1));
+    const int full = padded_span(oy, k, s, p, h) * padded_span(ox, k, s, p, w);
+    const float inv = 1.0f / (float)(incl ? full : (cnt > 0 ? cnt : 1));
     acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
     reinterpret_cast<float4*>(y)[i] = acc;
   }
@@ -208,7 +216,7 @@ __global__ __launch_bounds__(NT) void avgpool2d_bwd_k(const float* __restrict__ 
       if (iy < oy * s - p || iy > oy * s - p + k - 1) continue;
       for (int ox = ox0; ox <= ox1; ++ox) {
         if (ix < ox * s - p || ix > ox * s - p + k - 1) continue;
-        int cnt = k * k;
+        int cnt = padded_span(oy, k, s, p, h) * padded_span(ox, k, s, p, w);
         if (!incl) {
           const int y0 = max(0, oy * s - p), y1 = min(h, oy * s - p + k);
           const int x0 = max(0, ox * s - p), x1 = min(w, ox * s - p + k);
@@ -250,7 +258,7 @@ __global__ __launch_bounds__(NT) void avgpool2d_bwd_fd_k(const float* __restrict
       if (iy < oy * s - p || iy > oy * s - p + k - 1) continue;
       for (int ox = ox0; ox <= ox1; ++ox) {
         if (ix < ox * s - p || ix > ox * s - p + k - 1) continue;
-        int cnt = k * k;
+        int cnt = padded_span(oy, k, s, p, (int)h) * padded_span(ox, k, s, p, (int)w);
         if (!incl) {
           const int y0 = max(0, oy * s - p), y1 = min((int)h, oy * s - p + k);
           const int x0 = max(0, ox * s - p), x1 = min((int)w, ox * s - p + k);
@@ -673,7 +681,8 @@ __global__ __launch_bounds__(NT) void avgpool2d_fwd_a16_k(const __bf16* __restri
         ++cnt;
       }
     }
-    const float inv = 1.0f / (float)(incl ? k * k : (cnt > 0 ? cnt : 1));
+    const int full = padded_span(oy, k, s, p, h) * padded_span(ox, k, s, p, w);
+    const float inv = 1.0f / (float)(incl ? full : (cnt > 0 ? cnt : 1));
     acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
     Act<__bf16>::st(y, i, acc);
   }
@@ -712,7 +721,8 @@ __global__ __launch_bounds__(NT) void avgpool2d_fwd_a16_fd_k(const __bf16* __res
         ++cnt;
       }
     }
-    const float inv = 1.0f / (float)(incl ? k * k : (cnt > 0 ? cnt : 1));
+    const int full = padded_span(oy, k, s, p, h) * padded_span(ox, k, s, p, w);
+    const float inv = 1.0f / (float)(incl ? full : (cnt > 0 ? cnt : 1));
     acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
     Act<__bf16>::st(y, i, acc);
   }
