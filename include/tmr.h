@@ -381,6 +381,34 @@ int tmr_maxpool2d_fwd_bn_x(const float* x, const float* scale, const float* shif
                            uint8_t* argmax, int n, int h, int w, int c, int ho, int wo, int out_bf16,
                            hipStream_t stream);
 
+/* fp32-forward / bf16-backward train step (ResNet50Share precision "bf16-bwd"): the forward is the
+ * fp32 step's bit for bit; every trunk conv's dgrad and wgrad run in bf16 math on a bf16 dy, a
+ * bf16 copy of the conv's input and the bf16 CRSK weights (oracle.emulate_bf16_convs(ops=("dy",
+ * "bx", "bw"))).  These passes write the bf16 copies beside the fp32 values they already wrote:
+ *  - tmr_bn_apply_bits_dual / tmr_bn_apply2_bits_dual: z and bits of tmr_bn_apply_bits /
+ *    tmr_bn_apply2_bits, plus z16 = RNE(z).  c a multiple of 8, y / residual (yr) / z / z16 16-B
+ *    aligned (else refused).
+ *  - tmr_maxpool2d_fwd_bn_dual: y and argmax of tmr_maxpool2d_fwd_bn, plus y16 = RNE(y).  c = 8
+ *    times a power of two, x / y / y16 16-B and argmax 8-B aligned (else refused).
+ *  - tmr_bn_bwd_parts_ds_d16: tmr_bn_bwd_parts_ds with fp32 g, y, y_ds in and bf16 dy, dy_ds out:
+ *    the RNE of the fp32 call's dy's, the four BN gradients its bits.  Both dy's required.
+ * (The non-residual units take tmr_bn_apply_dual.) */
+int tmr_bn_apply_bits_dual(const float* y, const float* scale, const float* shift,
+                           const float* residual, float* z, void* z16, uint32_t* bits, int rows,
+                           int c, hipStream_t stream);
+int tmr_bn_apply2_bits_dual(const float* y, const float* scale, const float* shift,
+                            const float* yr, const float* rscale, const float* rshift, float* z,
+                            void* z16, uint32_t* bits, int rows, int c, hipStream_t stream);
+int tmr_maxpool2d_fwd_bn_dual(const float* x, const float* scale, const float* shift, float* y,
+                              void* y16, uint8_t* argmax, int n, int h, int w, int c, int ho,
+                              int wo, hipStream_t stream);
+int tmr_bn_bwd_parts_ds_d16(const float* g, const float* y, const void* parts, int nparts,
+                            const float* save_mean, const float* save_invstd, const float* gamma,
+                            void* dy, float* dgamma, float* dbeta, const float* y_ds,
+                            const float* save_mean_ds, const float* save_invstd_ds,
+                            const float* gamma_ds, void* dy_ds, float* dgamma_ds, float* dbeta_ds,
+                            int rows, int c, void* ws, size_t ws_bytes, hipStream_t stream);
+
 /* bf16-activation contract of the bf16 train step (TMR_MATH_BF16; tests/test_bf16_gpu.py,
  * oracle.emulate_bf16_convs(activations=True)): every conv output y is stored rounded to bf16
  * (TMR_IO_Y_BF16; BN statistics of the rounded values), every BatchNorm(+residual)(+ReLU) output

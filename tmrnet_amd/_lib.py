@@ -121,6 +121,10 @@ SIGNATURES = {
     "tmr_bn_bwd_parts_ds_ws_bytes": [I, I, I],
     "tmr_bn_bwd_parts_ds_coef_offset": [I, I, I, I],
     "tmr_bn_bwd_parts_ds": [P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P, SZ, P],
+    "tmr_bn_apply_bits_dual": [P, P, P, P, P, P, P, I, I, P],
+    "tmr_bn_apply2_bits_dual": [P, P, P, P, P, P, P, P, P, I, I, P],
+    "tmr_maxpool2d_fwd_bn_dual": [P, P, P, P, P, P, I, I, I, I, I, I, P],
+    "tmr_bn_bwd_parts_ds_d16": [P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, P, SZ, P],
     "tmr_bn_bwd_maxpool_a16": [P, P, I, I, I, I, I, P, P, P, P, P, P, P, P, P, I, P, SZ, P],
     "tmr_maxpool2d_fwd_bn_a16": [P, P, P, P, P, I, I, I, I, I, I, P],
     "tmr_avgpool_fwd_a16": [P, P, I, I, I, P],

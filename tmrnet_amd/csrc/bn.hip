@@ -1061,7 +1061,9 @@ __global__ __launch_bounds__(NT) void stem_bwd_apply8q(const PoolGeo pg, int h, 
 #ifndef TMR_BN_BITS8
 #define TMR_BN_BITS8 1   // 0: the 4-wide form only (A/B build)
 #endif
-template <bool RES>
+// DUAL (the fp32-forward / bf16-backward step, tmr_bn_apply_bits_dual): also a bf16 (RNE) copy z16
+// of z, one 16-B store per group -- the block output as the next convs' wgrad operand.
+template <bool RES, bool DUAL = false>
 __global__ __launch_bounds__(NT) void bn_apply_bits8_k(const float* __restrict__ y,
                                                        const float* __restrict__ scale,
                                                        const float* __restrict__ shift,
@@ -1070,7 +1072,8 @@ __global__ __launch_bounds__(NT) void bn_apply_bits8_k(const float* __restrict__
                                                        const float* __restrict__ rscale,
                                                        const float* __restrict__ rshift,
                                                        float* __restrict__ z,
-                                                       uint32_t* __restrict__ bits, long n8, int c8) {
+                                                       uint32_t* __restrict__ bits, long n8, int c8,
+                                                       __bf16* __restrict__ z16 = nullptr) {
   const int lane = threadIdx.x & 63;
   const long stride = (long)gridDim.x * NT;
   // one group: z of elements 8i .. 8i + 7 and their mask byte
@@ -1104,6 +1107,7 @@ __global__ __launch_bounds__(NT) void bn_apply_bits8_k(const float* __restrict__
       b |= (uint32_t)(v[e] > 0.f) << e;
     }
     st8(z, i, v);
+    if (DUAL) st8(z16, i, v);
     return b;
   };
   // the word of 4 lanes' bytes (group indices 4k .. 4k + 3: base is a multiple of 64)
@@ -1130,6 +1134,51 @@ __global__ __launch_bounds__(NT) void bn_apply_bits8_k(const float* __restrict__
     const uint32_t bj = oj ? apply(j, yb, rb) : 0u;
     put(bi, i, oi);
     put(bj, j, oj);
+  }
+}
+
+// bn_apply_k's DUAL form (z fp32 and its bf16 copy z16), 8 elements per thread and two groups in
+// flight: 16-B pieces of y, the residual, z and z16 (the 4-wide form stores z16 in 8-B pieces).
+// Same fmaf / add / max sequence per element: identical z and z16.
+template <bool RES, bool RELU>
+__global__ __launch_bounds__(NT) void bn_apply_dual8_k(const float* __restrict__ y,
+                                                       const float* __restrict__ scale,
+                                                       const float* __restrict__ shift,
+                                                       const float* __restrict__ res,
+                                                       float* __restrict__ z,
+                                                       __bf16* __restrict__ z16, long n8, int c8) {
+  const long stride = (long)gridDim.x * NT;
+  auto apply = [&](long i, const float (&yv)[8], const float (&rv)[8]) {
+    const int cc = chan_of(i, c8) * 8;
+    float v[8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const float4 sc = *reinterpret_cast<const float4*>(scale + cc + 4 * h);
+      const float4 sf = *reinterpret_cast<const float4*>(shift + cc + 4 * h);
+      const float s4[4] = {sc.x, sc.y, sc.z, sc.w}, f4[4] = {sf.x, sf.y, sf.z, sf.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float t = fmaf(yv[4 * h + e], s4[e], f4[e]);
+        if (RES) t += rv[4 * h + e];
+        if (RELU) t = fmaxf(t, 0.f);
+        v[4 * h + e] = t;
+      }
+    }
+    st8(z, i, v);
+    st8(z16, i, v);
+  };
+  for (long i = blockIdx.x * (long)NT + threadIdx.x; i < n8; i += 2 * stride) {
+    const long j = i + stride;
+    const bool hj = j < n8;
+    float ya[8], ra[8], yb[8], rb[8];
+    ld8(y, i, ya);
+    if (RES) ld8(res, i, ra);
+    if (hj) {
+      ld8(y, j, yb);
+      if (RES) ld8(res, j, rb);
+    }
+    apply(i, ya, ra);
+    if (hj) apply(j, yb, rb);
   }
 }
 
@@ -1327,6 +1376,54 @@ TMR_API int tmr_bn_apply2_bits(const float* y, const float* scale, const float* 
   return 0;
 }
 
+// The block outputs of the fp32-forward / bf16-backward step: tmr_bn_apply_bits / _apply2_bits
+// plus the bf16 copy of z in the same pass (the 8-wide kernel only: channel counts and alignments
+// it does not serve are refused -- the step's block outputs are all 8-channel multiples).
+static int bits_dual_ok(const char* name, int c, const void* y, const void* r, const void* z,
+                        const void* z16) {
+  TMR_CHECK_ARG(c % 8 == 0 && c >= 8, "%s: channels %d must be a multiple of 8", name, c);
+  TMR_CHECK_ARG((((uintptr_t)y | (uintptr_t)r | (uintptr_t)z | (uintptr_t)z16) & 15) == 0,
+                "%s: y / residual / z / z16 must be 16-B aligned", name);
+  return 0;
+}
+
+TMR_API int tmr_bn_apply_bits_dual(const float* y, const float* scale, const float* shift,
+                                   const float* residual, float* z, void* z16, uint32_t* bits,
+                                   int rows, int c, hipStream_t stream) {
+  TMR_CHECK_ARG(y && scale && shift && z && z16 && bits, "tmr_bn_apply_bits_dual: null operand");
+  TMR_CHECK_ARG(rows >= 0, "tmr_bn_apply_bits_dual: negative rows");
+  if (const int rc = bits_dual_ok("tmr_bn_apply_bits_dual", c, y, residual, z, z16)) return rc;
+  const long n8 = (long)rows * c / 8;
+  if (n8 == 0) return 0;
+  if (residual)
+    hipLaunchKernelGGL((bn_apply_bits8_k<true, true>), dim3(ew_blocks(n8)), dim3(NT), 0, stream, y,
+                       scale, shift, residual, nullptr, nullptr, nullptr, z, bits, n8, c / 8,
+                       (__bf16*)z16);
+  else
+    hipLaunchKernelGGL((bn_apply_bits8_k<false, true>), dim3(ew_blocks(n8)), dim3(NT), 0, stream, y,
+                       scale, shift, nullptr, nullptr, nullptr, nullptr, z, bits, n8, c / 8,
+                       (__bf16*)z16);
+  TMR_CHECK_LAUNCH("bn_apply_bits_dual");
+  return 0;
+}
+
+TMR_API int tmr_bn_apply2_bits_dual(const float* y, const float* scale, const float* shift,
+                                    const float* yr, const float* rscale, const float* rshift,
+                                    float* z, void* z16, uint32_t* bits, int rows, int c,
+                                    hipStream_t stream) {
+  TMR_CHECK_ARG(y && scale && shift && yr && rscale && rshift && z && z16 && bits,
+                "tmr_bn_apply2_bits_dual: null operand");
+  TMR_CHECK_ARG(rows >= 0, "tmr_bn_apply2_bits_dual: negative rows");
+  TMR_CHECK_ARG(yr != z, "tmr_bn_apply2_bits_dual: the branch input must not alias z");
+  if (const int rc = bits_dual_ok("tmr_bn_apply2_bits_dual", c, y, yr, z, z16)) return rc;
+  const long n8 = (long)rows * c / 8;
+  if (n8 == 0) return 0;
+  hipLaunchKernelGGL((bn_apply_bits8_k<false, true>), dim3(ew_blocks(n8)), dim3(NT), 0, stream, y,
+                     scale, shift, nullptr, yr, rscale, rshift, z, bits, n8, c / 8, (__bf16*)z16);
+  TMR_CHECK_LAUNCH("bn_apply2_bits_dual");
+  return 0;
+}
+
 TMR_API int tmr_bn_apply_bits_a16(const void* y, const float* scale, const float* shift,
                                   const void* residual, void* z, uint32_t* bits, int rows, int c,
                                   hipStream_t stream) {
@@ -1369,6 +1466,20 @@ TMR_API int tmr_bn_apply_dual(const float* y, const float* scale, const float* s
   const long n4 = (long)rows * c / 4;
   const int nb = ew_blocks(n4), c4 = c / 4;
   __bf16* h = (__bf16*)z16;
+  // 8 channels per thread (16-B pieces of z16 too), else the 4-wide form: the same values
+  if (c % 8 == 0 && (((uintptr_t)y | (uintptr_t)residual | (uintptr_t)z | (uintptr_t)z16) & 15) == 0) {
+    const long n8 = n4 / 2;
+    const int nb8 = ew_blocks(n8), c8 = c / 8;
+    if (residual) {
+      if (relu) hipLaunchKernelGGL((bn_apply_dual8_k<true, true>), dim3(nb8), dim3(NT), 0, stream, y, scale, shift, residual, z, h, n8, c8);
+      else hipLaunchKernelGGL((bn_apply_dual8_k<true, false>), dim3(nb8), dim3(NT), 0, stream, y, scale, shift, residual, z, h, n8, c8);
+    } else {
+      if (relu) hipLaunchKernelGGL((bn_apply_dual8_k<false, true>), dim3(nb8), dim3(NT), 0, stream, y, scale, shift, residual, z, h, n8, c8);
+      else hipLaunchKernelGGL((bn_apply_dual8_k<false, false>), dim3(nb8), dim3(NT), 0, stream, y, scale, shift, residual, z, h, n8, c8);
+    }
+    TMR_CHECK_LAUNCH("bn_apply_dual");
+    return 0;
+  }
   if (residual) {
     if (relu) hipLaunchKernelGGL((bn_apply_k<true, true, float, true>), dim3(nb), dim3(NT), 0, stream, y, scale, shift, residual, z, n4, c4, h);
     else hipLaunchKernelGGL((bn_apply_k<true, false, float, true>), dim3(nb), dim3(NT), 0, stream, y, scale, shift, residual, z, n4, c4, h);
@@ -1562,7 +1673,12 @@ TMR_API int tmr_bn_bwd_parts_x(const float* g, const float* y, const void* parts
   // wgrad, tmr_conv2d_wgrad_bnbwd, reads them at ws + tmr_bn_parts_coef_offset(nparts, c)
   if (!dyv) return 0;
   const long n4 = (long)rows * c / 4;
-  if (out_bf16)
+  // (a bf16 dy of fp32 g and y -- every non-downsample unit of the fp32-forward / bf16-backward
+  // step -- takes the 8-wide form too: the 4-wide one stores dy in 8-B pieces)
+  if (out_bf16 && c % 8 == 0 && (((uintptr_t)g | (uintptr_t)y | (uintptr_t)dyv) & 15) == 0)
+    hipLaunchKernelGGL((bn_bwd_apply8_k<float, float, __bf16>), dim3(ew_blocks(n4 / 2)), dim3(NT), 0,
+                       stream, g, y, coef, (__bf16*)dyv, n4 / 2, c / 8);
+  else if (out_bf16)
     hipLaunchKernelGGL((bn_bwd_apply<0, false, __bf16, float>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, g,
                        y, nullptr, nullptr, nullptr, coef, (__bf16*)dyv, nullptr, n4, c / 4);
   else if (c % 8 == 0 && (((uintptr_t)g | (uintptr_t)y | (uintptr_t)dyv) & 15) == 0)
@@ -1794,12 +1910,14 @@ TMR_API int tmr_bn_bwd_parts_g16(const void* g, const void* y, const void* parts
 // sequence of bn_bwd_apply / bn_bwd_apply8_a16 -- instead of two apply passes that each read g.
 // T: float (fp32 step: g, y, dy fp32) or __bf16 (bf16-activation step under R16: all bf16, dy
 // rounded RNE).  8 elements per thread, 16-B accesses.
-template <typename T>
+// TD: the dy's element type (fp32 g / y / y_ds in, bf16 dy's out: the fp32-forward / bf16-backward
+// step, tmr_bn_bwd_parts_ds_d16 -- the RNE of the fp32 form's values).
+template <typename T, typename TD = T>
 __global__ __launch_bounds__(NT) void bn_bwd_apply_ds8(const T* __restrict__ g, const T* __restrict__ y,
                                                        const T* __restrict__ yd,
                                                        const float* __restrict__ coef,
                                                        const float* __restrict__ coefd,
-                                                       T* __restrict__ dy, T* __restrict__ dyd, long n8,
+                                                       TD* __restrict__ dy, TD* __restrict__ dyd, long n8,
                                                        int c8) {
   const int c = c8 * 8;
   auto apply = [&](long i, const float (&gv)[8], const float (&yv)[8], const float (&dv)[8]) {
@@ -1854,12 +1972,14 @@ TMR_API size_t tmr_bn_bwd_parts_ds_coef_offset(int nparts, int rows, int c, int 
   return (tmr_bn_parts_ws_bytes(nparts, c) + 255) / 256 * 256 + (size_t)p.nrb * c * 2 * sizeof(double);
 }
 
-TMR_API int tmr_bn_bwd_parts_ds(const void* g, const void* y, const void* parts, int nparts,
+// out16 (bf16 == 0 only): fp32 operands in, both dy's stored bf16 (tmr_bn_bwd_parts_ds_d16)
+static int bn_bwd_parts_ds_impl(const void* g, const void* y, const void* parts, int nparts,
                                 const float* mean, const float* invstd, const float* gamma,
                                 void* dy, float* dgamma, float* dbeta, const void* yd,
                                 const float* mean_d, const float* invstd_d, const float* gamma_d,
                                 void* dyd, float* dgamma_d, float* dbeta_d, int rows, int c,
-                                int bf16, void* ws, size_t ws_bytes, hipStream_t stream) {
+                                int bf16, int out16, void* ws, size_t ws_bytes,
+                                hipStream_t stream) {
   TMR_CHECK_ARG(c % 8 == 0 && c >= 8 && rows > 0 && nparts > 0,
                 "tmr_bn_bwd_parts_ds: bad shape rows=%d c=%d parts=%d", rows, c, nparts);
   TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd_parts_ds: unsupported channel count %d", c);
@@ -1921,12 +2041,40 @@ TMR_API int tmr_bn_bwd_parts_ds(const void* g, const void* y, const void* parts,
     hipLaunchKernelGGL(bn_bwd_apply_ds8<__bf16>, dim3(ew_blocks(n8 / 2)), dim3(NT), 0, stream,
                        (const __bf16*)g, (const __bf16*)y, (const __bf16*)yd, coef, coefd,
                        (__bf16*)dy, (__bf16*)dyd, n8, c / 8);
+  else if (out16)
+    hipLaunchKernelGGL((bn_bwd_apply_ds8<float, __bf16>), dim3(ew_blocks(n8 / 2)), dim3(NT), 0, stream,
+                       (const float*)g, (const float*)y, (const float*)yd, coef, coefd,
+                       (__bf16*)dy, (__bf16*)dyd, n8, c / 8);
   else
     hipLaunchKernelGGL(bn_bwd_apply_ds8<float>, dim3(ew_blocks(n8 / 2)), dim3(NT), 0, stream,
                        (const float*)g, (const float*)y, (const float*)yd, coef, coefd, (float*)dy,
                        (float*)dyd, n8, c / 8);
   TMR_CHECK_LAUNCH("bn_bwd_apply_ds");
   return 0;
+}
+
+TMR_API int tmr_bn_bwd_parts_ds(const void* g, const void* y, const void* parts, int nparts,
+                                const float* mean, const float* invstd, const float* gamma,
+                                void* dy, float* dgamma, float* dbeta, const void* yd,
+                                const float* mean_d, const float* invstd_d, const float* gamma_d,
+                                void* dyd, float* dgamma_d, float* dbeta_d, int rows, int c,
+                                int bf16, void* ws, size_t ws_bytes, hipStream_t stream) {
+  return bn_bwd_parts_ds_impl(g, y, parts, nparts, mean, invstd, gamma, dy, dgamma, dbeta, yd,
+                              mean_d, invstd_d, gamma_d, dyd, dgamma_d, dbeta_d, rows, c, bf16, 0,
+                              ws, ws_bytes, stream);
+}
+
+TMR_API int tmr_bn_bwd_parts_ds_d16(const float* g, const float* y, const void* parts, int nparts,
+                                    const float* mean, const float* invstd, const float* gamma,
+                                    void* dy, float* dgamma, float* dbeta, const float* yd,
+                                    const float* mean_d, const float* invstd_d,
+                                    const float* gamma_d, void* dyd, float* dgamma_d,
+                                    float* dbeta_d, int rows, int c, void* ws, size_t ws_bytes,
+                                    hipStream_t stream) {
+  TMR_CHECK_ARG(dy && dyd, "tmr_bn_bwd_parts_ds_d16: null dy / dy_ds (both outputs are written)");
+  return bn_bwd_parts_ds_impl(g, y, parts, nparts, mean, invstd, gamma, dy, dgamma, dbeta, yd,
+                              mean_d, invstd_d, gamma_d, dyd, dgamma_d, dbeta_d, rows, c, 0, 1, ws,
+                              ws_bytes, stream);
 }
 
 TMR_API int tmr_bn_bwd_maxpool_a16(const float* dyp, const uint8_t* argmax, int n, int h, int w,

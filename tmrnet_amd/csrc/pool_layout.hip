@@ -112,12 +112,15 @@ __device__ __forceinline__ float raw_val(const Raw8& r, int e) {
 // stores of y and 8-B argmax stores.  Same BN+ReLU arithmetic and scan order as maxpool_fwd_k:
 // identical outputs.  total = n*ho*wo*c/8 < 2^31, c / 8 a power of two (lc8 = log2), both
 // checked on the host.
-template <typename TX, typename TY>
+// DUAL (TY float; tmr_maxpool2d_fwd_bn_dual): the pooled output also as a bf16 (RNE) copy y16, one
+// 16-B store -- layer1.0's forwards read y, their bf16-math wgrads y16.
+template <typename TX, typename TY, bool DUAL = false>
 __global__ __launch_bounds__(NT) void maxpool_fwd_bn8(const TX* __restrict__ x, TY* __restrict__ y,
                                                      uint2* __restrict__ am, int total, int h,
                                                      int w, int lc8, FastDiv dHWo, FastDiv dWo,
                                                      const float* __restrict__ scale,
-                                                     const float* __restrict__ shift) {
+                                                     const float* __restrict__ shift,
+                                                     __bf16* __restrict__ y16 = nullptr) {
   const int c8 = 1 << lc8;
   for (int i = blockIdx.x * NT + threadIdx.x; i < total; i += gridDim.x * NT) {
     const int cq = i & (c8 - 1);
@@ -164,6 +167,16 @@ __global__ __launch_bounds__(NT) void maxpool_fwd_bn8(const TX* __restrict__ x, 
       const long j = 2 * (long)i;
       reinterpret_cast<float4*>(y)[j] = make_float4(best[0], best[1], best[2], best[3]);
       reinterpret_cast<float4*>(y)[j + 1] = make_float4(best[4], best[5], best[6], best[7]);
+      if constexpr (DUAL) {
+        typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+        uint32_t ow[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bf16x2_t pr = {(__bf16)best[2 * e], (__bf16)best[2 * e + 1]};
+          ow[e] = __builtin_bit_cast(uint32_t, pr);
+        }
+        reinterpret_cast<uint4*>(y16)[i] = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+      }
     } else {
       typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
       uint32_t ow[4];
@@ -351,6 +364,29 @@ TMR_API int tmr_maxpool2d_fwd_bn_x(const float* x, const float* scale, const flo
     hipLaunchKernelGGL((maxpool_fwd_k<true>), dim3(ew_blocks(total)), dim3(NT), 0, stream, x,
                        (float*)y, (uchar4*)argmax, n, h, w, c / 4, ho, wo, scale, shift);
   TMR_CHECK_LAUNCH("maxpool_fwd_bn");
+  return 0;
+}
+
+// The stem of the fp32-forward / bf16-backward step: tmr_maxpool2d_fwd_bn's y and argmax plus the
+// bf16 copy of y in the same pass.  The 8-channel kernel only: what it does not serve is refused.
+TMR_API int tmr_maxpool2d_fwd_bn_dual(const float* x, const float* scale, const float* shift,
+                                      float* y, void* y16, uint8_t* argmax, int n, int h, int w,
+                                      int c, int ho, int wo, hipStream_t stream) {
+  TMR_CHECK_ARG(x && scale && shift && y && y16 && argmax, "tmr_maxpool2d_fwd_bn_dual: null operand");
+  TMR_CHECK_ARG(n > 0 && h > 0 && w > 0 && ho == (h + 2 - 3) / 2 + 1 && wo == (w + 2 - 3) / 2 + 1,
+                "tmr_maxpool2d_fwd_bn_dual: pooled %dx%d is not MaxPool2d(3,2,1) of %dx%d", ho, wo, h, w);
+  const int c8 = c / 8;
+  TMR_CHECK_ARG(c >= 8 && c % 8 == 0 && (c8 & (c8 - 1)) == 0 && (long)n * h * w * c8 < 0x7fffffffL,
+                "tmr_maxpool2d_fwd_bn_dual: channels %d must be 8 times a power of two, "
+                "n*h*w*c/8 < 2^31", c);
+  TMR_CHECK_ARG((((uintptr_t)x | (uintptr_t)y | (uintptr_t)y16) & 15) == 0 && ((uintptr_t)argmax & 7) == 0,
+                "tmr_maxpool2d_fwd_bn_dual: x / y / y16 must be 16-B aligned, argmax 8-B aligned");
+  const int t8 = (int)((long)n * ho * wo * c8);
+  hipLaunchKernelGGL((maxpool_fwd_bn8<float, float, true>), dim3(ew_blocks(t8)), dim3(NT), 0, stream,
+                     x, y, (uint2*)argmax, t8, h, w, __builtin_ctz(c8),
+                     make_fastdiv((uint32_t)(ho * wo)), make_fastdiv((uint32_t)wo), scale, shift,
+                     (__bf16*)y16);
+  TMR_CHECK_LAUNCH("maxpool_fwd_bn_dual");
   return 0;
 }
 

@@ -105,11 +105,14 @@ def _frames_to_features(share, x):
 
 
 def _make_trunk(backbone, precision):
-    if precision not in ("fp32", "bf16"):
-        raise ValueError("precision must be 'fp32' or 'bf16', got %r" % precision)
+    if precision not in ("fp32", "bf16", "bf16-bwd"):
+        raise ValueError("precision must be 'fp32', 'bf16' or 'bf16-bwd', got %r" % precision)
     if backbone == "resnet50":
         return ResNet50Share(precision=precision)
     if backbone == "resnest50":
+        if precision == "bf16-bwd":
+            raise ValueError("precision='bf16-bwd' (fp32 forward, bf16 backward convs) exists for "
+                             "the resnet50 backbone only; resnest50 takes 'fp32' or 'bf16'")
         from .resnest import ResNeSt50Share
         return ResNeSt50Share(precision=precision)
     raise ValueError("unknown backbone %r" % backbone)
@@ -118,7 +121,9 @@ def _make_trunk(backbone, precision):
 class resnet_lstm(nn.Module):  # noqa: N801  (reference class name)
     """precision='bf16' runs the trunk convolutions (fwd, dgrad, wgrad) with bf16 operands on
     the bf16 matrix cores, fp32 accumulation, fp32 activations/BN/master weights (the bf16
-    configs C4/C5); everything else stays fp32."""
+    configs C4/C5); everything else stays fp32.  precision='bf16-bwd' (resnet50 only) keeps the
+    'fp32' forward bit for bit -- train and eval -- and runs only the trunk convs' dgrad and wgrad
+    on bf16 operands (trunk.ResNet50Share)."""
 
     def __init__(self, seq_len=10, num_classes=7, time_conv=False, backbone="resnet50",
                  precision="fp32"):

@@ -414,13 +414,33 @@ def bn_bwd_maxpool(dyp, am, y, scale, shift, mean, inv, gamma, bf16=False):
 
 
 def bn_bwd_parts_ds(g, y, parts, nparts, mean, inv, gamma, yd, mean_d, inv_d, gamma_d,
-                    fold3=False, foldd=False):
+                    fold3=False, foldd=False, dy16=False):
     """BN backward of a downsample block's bn3 (from the fused dgrad's partials, g already
     masked) and of its downsample BN (a reduction pass over g and y_ds), with one apply pass that
     reads g once -> (dy, dgamma, dbeta, dy_ds, dgamma_ds, dbeta_ds); the values of bn_bwd_parts +
     bn_bwd.  g, y, y_ds all fp32 or all bf16 (the dy's take their dtype).
     fold3 / foldd (fp32): that unit's wgrad produces its dy itself (conv_wgrad_bnbwd) -- the same
-    entry point with that output NULL; the result is then bn_bwd_parts_ds_coef's."""
+    entry point with that output NULL; the result is then bn_bwd_parts_ds_coef's.
+    dy16 (fp32 g, y, y_ds): both dy's stored bf16, the RNE of the fp32 call's
+    (tmr_bn_bwd_parts_ds_d16: the fp32-forward / bf16-backward step)."""
+    if dy16:
+        if fold3 or foldd:
+            raise RuntimeError("bn_bwd_parts_ds: bf16 dy's (dy16) take no wgrad fold")
+        c = y.shape[-1]
+        rows = y.numel() // c
+        if not (g.dtype == y.dtype == yd.dtype == f32 and g.shape == y.shape == yd.shape
+                and g.is_contiguous() and y.is_contiguous() and yd.is_contiguous()):
+            raise RuntimeError("bn_bwd_parts_ds: dy16 takes contiguous fp32 g, y and y_ds of one "
+                               "shape")
+        nb = query("tmr_bn_bwd_parts_ds_ws_bytes", int(nparts), rows, c)
+        ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=y.device)
+        dy, dyd = torch.empty_like(y, dtype=BF16), torch.empty_like(yd, dtype=BF16)
+        dg, db = _empty((c,), mean), _empty((c,), mean)
+        dgd, dbd = _empty((c,), mean), _empty((c,), mean)
+        call("tmr_bn_bwd_parts_ds_d16", g, y, parts, int(nparts), mean, inv, gamma, dy, dg, db, yd,
+             mean_d, inv_d, gamma_d, dyd, dgd, dbd, rows, c, ws, ctypes.c_size_t(ws.numel() * 8),
+             stream_ptr())
+        return dy, dg, db, dyd, dgd, dbd
     if fold3 or foldd:
         return bn_bwd_parts_ds_coef(g, y, parts, nparts, mean, inv, gamma, yd, mean_d, inv_d,
                                     gamma_d, apply3=not fold3, applyd=not foldd)
@@ -928,6 +948,40 @@ def bn_apply2_bits(y, scale, shift, yr, rscale, rshift):
     return z, bits
 
 
+def bn_apply_bits_dual(y, scale, shift, residual=None):
+    """bn_apply_bits (fp32) writing the bf16 (RNE) copy of z in the same pass -> (z, bits, z16):
+    a block output of the fp32-forward / bf16-backward step (tmr_bn_apply_bits_dual)."""
+    _req(y, "y")
+    if residual is not None:
+        _req(residual, "residual")
+        if residual.shape != y.shape:
+            raise RuntimeError("bn_apply_bits_dual: residual shape %s != %s"
+                               % (tuple(residual.shape), tuple(y.shape)))
+    c = y.shape[-1]
+    z = torch.empty_like(y)
+    z16 = torch.empty_like(y, dtype=BF16)
+    bits = relu_bits_empty(y)
+    call("tmr_bn_apply_bits_dual", y, scale, shift, residual, z, z16, bits, y.numel() // c, c,
+         stream_ptr())
+    return z, bits, z16
+
+
+def bn_apply2_bits_dual(y, scale, shift, yr, rscale, rshift):
+    """bn_apply2_bits (fp32) writing the bf16 (RNE) copy of z in the same pass -> (z, bits, z16)
+    (tmr_bn_apply2_bits_dual)."""
+    _req(y, "y"); _req(yr, "yr")
+    if yr.shape != y.shape:
+        raise RuntimeError("bn_apply2_bits_dual: branch shape %s != %s"
+                           % (tuple(yr.shape), tuple(y.shape)))
+    c = y.shape[-1]
+    z = torch.empty_like(y)
+    z16 = torch.empty_like(y, dtype=BF16)
+    bits = relu_bits_empty(y)
+    call("tmr_bn_apply2_bits_dual", y, scale, shift, yr, rscale, rshift, z, z16, bits,
+         y.numel() // c, c, stream_ptr())
+    return z, bits, z16
+
+
 def bn_apply_dual(y, scale, shift, residual=None, relu=True):
     """bn_apply writing z in fp32 and a bf16 (RNE) copy in one pass -> (z, z16): a block output
     is the next block's identity residual (fp32) and its bf16-math convs' operand (bf16)."""
@@ -1022,6 +1076,20 @@ def maxpool_fwd_bn(x, scale, shift, bf16=False):
     call("tmr_maxpool2d_fwd_bn_x", x, scale, shift, y, am, n, h, w, c, ho, wo, int(bf16),
          stream_ptr())
     return y, am
+
+
+def maxpool_fwd_bn_dual(x, scale, shift):
+    """maxpool_fwd_bn (fp32) writing the bf16 (RNE) copy of the pooled output in the same pass
+    -> (y, y16, argmax) (tmr_maxpool2d_fwd_bn_dual)."""
+    _req(x, "x")
+    n, h, w, c = x.shape
+    ho = (h + 2 - 3) // 2 + 1
+    wo = (w + 2 - 3) // 2 + 1
+    am = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=x.device)
+    y = _empty((n, ho, wo, c), x)
+    y16 = _empty((n, ho, wo, c), x, dtype=BF16)
+    call("tmr_maxpool2d_fwd_bn_dual", x, scale, shift, y, y16, am, n, h, w, c, ho, wo, stream_ptr())
+    return y, y16, am
 
 
 def maxpool_bwd(dy, am, in_hw):

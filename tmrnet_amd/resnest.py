@@ -611,6 +611,9 @@ class GlobalAvgPool2d(nn.Module):
 class ResNeSt50Share(nn.Sequential):
     def __init__(self, precision="fp32"):
         super().__init__()
+        if precision == "bf16-bwd":   # (trunk.BWD16: the split-attention backward has no such form)
+            raise ValueError("precision='bf16-bwd' (fp32 forward, bf16 backward convs) exists for "
+                             "the resnet50 backbone only; resnest50 takes 'fp32' or 'bf16'")
         self.precision = precision
         # eval mode, precision "bf16": store activations as bf16 (_features_infer16; opt-in, the
         # inference paths set it through lfb_build.inference_mode)

@@ -154,6 +154,7 @@ WGRAD_BNBWD_DS_MIN = 8_000_000
 def _ds_fold(g, r3, rd):
     """Which of a downsample block's two units (bn3's conv3, the downsample conv) let their wgrad
     produce dy (WGRAD_BNBWD_DS) -> (fold3, foldd)."""
+    # (fp32 math only: the BWD16 step's g is fp32 but its wgrads run in bf16 math on a bf16 dy)
     if not (WGRAD_BNBWD and WGRAD_BNBWD_DS and g.dtype == torch.float32
             and r3["math"] == "fp32" and rd["math"] == "fp32" and g.numel() >= WGRAD_BNBWD_DS_MIN):
         return False, False
@@ -167,11 +168,19 @@ def _ds_fold(g, r3, rd):
 
 def _ds_dual(g, r3, rd):
     """DS_DUAL applies: g, y3 and y_ds of one dtype, which is also the dy dtype the separate passes
-    would write (fp32 y under bf16 storage writes bf16 dy: not this path), 8-channel multiples."""
+    would write (fp32 y under bf16 storage writes bf16 dy: not this path -- except the BWD16
+    step's records, whose fp32 g / y / y_ds in, bf16 dy's out form is _ds_dy16), 8-channel
+    multiples."""
     y = r3["y"]
     return (DS_DUAL and g.is_contiguous() and g.dtype == y.dtype == rd["y"].dtype
             and y.shape == rd["y"].shape and y.shape[-1] % 8 == 0
-            and not (_store16(r3["math"]) and y.dtype == torch.float32))
+            and (_ds_dy16(r3, rd) or not (_store16(r3["math"]) and y.dtype == torch.float32)))
+
+
+def _ds_dy16(r3, rd):
+    """The BWD16 step's downsample blocks: fp32 g, y3, y_ds, both dy's stored bf16
+    (ops.bn_bwd_parts_ds(dy16=True))."""
+    return bool(r3.get("dy16") and rd.get("dy16") and r3["y"].dtype == torch.float32)
 
 # the fp32 block outputs' ReLU masks as bits for the mask-3 dgrads (round 2: 3622 -> 3634 frames/s,
 # profiles/r2/bench_r3a/).  The bf16-activation step re-reads its 2-byte z instead: bits measured no
@@ -193,6 +202,27 @@ def _full16(math):
     return _store16(math) and FULL16
 
 
+# precision "bf16-bwd" (ResNet-50 only): the forward is the fp32 step's, bit for bit -- the same
+# conv kernels on fp32 operands, BN statistics, z, running statistics; eval mode is the fp32 path.
+# Every trunk conv's dgrad and wgrad run with math "bf16" and fp32 accumulation on three roundings
+# (the oracle's emulate_bf16_convs(ops=("dy", "bx", "bw"))): dy stored bf16 (RNE) by the BN
+# backward that produces it; the wgrad reads a bf16 copy of the conv's input, written in the
+# forward by the pass that writes the fp32 value (bn_apply_dual, bn_apply(2)_bits_dual,
+# maxpool_fwd_bn_dual; the stem's NHWC4 fp32 input is rounded on load by the direct bf16 wgrad);
+# the dgrad reads the bf16 CRSK weight copy.  BN statistics, y, the ReLU masks (bits for block
+# outputs, y*scale+shift otherwise), the masked gradients g, the residual-stream gradient, dW and
+# the BN gradients stay fp32: no G16 / R16 here.  Saved per unit: the bf16 input copy, fp32 y, bits
+# for block outputs, statistics and coefficients -- the fp32 z of a non-residual unit is dropped
+# once the next conv's forward has read it, and the block outputs' fp32 z after the forward (mask 3
+# reads the bits; the last block's stays for the first BN backward's mask).
+BWD16 = "bf16-bwd"
+
+
+def _fwd_math(precision):
+    """The math mode of the forward convs (ops.MATH) under ResNet50Share.precision."""
+    return "fp32" if precision == BWD16 else precision
+
+
 def _act16(math):
     return _full16(math) and ACT16
 
@@ -200,12 +230,13 @@ def _act16(math):
 def _infer16(share):
     """The bf16-activation inference trunk applies: eval mode, every conv operand bf16 in HBM
     (_full16) and the opt-in switch ResNet50Share.infer_act16."""
-    return bool(not share.training and _full16(share.precision)
+    return bool(not share.training and share.precision != BWD16 and _full16(share.precision)
                 and getattr(share, "infer_act16", False))
 
 
 def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None, math="fp32",
-             defer=False, branch=None, nbt=None, dual=False, groups=1, y16=False):
+             defer=False, branch=None, nbt=None, dual=False, groups=1, y16=False, bwd16=False,
+             x16=None):
     """conv (NHWC implicit GEMM) -> BN -> (+residual) -> (ReLU); returns z.
 
     Train mode only: ``defer`` returns (y, scale, shift) instead of applying the BN -- the
@@ -215,9 +246,15 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
     _full16): returns (z fp32, z bf16 copy).  ``groups``: a grouped conv
     (train mode, or eval mode with y16; ResNeSt's radix-2 3x3, tmr_conv_desc.groups).  ``y16``
     (eval mode, bf16 activations: the shares' infer_act16): x and residual bf16, z rounded once
-    to bf16."""
+    to bf16.  ``bwd16`` (train mode with recs, math "fp32": the BWD16 step): the forward of
+    math "fp32", returning (z fp32, z bf16 copy) unless deferred, and a record for a bf16-math
+    backward -- ``x16`` the bf16 copy of x (None: the stem's NHWC4 input), the bf16 CRSK weights."""
     w = conv.weight
     k, c, r, s = w.shape
+    if bwd16 and not (training and recs is not None and math == "fp32" and groups == 1
+                      and not dual and not y16):
+        raise RuntimeError("bwd16 is the train-mode fp32 forward of an ungrouped conv with a "
+                           "recorded backward")
     cs = x.shape[3]
     s16 = _store16(math)
     if r == 1 and s == 1 and c == cs and not s16:
@@ -252,8 +289,17 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
     # (bf16 activations too: the bits of the rounded z, tmr_bn_apply_bits_a16)
     bits = (recs is not None and relu and not dual and _dma32(math) and y.dtype == torch.float32
             and (residual is not None or branch is not None))
+    z16 = None
     if defer:
         z = None
+    elif bwd16 and bits and branch is not None:
+        z, zbits, z16 = ops.bn_apply2_bits_dual(y, scale, shift, branch[0], branch[1], branch[2])
+    elif bwd16 and bits:
+        z, zbits, z16 = ops.bn_apply_bits_dual(y, scale, shift, residual)
+    elif bwd16:
+        if residual is not None or branch is not None:
+            raise RuntimeError("bwd16: a residual unit without ReLU has no dual apply")
+        z, z16 = ops.bn_apply_dual(y, scale, shift, None, relu)
     elif branch is not None and bits:
         z, zbits = ops.bn_apply2_bits(y, scale, shift, branch[0], branch[1], branch[2])
     elif bits:
@@ -271,7 +317,9 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
         # without a residual the backward recomputes the ReLU mask from y (scale/shift)
         has_res = residual is not None or branch is not None
         # the dgrad view of a bf16-operand conv reads the transposed weights (LDS-DMA engine)
-        if groups > 1 and ((_full16(math) and x.dtype == torch.bfloat16) or _dma32(math)):
+        if bwd16:   # (the stem's 3 input channels: no dgrad)
+            wt = ops.weight_to_crsk(w.detach().contiguous()) if c % 8 == 0 else None
+        elif groups > 1 and ((_full16(math) and x.dtype == torch.bfloat16) or _dma32(math)):
             wt = ops.weight_to_crsk_grouped(w.detach().contiguous(), groups,
                                             bf16=x.dtype == torch.bfloat16)
         elif _full16(math) and x.dtype == torch.bfloat16:
@@ -280,12 +328,16 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
             wt = ops.weight_to_crsk(w.detach().contiguous(), bf16=False)
         else:   # (the stem's 3 input channels: no dgrad)
             wt = None
-        recs.append({"x": x, "wk": wk, "wt": wt, "y": y,
+        # bwd16: the backward's conv views read the bf16 copies in bf16 math, dy stored bf16
+        recs.append({"x": x16 if (bwd16 and x16 is not None) else x, "wk": wk, "wt": wt, "y": y,
                      "z": (z[0] if dual else z) if has_res else None, "zbits": zbits,
                      "scale": scale, "shift": shift, "mean": mean, "inv": inv,
                      "stride": stride, "pad": pad, "relu": relu, "conv": conv, "bn": bn,
-                     "c_real": c, "math": math, "groups": groups})
-    return (y, scale, shift) if defer else z
+                     "c_real": c, "math": "bf16" if bwd16 else math, "groups": groups,
+                     "res": has_res, "dy16": bwd16})
+    if defer:
+        return y, scale, shift
+    return (z, z16) if bwd16 else z
 
 
 def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need_dx=True,
@@ -308,12 +360,13 @@ def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need
     r16: the same for fuse_prev a block output (R16): the dgrad adds into dx_out (bf16 in place,
     or fp32 read and a new bf16 tensor returned).
     fold: with parts, the fp32 wgrad may produce dy itself (WGRAD_BNBWD) where the library serves
-    the unit; the ResNet-50 trunk's units only.
+    the unit; the ResNet-50 trunk's units only (records of math "fp32": not the BWD16 step's).
     gcoef: (g, coef) in place of dy -- the caller ran the BN backward's reductions
     (ops.bn_bwd_parts_ds_coef) and the fused wgrad produces dy from the masked gradient g, this
     unit's y and its coefficients; only wgrad and dgrad run here."""
     conv, bn = rec["conv"], rec["bn"]
-    s16 = _store16(rec["math"])   # dy feeds only this conv's dgrad / wgrad
+    # dy feeds only this conv's dgrad / wgrad (the BWD16 step's records always store it bf16)
+    s16 = rec.get("dy16", False) or _store16(rec["math"])
     dy_given = dy is not None or gcoef is not None
     dw = None
     kr, ks = conv.weight.shape[2:]
@@ -361,10 +414,13 @@ def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need
         wdg = rec["wt"] if wt else rec["wk"]
         if fuse_prev is not None:
             p = fuse_prev
-            mask = (1 if p["z"] is not None else 2) if p["relu"] else 0
+            mask = (1 if p.get("res", p["z"] is not None) else 2) if p["relu"] else 0
             zm = p["z"]
             if mask == 1 and wt and p.get("zbits") is not None:
-                mask, zm = 3, p["zbits"]   # the ReLU mask as bits (fp32 LDS-DMA dgrad)
+                mask, zm = 3, p["zbits"]   # the ReLU mask as bits (LDS-DMA dgrad)
+            elif mask == 1 and zm is None:   # (the BWD16 step keeps only the bits)
+                raise RuntimeError("a residual unit's ReLU mask needs its saved z or its bits on "
+                                   "the LDS-DMA dgrad")
             bf8 = (wt and p["y"].dtype == torch.bfloat16 and
                    (p["y"].shape[-1] // grp) % 8 == 0)
             # (a grouped dgrad -- ResNeSt's radix-2 conv -- stores its per-group channel slices bf16
@@ -404,7 +460,10 @@ class TrunkFn(torch.autograd.Function):
         recs = [] if keep else None
         nbt = []   # BatchNorm num_batches_tracked counters, incremented together at the end
         conv1, bn1, layers = share.trunk_parts()
-        mt = share.precision
+        mt = _fwd_math(share.precision)
+        # the BWD16 step: the fp32 forward plus the bf16 copies its bf16-math backward reads
+        # (without a backward to record -- eval, no grad -- it is the fp32 path itself)
+        bw = bool(keep and share.precision == BWD16)
         a16 = training and _act16(mt)            # every activation bf16: no fp32 copies
         f16 = training and _full16(mt) and not a16
         # eval mode, opt-in (share.infer_act16): every stored activation bf16, rounded once after
@@ -418,8 +477,11 @@ class TrunkFn(torch.autograd.Function):
             # share.bn1 + relu applied inside the maxpool (the backward recomputes the ReLU
             # mask from y, so the stem's BN output is never needed)
             y0, sc0, sh0 = _conv_bn(xs, conv1, bn1, 2, 3, True, training, recs=recs, math=mt,
-                                    defer=True, nbt=nbt)
-            p, am = ops.maxpool_fwd_bn(y0, sc0, sh0, bf16=f16)
+                                    defer=True, nbt=nbt, bwd16=bw)
+            if bw:
+                p, h16, am = ops.maxpool_fwd_bn_dual(y0, sc0, sh0)
+            else:
+                p, am = ops.maxpool_fwd_bn(y0, sc0, sh0, bf16=f16)
             stem_hw = (y0.shape[1], y0.shape[2])
         elif i16:
             # bf16-activation inference: the stem reads the NHWC8 bf16 copy of its input on the
@@ -437,30 +499,45 @@ class TrunkFn(torch.autograd.Function):
         # h: the block input as the identity residual (fp32), hx: as the conv operand (the bf16
         # copy under f16; the maxpool output is only ever a conv operand)
         h, hx = (None, p) if f16 else (p, p)
+        if not bw:
+            h16 = None   # (bw: the bf16 copy of the block input, the wgrads' operand)
+        z1h = z2h = None
         blocks = []
         for layer in layers:
             for blk in layer:
                 brec = [] if keep else None
                 z1 = _conv_bn(hx, blk.conv1, blk.bn1, 1, 0, True, training, recs=brec, math=mt,
-                              nbt=nbt, y16=i16)
+                              nbt=nbt, y16=i16, bwd16=bw, x16=h16)
+                if bw:
+                    z1, z1h = z1
                 z2 = _conv_bn(z1, blk.conv2, blk.bn2, blk.stride, 1, True, training, recs=brec,
-                              math=mt, nbt=nbt, y16=i16)
+                              math=mt, nbt=nbt, y16=i16, bwd16=bw, x16=z1h)
+                if bw:
+                    z2, z2h = z2
                 if blk.downsample is not None:
                     # train: the branch's BN is applied inside the BN3 pass (bn_apply2)
                     idn = _conv_bn(hx, blk.downsample[0], blk.downsample[1], blk.stride, 0, False,
                                    training, recs=brec, math=mt, defer=training, nbt=nbt,
-                                   y16=i16)
+                                   y16=i16, bwd16=bw, x16=h16)
                 else:
                     if h is None:
                         raise RuntimeError("identity residual of the stem output (no downsample)")
                     idn = h
                 if isinstance(idn, tuple):
                     h = _conv_bn(z2, blk.conv3, blk.bn3, 1, 0, True, training, branch=idn,
-                                 recs=brec, math=mt, nbt=nbt, dual=f16)
+                                 recs=brec, math=mt, nbt=nbt, dual=f16, bwd16=bw, x16=z2h)
                 else:
                     h = _conv_bn(z2, blk.conv3, blk.bn3, 1, 0, True, training, residual=idn,
-                                 recs=brec, math=mt, nbt=nbt, dual=f16, y16=i16)
-                h, hx = h if f16 else (h, h)
+                                 recs=brec, math=mt, nbt=nbt, dual=f16, y16=i16, bwd16=bw,
+                                 x16=z2h)
+                if bw:
+                    h, h16 = h
+                    hx = h
+                    if blocks:   # the previous block output's fp32 z: its mask is in the bits
+                        blocks[-1][1][-1]["z"] = None
+                    del z1, z2, idn   # (their fp32 z's were only this block's forward operands)
+                else:
+                    h, hx = h if f16 else (h, h)
                 blocks.append((blk, brec))
         feat = ops.avgpool_fwd(h)
         ops.counters_add_one(nbt)
@@ -507,7 +584,8 @@ class TrunkFn(torch.autograd.Function):
                     gc3 = (g, c3) if f3 else None
                     gcd = (g, cd) if fd else None
                 else:
-                    dy3, dg3, db3, dyd, dgd, dbd = ops.bn_bwd_parts_ds(*bargs)
+                    dy3, dg3, db3, dyd, dgd, dbd = ops.bn_bwd_parts_ds(
+                        *bargs, dy16=_ds_dy16(r3, rd))
                 grads[r3["bn"].weight], grads[r3["bn"].bias] = dg3, db3
                 grads[rd["bn"].weight], grads[rd["bn"].bias] = dgd, dbd
                 dz2, _, fz2 = _conv_bn_bwd(r3, None, grads, fuse_prev=r2, g16=True, dy=dy3, gcoef=gc3)
@@ -560,7 +638,11 @@ class ResNet50Share(nn.Sequential):
 
     def __init__(self, indexed=False, precision="fp32"):
         super().__init__()
-        self.precision = precision   # conv operand precision: "fp32" | "bf16" (ops.MATH)
+        # conv operand precision: "fp32" | "bf16" (ops.MATH), or "bf16-bwd" (BWD16: the fp32
+        # forward, bf16 operands in the backward convs only)
+        if precision not in ("fp32", "bf16", BWD16):
+            raise ValueError("precision must be 'fp32', 'bf16' or 'bf16-bwd', got %r" % (precision,))
+        self.precision = precision
         # eval mode under precision "bf16", opt-in: bf16 activations (TrunkFn._forward i16; the
         # default keeps every eval path's fp32 activations and bits)
         self.infer_act16 = False
