@@ -363,6 +363,61 @@ typedef struct tmr_wlayout {
 } tmr_wlayout;
 int tmr_weight_layouts_epb(void);
 int tmr_weight_layouts_multi(const tmr_wlayout* table, int n, int total_blocks, hipStream_t stream);
+/* The same launch with a per-entry factor: scales (device memory, n pointers) holds NULL, or k
+ * per-output-channel factors that entry's copy is multiplied by before it is stored
+ * (out[...k...] = w[k][...] * scale[k]).  The frozen-BatchNorm step's dgrad weights. */
+int tmr_weight_layouts_multi_scaled(const tmr_wlayout* table, const float* const* scales, int n,
+                                    int total_blocks, hipStream_t stream);
+
+/* ---- Frozen BatchNorm: a train-mode step on the running statistics (fp32) --------------------
+ * Forward: z = y*scale + shift with scale = gamma / sqrt(running_var + eps), shift = beta -
+ * running_mean*scale, through tmr_bn_apply / _bits / tmr_bn_apply2_bits / tmr_maxpool2d_fwd_bn;
+ * tmr_bn_frozen_params computes scale, shift and inv = 1 / sqrt(running_var + eps) of every table
+ * entry (device memory) in one launch, tmr_bn_eval_params' arithmetic per channel.
+ * Backward, with g the gradient at the BN output after the ReLU mask: dy = g*scale,
+ * dbeta = sum g, dgamma = inv * sum g*(y - running_mean), the identity branch receives g.
+ * tmr_bn_frozen_bwd does all of it in one read of g and y:
+ *   mask 0: g is already masked (or the BN has no ReLU); 1: zmask = the saved output z (z > 0);
+ *   2: the forward's fmaf(y, scale, shift) > 0 (no residual); 3: zmask = tmr_bn_apply_bits' bits.
+ *   dres (NULL, or g itself: in place) receives the masked g, dy (NULL: the caller folds the scale
+ *   into its conv operands) g*scale, parts the partial sums: tmr_bn_frozen_bwd_parts(rows, c) rows
+ *   of c float2 (sum g, sum g*(y - mean)) -- the layout of tmr_conv2d_dgrad_bnbwd's partials, which
+ *   a frozen BN's `mean` = running_mean makes the same sums.  want_sums = 0 reads no y (mask 2
+ *   aside) and leaves parts untouched.  tmr_bn_frozen_finalize reduces either kind of partials to
+ *   dgamma / dbeta (either may be NULL); its workspace is tmr_bn_parts_ws_bytes(nparts, c).
+ * tmr_bn_frozen_bwd_ds: a downsample block's two BNs on one g -- also dy_ds = g*scale_d and the
+ *   partials of (g, y_ds, mean_d), bit for bit two single calls.
+ * tmr_bn_frozen_bwd_maxpool: the stem -- g gathered through MaxPool2d(3,2,1)'s argmax
+ *   (tmr_maxpool2d_bwd's values), mask 2; tmr_bn_frozen_bwd_maxpool_parts(n, h, w, c) rows.
+ * 8 channels per thread, 16-B pieces: channels must be a multiple of 8 (c / 8 up to 32 or a
+ * multiple of 32; the maxpool form: a power of two up to 256) and the tensors 16-B aligned --
+ * anything else is refused.
+ * tmr_scale_rows: w[k][0..row) *= scale[k] in place -- dW of a unit whose wgrad ran on g. */
+typedef struct tmr_bn_frozen_entry {
+  const float *gamma, *beta, *mean, *var; /* the BN's weight, bias, running_mean, running_var */
+  float *scale, *shift, *inv;             /* c floats each */
+  int c;
+  float eps;
+} tmr_bn_frozen_entry;
+int tmr_bn_frozen_params(const tmr_bn_frozen_entry* table, int n, hipStream_t stream);
+int tmr_bn_frozen_bwd_parts(int rows, int c);
+int tmr_bn_frozen_bwd(const float* g, const void* zmask, int mask, const float* y,
+                      const float* scale, const float* shift, const float* mean, float* dy,
+                      float* dres, void* parts, size_t parts_bytes, int rows, int c, int want_sums,
+                      hipStream_t stream);
+int tmr_bn_frozen_bwd_ds(const float* g, const void* zmask, int mask, const float* y,
+                         const float* scale, const float* shift, const float* mean, float* dy,
+                         const float* yd, const float* scale_d, const float* mean_d, float* dyd,
+                         float* dres, void* parts, void* parts_d, size_t parts_bytes, int rows,
+                         int c, int want_sums, hipStream_t stream);
+int tmr_bn_frozen_bwd_maxpool_parts(int n, int h, int w, int c);
+int tmr_bn_frozen_bwd_maxpool(const float* dyp, const uint8_t* argmax, int n, int h, int w, int ho,
+                              int wo, const float* y, const float* scale, const float* shift,
+                              const float* mean, float* dy, void* parts, size_t parts_bytes, int c,
+                              int want_sums, hipStream_t stream);
+int tmr_bn_frozen_finalize(const void* parts, int nparts, int c, const float* inv, float* dgamma,
+                           float* dbeta, void* ws, size_t ws_bytes, hipStream_t stream);
+int tmr_scale_rows(float* w, const float* scale, int k, long row, hipStream_t stream);
 int tmr_bn_apply_dual(const float* y, const float* scale, const float* shift, const float* residual,
                       float* z, void* z16, int rows, int c, int relu, hipStream_t stream);
 /* Block outputs of the fp32 train step: tmr_bn_apply (residual optional) / tmr_bn_apply2 with

@@ -90,10 +90,8 @@ def kernel_table(path, frames, top):
 
 
 # ---------------------------------------------------------------- the legs
-def main():
-    ap = argparse.ArgumentParser()
+def add_protocol_args(ap):
     ap.add_argument("--config", choices=sorted(CONFIGS), default="C2")
-    ap.add_argument("--precisions", default=",".join(PRECISIONS))
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
@@ -101,6 +99,12 @@ def main():
                     help="bench.py's --augment (its default: the reference train transform)")
     ap.add_argument("--no-prof", action="store_true", help="skip the instrumented step")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    add_protocol_args(ap)
+    ap.add_argument("--precisions", default=",".join(PRECISIONS))
     ap.add_argument("--kernel-table", default=None, metavar="STATS_CSV")
     ap.add_argument("--top", type=int, default=16)
     args = ap.parse_args()
@@ -108,7 +112,19 @@ def main():
     if args.kernel_table:
         kernel_table(args.kernel_table, clips * T, args.top)
         return
+    precs = [p for p in args.precisions.split(",") if p]
+    for p in precs:
+        if p not in PRECISIONS:
+            raise SystemExit("unknown precision %r" % p)
+    run_legs(args, [(p, p, None) for p in precs])
 
+
+def run_legs(args, specs):
+    """The protocol above over `specs` = [(leg name, trunk precision, prepare)]: prepare(model),
+    when given, runs on the leg's fresh train-mode model before its optimizer is built (other
+    benchmarks' legs: scripts/frozen_bn_bench.py).  One JSON line per leg, its name under
+    "precision"."""
+    clips, T, L = CONFIGS[args.config]
     import torch
     import bench
     import tmrnet_amd
@@ -116,10 +132,7 @@ def main():
     from tmrnet_amd.augment import ClipAugment
     from tmrnet_amd.optim import sgd_param_groups
 
-    precs = [p for p in args.precisions.split(",") if p]
-    for p in precs:
-        if p not in PRECISIONS:
-            raise SystemExit("unknown precision %r" % p)
+    precs = [name for name, _, _ in specs]
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     per_leg = args.warmup + args.steps
@@ -131,9 +144,11 @@ def main():
     lr = 5e-7   # bench.py's (the reference default)
 
     legs = {}
-    for p in precs:
+    for p, trunk_precision, prepare in specs:
         torch.manual_seed(0)
-        model = tmrnet_amd.resnet_lstm(seq_len=T, precision=p).to(dev).train()
+        model = tmrnet_amd.resnet_lstm(seq_len=T, precision=trunk_precision).to(dev).train()
+        if prepare is not None:
+            prepare(model)
         opt = tmrnet_amd.SGD(sgd_param_groups(model, lr), lr=lr / 10, momentum=0.9,
                              weight_decay=5e-4)
         legs[p] = dict(model=model, opt=opt, ms=[], mem=0, oom=False, i=0)

@@ -3,7 +3,7 @@ libtmr.so behind a C ABI, PyTorch-ROCm only for memory, streams and torch.distri
 from . import _lib, ops  # noqa: F401
 from .lstm import LSTM  # noqa: F401
 from .nlblock import NLBlock, LFBRows  # noqa: F401
-from .trunk import ResNet50Share, resnet50_share  # noqa: F401
+from .trunk import ResNet50Share, resnet50_share, freeze_bn, unfreeze_bn  # noqa: F401
 from .model import resnet_lstm, resnet_lstm_LFB, MemoryBankModel  # noqa: F401
 from .loss import CrossEntropyLoss  # noqa: F401
 from .optim import SGD, Adam  # noqa: F401

@@ -118,6 +118,15 @@ SIGNATURES = {
     "tmr_bn_bwd_g16": [P, P, P, P, P, P, P, P, I, I, P, SZ, P],
     "tmr_weight_layouts_epb": [],
     "tmr_weight_layouts_multi": [P, I, I, P],
+    "tmr_weight_layouts_multi_scaled": [P, P, I, I, P],
+    "tmr_bn_frozen_params": [P, I, P],
+    "tmr_bn_frozen_bwd_parts": [I, I],
+    "tmr_bn_frozen_bwd": [P, P, I, P, P, P, P, P, P, P, SZ, I, I, I, P],
+    "tmr_bn_frozen_bwd_ds": [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, SZ, I, I, I, P],
+    "tmr_bn_frozen_bwd_maxpool_parts": [I, I, I, I],
+    "tmr_bn_frozen_bwd_maxpool": [P, P, I, I, I, I, I, P, P, P, P, P, P, SZ, I, I, P],
+    "tmr_bn_frozen_finalize": [P, I, I, P, P, P, P, SZ, P],
+    "tmr_scale_rows": [P, P, I, L, P],
     "tmr_bn_bwd_parts_ds_ws_bytes": [I, I, I],
     "tmr_bn_bwd_parts_ds_coef_offset": [I, I, I, I],
     "tmr_bn_bwd_parts_ds": [P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, P, SZ, P],

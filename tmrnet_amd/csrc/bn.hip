@@ -2125,3 +2125,480 @@ TMR_API int tmr_bn_bwd_maxpool_a16(const float* dyp, const uint8_t* argmax, int 
   TMR_CHECK_LAUNCH("stem_bwd_apply");
   return 0;
 }
+
+// ---- frozen BatchNorm: a train-mode step on the running statistics (include/tmr.h
+// "tmr_bn_frozen_*") ----------------------------------------------------------------------------
+// The forward is the eval-mode BN (y*scale + shift, scale = gamma / sqrt(running_var + eps),
+// shift = beta - running_mean*scale) through the existing apply forms.  The backward has no
+// projection: with g the ReLU-masked gradient at the BN output, dy = g*scale, dbeta = sum g,
+// dgamma = inv * sum g*(y - running_mean) -- one read of g and y where the batch-statistics
+// backward reduces and then applies.  These kernels serve the units whose g arrives unmasked (the
+// last block's bn3, the stem through the maxpool) or that share g (a downsample block's two BNs);
+// the other units take g masked from a fused dgrad, whose partials tmr_bn_frozen_finalize reads.
+namespace {
+
+// The coefficients of every BN of a trunk in one launch: one workgroup per table entry,
+// bn_eval_params_k's arithmetic per channel (so the frozen step and eval mode apply the same
+// scale / shift), plus inv for dgamma.
+__global__ __launch_bounds__(NT) void bn_frozen_params_k(const tmr_bn_frozen_entry* __restrict__ tab) {
+  const tmr_bn_frozen_entry e = tab[blockIdx.x];
+  for (int ch = threadIdx.x; ch < e.c; ch += NT) {
+    float inv = 1.0f / sqrtf(e.var[ch] + e.eps);
+    float g = e.gamma ? e.gamma[ch] : 1.f;
+    float b = e.beta ? e.beta[ch] : 0.f;
+    e.scale[ch] = g * inv;
+    e.shift[ch] = b - e.mean[ch] * g * inv;
+    e.inv[ch] = inv;
+  }
+}
+
+// A thread keeps 8 channels and walks rows (its sums stay in registers); cthreads threads side by
+// side cover 32 B each of a row, the block's other threads take other rows.
+struct FPlan {
+  int cthreads, rthreads, cblocks, rpb, nrb;
+};
+
+// c / 8 channel groups in blocks of cthreads: every c / 8 up to 32 and every multiple of 32 above
+bool fplan_covers(int c) {
+  const int c8 = c / 8;
+  return c % 8 == 0 && c8 > 0 && c8 % (c8 < 32 ? c8 : 32) == 0;
+}
+
+FPlan make_fplan(int rows, int c) {
+  FPlan p;
+  const int c8 = c / 8;
+  p.cthreads = c8 < 32 ? c8 : 32;
+  p.rthreads = NT / p.cthreads;
+  p.cblocks = c8 / p.cthreads;
+  // ~4096 workgroups for large inputs, >= 4 rows per thread
+  int target = 4096 / p.cblocks;
+  if (target < 1) target = 1;
+  int rpb = cdiv(rows, target);
+  if (rpb < p.rthreads * 4) rpb = p.rthreads * 4;
+  rpb = (rpb + p.rthreads - 1) / p.rthreads * p.rthreads;
+  p.rpb = rpb;
+  p.nrb = cdiv(rows, rpb);
+  return p;
+}
+
+// MASK 0: g is already masked (or the BN has no ReLU); 1: z > 0 from the saved output z; 2: from
+// the forward's own fmaf(y, scale, shift) (no residual); 3: from the ReLU-mask bits of
+// tmr_bn_apply_bits (8 elements = one byte).  DUAL: a downsample block's second BN (y_ds, its
+// scale and mean) on the same masked g.  Outputs that are NULL are skipped: dres (may alias g: the
+// identity branch's gradient in place), dy / dy_ds (the caller folds the scale into its conv
+// operands), parts / parts_d (want_sums = 0).  Partials: float2 (sum g, sum g*(y - mean)) per row
+// block and channel, the layout of the fused dgrad's (tmr_conv2d_dgrad_bnbwd).
+template <int MASK, bool DUAL>
+__global__ __launch_bounds__(NT) void bn_frozen_bwd8_k(
+    const float* g, const void* __restrict__ zm, const float* __restrict__ y,
+    const float* __restrict__ scale, const float* __restrict__ shift,
+    const float* __restrict__ mean, float* __restrict__ dy, float* dres,
+    const float* __restrict__ yd, const float* __restrict__ scale_d,
+    const float* __restrict__ mean_d, float* __restrict__ dyd, float2* __restrict__ parts,
+    float2* __restrict__ parts_d, int rows, int c, int rpb, int cthreads) {
+  constexpr int NV = DUAL ? 24 : 16;
+  const int rthreads = NT / cthreads;
+  const int tc = threadIdx.x % cthreads, tr = threadIdx.x / cthreads;
+  const bool live = tr < rthreads;   // NT is no multiple of cthreads = 3 (c = 24): one thread idles
+  const int c8 = c >> 3;
+  const int cg = blockIdx.y * cthreads + tc;
+  const bool sums = parts != nullptr;
+  const bool need_y = sums || MASK == 2;
+  float sc[8], sf[8], mu[8], sd[8], md[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    sc[e] = scale[cg * 8 + e];
+    sf[e] = MASK == 2 ? shift[cg * 8 + e] : 0.f;
+    mu[e] = mean[cg * 8 + e];
+    sd[e] = DUAL ? scale_d[cg * 8 + e] : 0.f;
+    md[e] = DUAL ? mean_d[cg * 8 + e] : 0.f;
+  }
+  float s[8], q[8], qd[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s[e] = q[e] = qd[e] = 0.f;
+  const int r0 = blockIdx.x * rpb;
+  const int r1 = min(rows, r0 + rpb);
+  auto step = [&](long i, const float (&gv)[8], const float (&yv)[8], const float (&dv)[8],
+                  const float (&zv)[8], uint32_t mb) {
+    float gm[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      bool on = true;
+      if (MASK == 1) on = zv[e] > 0.f;
+      if (MASK == 2) on = fmaf(yv[e], sc[e], sf[e]) > 0.f;
+      if (MASK == 3) on = (mb >> e) & 1u;
+      gm[e] = on ? gv[e] : 0.f;
+    }
+    if (dres) st8(dres, i, gm);
+    if (dy) {
+      float o[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = gm[e] * sc[e];
+      st8(dy, i, o);
+    }
+    if (DUAL && dyd) {
+      float o[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = gm[e] * sd[e];
+      st8(dyd, i, o);
+    }
+    if (sums) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        s[e] += gm[e];
+        q[e] = fmaf(gm[e], yv[e] - mu[e], q[e]);
+        if (DUAL) qd[e] = fmaf(gm[e], dv[e] - md[e], qd[e]);
+      }
+    }
+  };
+  auto load = [&](long i, float (&gv)[8], float (&yv)[8], float (&dv)[8], float (&zv)[8],
+                  uint32_t& mb) {
+    ld8(g, i, gv);
+    if (need_y) ld8(y, i, yv);
+    if (DUAL && sums) ld8(yd, i, dv);
+    if (MASK == 1) ld8(reinterpret_cast<const float*>(zm), i, zv);
+    if (MASK == 3) mb = (reinterpret_cast<const uint32_t*>(zm)[i >> 2] >> (8 * (int)(i & 3))) & 0xffu;
+  };
+  // two row groups in flight per thread, both loaded before either is used (as bn_bwd_apply8_k)
+  if (live) {
+    for (int r = r0 + tr; r < r1; r += 2 * rthreads) {
+      const int rb = r + rthreads;
+      const bool hb = rb < r1;
+      const long i = (long)r * c8 + cg, j = (long)rb * c8 + cg;
+      float ga[8], ya[8], da[8], za[8], gb[8], yb[8], db[8], zb[8];
+      uint32_t ma = 0, mbb = 0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ya[e] = da[e] = za[e] = yb[e] = db[e] = zb[e] = 0.f;
+      load(i, ga, ya, da, za, ma);
+      if (hb) load(j, gb, yb, db, zb, mbb);
+      step(i, ga, ya, da, za, ma);
+      if (hb) step(j, gb, yb, db, zb, mbb);
+    }
+  }
+  if (!sums) return;   // (uniform: a kernel argument)
+  __shared__ float red[NV][NT];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    red[e][threadIdx.x] = s[e];
+    red[8 + e][threadIdx.x] = q[e];
+    if (DUAL) red[NV - 8 + e][threadIdx.x] = qd[e];
+  }
+  __syncthreads();
+  if (tr == 0) {
+    float a[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) a[v] = 0.f;
+    for (int k = 0; k < rthreads; ++k)
+#pragma unroll
+      for (int v = 0; v < NV; ++v) a[v] += red[v][k * cthreads + tc];
+    const long o = (long)blockIdx.x * c + cg * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      parts[o + e] = make_float2(a[e], a[8 + e]);
+      if (DUAL) parts_d[o + e] = make_float2(a[e], a[NV - 8 + e]);
+    }
+  }
+}
+
+// The stem: the gradient through MaxPool2d(3,2,1) gathered per 2x2 input quad (stem_bwd_apply8q's
+// gather and summation order), masked by the forward's fmaf(y, scale, shift) > 0, dy = g*scale and
+// the per-channel partial sums in the same pass.  c / 8 is a power of two that divides NT, so a
+// thread's channel group is the same on every grid-stride trip and its sums stay in registers.
+__global__ __launch_bounds__(NT) void bn_frozen_bwd_maxpool8q_k(
+    const PoolGeo pg, int h, int w, FastDiv dQHW, FastDiv dQW, const float* __restrict__ y,
+    const float* __restrict__ scale, const float* __restrict__ shift,
+    const float* __restrict__ mean, float* __restrict__ dy, float2* __restrict__ parts, int nq,
+    int lc8) {
+  const int c8 = 1 << lc8, c = c8 * 8;
+  const uint2* am = reinterpret_cast<const uint2*>(pg.am);
+  const float4* dp = reinterpret_cast<const float4*>(pg.dyp);
+  const int cq = threadIdx.x & (c8 - 1);
+  const bool sums = parts != nullptr;
+  float sc[8], sf[8], mu[8], s[8], q[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    sc[e] = scale[cq * 8 + e];
+    sf[e] = shift[cq * 8 + e];
+    mu[e] = mean[cq * 8 + e];
+    s[e] = q[e] = 0.f;
+  }
+  for (int i = blockIdx.x * NT + threadIdx.x; i < nq; i += gridDim.x * NT) {
+    const uint32_t qi = (uint32_t)i >> lc8;
+    const uint32_t nn = fdiv(qi, dQHW);
+    const uint32_t rem = qi - nn * dQHW.d;
+    const int k = (int)fdiv(rem, dQW), l = (int)(rem - (uint32_t)k * dQW.d);
+    const bool pin[2][2] = {{true, l + 1 < pg.wo}, {k + 1 < pg.ho, k + 1 < pg.ho && l + 1 < pg.wo}};
+    uint2 a[2][2];
+    float4 d0[2][2], d1[2][2];
+#pragma unroll
+    for (int ddy = 0; ddy < 2; ++ddy)
+#pragma unroll
+      for (int ddx = 0; ddx < 2; ++ddx) {
+        const int o = (((int)nn * pg.ho + k + ddy) * pg.wo + l + ddx) * c8 + cq;
+        if (pin[ddy][ddx]) {
+          a[ddy][ddx] = am[o];
+          d0[ddy][ddx] = dp[2 * (long)o];
+          d1[ddy][ddx] = dp[2 * (long)o + 1];
+        } else {
+          a[ddy][ddx] = make_uint2(0xffffffffu, 0xffffffffu);
+          d0[ddy][ddx] = d1[ddy][ddx] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+#pragma unroll
+    for (int py = 0; py < 2; ++py)
+#pragma unroll
+      for (int px = 0; px < 2; ++px) {
+        const int iy = 2 * k + py, ix = 2 * l + px;
+        if (iy >= h || ix >= w) continue;
+        const long pix = ((long)nn * h + iy) * w + ix;
+        float v[8], gq[8];
+        ld8(y, pix * c8 + cq, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) gq[e] = 0.f;
+#pragma unroll
+        for (int ddy = 0; ddy < 2; ++ddy)
+#pragma unroll
+          for (int ddx = 0; ddx < 2; ++ddx) {
+            if (ddy > py || ddx > px || !pin[ddy][ddx]) continue;
+            const uint32_t id = (uint32_t)((py + 1 - 2 * ddy) * 3 + (px + 1 - 2 * ddx));
+            const float dv[8] = {d0[ddy][ddx].x, d0[ddy][ddx].y, d0[ddy][ddx].z, d0[ddy][ddx].w,
+                                 d1[ddy][ddx].x, d1[ddy][ddx].y, d1[ddy][ddx].z, d1[ddy][ddx].w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              const uint32_t ab = ((e < 4 ? a[ddy][ddx].x : a[ddy][ddx].y) >> (8 * (e & 3))) & 0xffu;
+              if (ab == id) gq[e] += dv[e];
+            }
+          }
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float gm = fmaf(v[e], sc[e], sf[e]) > 0.f ? gq[e] : 0.f;
+          o[e] = gm * sc[e];
+          s[e] += gm;
+          q[e] = fmaf(gm, v[e] - mu[e], q[e]);
+        }
+        st8(dy, pix * c8 + cq, o);
+      }
+  }
+  if (!sums) return;   // (uniform: a kernel argument)
+  __shared__ float red[16][NT];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    red[e][threadIdx.x] = s[e];
+    red[8 + e][threadIdx.x] = q[e];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < c8) {
+    float t[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) t[v] = 0.f;
+    for (int k = 0; k < NT / c8; ++k)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) t[v] += red[v][k * c8 + threadIdx.x];
+    const long o = (long)blockIdx.x * c + threadIdx.x * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) parts[o + e] = make_float2(t[e], t[8 + e]);
+  }
+}
+
+// level 2 of the partials' reduction (parts_slab_k<1> is level 1): dbeta = sum g,
+// dgamma = inv * sum g*(y - mean)
+__global__ __launch_bounds__(SLAB_CH * SLAB_PH) void frozen_final_slabs_k(
+    const double* __restrict__ ws, int nslabs, int c, const float* __restrict__ inv,
+    float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  int ch;
+  double t[3];
+  if (!slab_sum<2>(ws, nslabs, c, ch, t)) return;
+  if (dgamma) dgamma[ch] = (float)(t[1] * (double)inv[ch]);
+  if (dbeta) dbeta[ch] = (float)t[0];
+}
+
+// dW rows scaled per output channel: the wgrad of a unit whose dy = g*scale was folded away ran
+// on g, so dW[k] = scale[k] * (x^T g)[k]
+__global__ __launch_bounds__(NT) void scale_rows_k(float* __restrict__ w,
+                                                   const float* __restrict__ scale, long n,
+                                                   int row) {
+  for (long i = blockIdx.x * (long)NT + threadIdx.x; i < n; i += (long)gridDim.x * NT)
+    w[i] *= scale[i / row];
+}
+__global__ __launch_bounds__(NT) void scale_rows4_k(float4* __restrict__ w,
+                                                    const float* __restrict__ scale, long n4,
+                                                    int row4) {
+  for (long i = blockIdx.x * (long)NT + threadIdx.x; i < n4; i += (long)gridDim.x * NT) {
+    const float sv = scale[i / row4];
+    float4 v = w[i];
+    v.x *= sv; v.y *= sv; v.z *= sv; v.w *= sv;
+    w[i] = v;
+  }
+}
+
+int frozen_check(const char* name, int rows, int c, const void* a, const void* b, const void* d,
+                 const void* e, const void* f, const void* h) {
+  TMR_CHECK_ARG(rows > 0 && c >= 8 && c % 8 == 0,
+                "%s: bad shape rows=%d c=%d (channels must be a multiple of 8)", name, rows, c);
+  TMR_CHECK_ARG(fplan_covers(c), "%s: unsupported channel count %d", name, c);
+  TMR_CHECK_ARG((((uintptr_t)a | (uintptr_t)b | (uintptr_t)d | (uintptr_t)e | (uintptr_t)f |
+                  (uintptr_t)h) & 15) == 0,
+                "%s: g / z / y / y_ds / dy / dy_ds / dres must be 16-B aligned", name);
+  return 0;
+}
+
+}  // namespace
+
+TMR_API int tmr_bn_frozen_params(const tmr_bn_frozen_entry* table_dev, int n, hipStream_t stream) {
+  TMR_CHECK_ARG(table_dev && n > 0, "tmr_bn_frozen_params: empty table");
+  hipLaunchKernelGGL(bn_frozen_params_k, dim3(n), dim3(NT), 0, stream, table_dev);
+  TMR_CHECK_LAUNCH("bn_frozen_params");
+  return 0;
+}
+
+TMR_API int tmr_bn_frozen_bwd_parts(int rows, int c) {
+  if (rows <= 0 || c < 8 || c % 8 || !fplan_covers(c)) {
+    tmr_set_error("tmr_bn_frozen_bwd_parts: bad size (rows %d, channels %d)", rows, c);
+    return -1;
+  }
+  return make_fplan(rows, c).nrb;
+}
+
+static int bn_frozen_bwd_impl(bool dual, const float* g, const void* zmask, int mask,
+                              const float* y, const float* scale, const float* shift,
+                              const float* mean, float* dy, const float* yd, const float* scale_d,
+                              const float* mean_d, float* dyd, float* dres, void* parts,
+                              void* parts_d, size_t parts_bytes, int rows, int c, int want_sums,
+                              hipStream_t stream) {
+  const char* name = dual ? "tmr_bn_frozen_bwd_ds" : "tmr_bn_frozen_bwd";
+  if (const int rc = frozen_check(name, rows, c, g, mask == 1 ? zmask : nullptr, y, yd, dy, dyd))
+    return rc;
+  TMR_CHECK_ARG(((uintptr_t)dres & 15) == 0, "%s: dres must be 16-B aligned", name);
+  TMR_CHECK_ARG(mask >= 0 && mask <= 3, "%s: bad mask %d", name, mask);
+  TMR_CHECK_ARG(g && scale && mean, "%s: null operand", name);
+  TMR_CHECK_ARG(mask == 0 || mask == 2 || zmask, "%s: mask %d needs z (1) or the mask bits (3)", name, mask);
+  TMR_CHECK_ARG(mask != 3 || ((uintptr_t)zmask & 3) == 0, "%s: misaligned mask bits", name);
+  TMR_CHECK_ARG(mask != 2 || (y && shift), "%s: mask 2 needs y and shift", name);
+  TMR_CHECK_ARG(!dual || (scale_d && mean_d && (!want_sums || yd)), "%s: null downsample operand", name);
+  const FPlan p = make_fplan(rows, c);
+  float2 *pp = nullptr, *pd = nullptr;
+  if (want_sums) {
+    TMR_CHECK_ARG(y && parts && (!dual || parts_d), "%s: the sums need y and the partials buffer", name);
+    TMR_CHECK_ARG(parts_bytes >= (size_t)p.nrb * c * sizeof(float2),
+                  "%s: partials buffer too small (tmr_bn_frozen_bwd_parts rows of c float2)", name);
+    pp = (float2*)parts;
+    pd = (float2*)parts_d;
+  }
+  const dim3 grid(p.nrb, p.cblocks);
+#define TMR_FROZEN(M)                                                                           \
+  if (dual)                                                                                      \
+    hipLaunchKernelGGL((bn_frozen_bwd8_k<M, true>), grid, dim3(NT), 0, stream, g, zmask, y,      \
+                       scale, shift, mean, dy, dres, yd, scale_d, mean_d, dyd, pp, pd, rows, c,  \
+                       p.rpb, p.cthreads);                                                       \
+  else                                                                                           \
+    hipLaunchKernelGGL((bn_frozen_bwd8_k<M, false>), grid, dim3(NT), 0, stream, g, zmask, y,     \
+                       scale, shift, mean, dy, dres, yd, scale_d, mean_d, dyd, pp, pd, rows, c,  \
+                       p.rpb, p.cthreads)
+  if (mask == 0) { TMR_FROZEN(0); } else if (mask == 1) { TMR_FROZEN(1); }
+  else if (mask == 2) { TMR_FROZEN(2); } else { TMR_FROZEN(3); }
+#undef TMR_FROZEN
+  TMR_CHECK_LAUNCH("bn_frozen_bwd");
+  return 0;
+}
+
+TMR_API int tmr_bn_frozen_bwd(const float* g, const void* zmask, int mask, const float* y,
+                              const float* scale, const float* shift, const float* mean,
+                              float* dy, float* dres, void* parts, size_t parts_bytes, int rows,
+                              int c, int want_sums, hipStream_t stream) {
+  return bn_frozen_bwd_impl(false, g, zmask, mask, y, scale, shift, mean, dy, nullptr, nullptr,
+                            nullptr, nullptr, dres, parts, nullptr, parts_bytes, rows, c, want_sums,
+                            stream);
+}
+
+TMR_API int tmr_bn_frozen_bwd_ds(const float* g, const void* zmask, int mask, const float* y,
+                                 const float* scale, const float* shift, const float* mean,
+                                 float* dy, const float* yd, const float* scale_d,
+                                 const float* mean_d, float* dyd, float* dres, void* parts,
+                                 void* parts_d, size_t parts_bytes, int rows, int c, int want_sums,
+                                 hipStream_t stream) {
+  return bn_frozen_bwd_impl(true, g, zmask, mask, y, scale, shift, mean, dy, yd, scale_d, mean_d,
+                            dyd, dres, parts, parts_d, parts_bytes, rows, c, want_sums, stream);
+}
+
+TMR_API int tmr_bn_frozen_bwd_maxpool_parts(int n, int h, int w, int c) {
+  const long nq = (long)n * ((h + 1) / 2) * ((w + 1) / 2) * (c / 8);
+  if (n <= 0 || h <= 0 || w <= 0 || c < 8 || c % 8 || nq >= 0x7fffffffL) {
+    tmr_set_error("tmr_bn_frozen_bwd_maxpool_parts: bad size (n %d, h %d, w %d, channels %d)", n,
+                  h, w, c);
+    return -1;
+  }
+  return ew_blocks(nq);
+}
+
+TMR_API int tmr_bn_frozen_bwd_maxpool(const float* dyp, const uint8_t* argmax, int n, int h, int w,
+                                      int ho, int wo, const float* y, const float* scale,
+                                      const float* shift, const float* mean, float* dy,
+                                      void* parts, size_t parts_bytes, int c, int want_sums,
+                                      hipStream_t stream) {
+  const long rows_l = (long)n * h * w;
+  TMR_CHECK_ARG(n > 0 && h > 0 && w > 0 && c >= 8 && c % 8 == 0 && rows_l < 0x7fffffffL,
+                "tmr_bn_frozen_bwd_maxpool: bad shape n=%d h=%d w=%d c=%d (channels must be a "
+                "multiple of 8)", n, h, w, c);
+  const int c8 = c / 8;
+  TMR_CHECK_ARG((c8 & (c8 - 1)) == 0 && c8 <= NT,
+                "tmr_bn_frozen_bwd_maxpool: unsupported channel count %d (c / 8 must be a power of "
+                "two up to %d)", c, NT);
+  TMR_CHECK_ARG(ho == (h + 2 - 3) / 2 + 1 && wo == (w + 2 - 3) / 2 + 1,
+                "tmr_bn_frozen_bwd_maxpool: pooled %dx%d is not MaxPool2d(3,2,1) of %dx%d", ho, wo, h, w);
+  TMR_CHECK_ARG(dyp && argmax && y && scale && shift && mean && dy,
+                "tmr_bn_frozen_bwd_maxpool: null operand");
+  TMR_CHECK_ARG((((uintptr_t)dyp | (uintptr_t)y | (uintptr_t)dy) & 15) == 0 && ((uintptr_t)argmax & 7) == 0,
+                "tmr_bn_frozen_bwd_maxpool: dyp / y / dy must be 16-B aligned, argmax 8-B");
+  const int qh = (h + 1) / 2, qw = (w + 1) / 2;
+  const long nq_l = (long)n * qh * qw * c8;
+  TMR_CHECK_ARG(nq_l < 0x7fffffffL && (long)n * ho * wo * c8 < 0x7fffffffL,
+                "tmr_bn_frozen_bwd_maxpool: input too large");
+  const int nq = (int)nq_l, nb = ew_blocks(nq);
+  float2* pp = nullptr;
+  if (want_sums) {
+    TMR_CHECK_ARG(parts && parts_bytes >= (size_t)nb * c * sizeof(float2),
+                  "tmr_bn_frozen_bwd_maxpool: partials buffer too small "
+                  "(tmr_bn_frozen_bwd_maxpool_parts rows of c float2)");
+    pp = (float2*)parts;
+  }
+  PoolGeo pg;
+  pg.dyp = dyp; pg.am = (const uchar4*)argmax;
+  pg.dHW = make_fastdiv((uint32_t)(h * w)); pg.dW = make_fastdiv((uint32_t)w);
+  pg.ho = ho; pg.wo = wo;
+  hipLaunchKernelGGL(bn_frozen_bwd_maxpool8q_k, dim3(nb), dim3(NT), 0, stream, pg, h, w,
+                     make_fastdiv((uint32_t)(qh * qw)), make_fastdiv((uint32_t)qw), y, scale, shift,
+                     mean, dy, pp, nq, __builtin_ctz(c8));
+  TMR_CHECK_LAUNCH("bn_frozen_bwd_maxpool");
+  return 0;
+}
+
+TMR_API int tmr_bn_frozen_finalize(const void* parts, int nparts, int c, const float* inv,
+                                   float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                                   hipStream_t stream) {
+  TMR_CHECK_ARG(parts && inv && nparts > 0 && c > 0,
+                "tmr_bn_frozen_finalize: bad arguments (parts %d, channels %d)", nparts, c);
+  TMR_CHECK_ARG(ws && ws_bytes >= slab_ws_bytes(nparts, c),
+                "tmr_bn_frozen_finalize: workspace too small (need tmr_bn_parts_ws_bytes)");
+  const SlabPlan sp = slab_plan(nparts, c);
+  hipLaunchKernelGGL(parts_slab_k<1>, dim3(sp.groups, sp.nslabs), dim3(256), 0, stream, parts,
+                     nparts, c, sp.rows, (double*)ws);
+  TMR_CHECK_LAUNCH("bn_parts_slab");
+  hipLaunchKernelGGL(frozen_final_slabs_k, dim3(sp.groups), dim3(SLAB_CH * SLAB_PH), 0, stream,
+                     (const double*)ws, sp.nslabs, c, inv, dgamma, dbeta);
+  TMR_CHECK_LAUNCH("bn_frozen_final_slabs");
+  return 0;
+}
+
+TMR_API int tmr_scale_rows(float* w, const float* scale, int k, long row, hipStream_t stream) {
+  TMR_CHECK_ARG(w && scale && k > 0 && row > 0 && row < 0x7fffffffL,
+                "tmr_scale_rows: bad arguments (k %d, row %ld)", k, row);
+  const long n = (long)k * row;
+  if (row % 4 == 0 && ((uintptr_t)w & 15) == 0)
+    hipLaunchKernelGGL(scale_rows4_k, dim3(ew_blocks(n / 4)), dim3(NT), 0, stream, (float4*)w,
+                       scale, n / 4, (int)(row / 4));
+  else
+    hipLaunchKernelGGL(scale_rows_k, dim3(ew_blocks(n)), dim3(NT), 0, stream, w, scale, n, (int)row);
+  TMR_CHECK_LAUNCH("scale_rows");
+  return 0;
+}

@@ -482,8 +482,11 @@ TMR_API int tmr_weight_oihw_to_crsk_x(const float* w, void* wt, int k, int c, in
 // Every weight layout of a train step in one launch (tmr_weight_layouts_multi): block b converts
 // elements [ (b - block0) * NT * WL_EPB, ... ) of the entry whose block range holds it (binary
 // search over block0); the element mapping and rounding of oihw_to_krsc_k / oihw_to_crsk_k.
+// scales (tmr_weight_layouts_multi_scaled): per entry NULL or k per-output-channel factors the
+// copy is multiplied by (the frozen-BatchNorm step's dgrad weights, W[k] * scale[k])
 constexpr int WL_EPB = 8;
-__global__ __launch_bounds__(NT) void wlayout_multi_k(const tmr_wlayout* __restrict__ tab, int n) {
+__global__ __launch_bounds__(NT) void wlayout_multi_k(const tmr_wlayout* __restrict__ tab, int n,
+                                                      const float* const* __restrict__ scales) {
   int lo = 0, hi = n - 1;
   const long long b = blockIdx.x;
   while (lo < hi) {
@@ -491,6 +494,7 @@ __global__ __launch_bounds__(NT) void wlayout_multi_k(const tmr_wlayout* __restr
     if (tab[mid].block0 <= b) lo = mid; else hi = mid - 1;
   }
   const tmr_wlayout e = tab[lo];
+  const float* sc = scales ? scales[lo] : nullptr;
   const long long base = (b - e.block0) * (long long)NT * WL_EPB;
 #pragma unroll
   for (int j = 0; j < WL_EPB; ++j) {
@@ -503,12 +507,14 @@ __global__ __launch_bounds__(NT) void wlayout_multi_k(const tmr_wlayout* __restr
       const int tap = (int)(t % e.rs);
       const int ko = (int)(t / e.rs);
       v = ci < e.c ? e.w[((long long)ko * e.c + ci) * e.rs + tap] : 0.f;
+      if (sc) v *= sc[ko];
     } else {             // CRSK
       const int ko = (int)(i % e.k);
       const long long t = i / e.k;
       const int tap = (int)(t % e.rs);
       const int ci = (int)(t / e.rs);
       v = e.w[((long long)ko * e.c + ci) * e.rs + tap];
+      if (sc) v *= sc[ko];
     }
     if (e.bf16) reinterpret_cast<__bf16*>(e.out)[i] = (__bf16)v;   // RNE
     else reinterpret_cast<float*>(e.out)[i] = v;
@@ -518,8 +524,19 @@ __global__ __launch_bounds__(NT) void wlayout_multi_k(const tmr_wlayout* __restr
 TMR_API int tmr_weight_layouts_multi(const tmr_wlayout* tab_dev, int n, int total_blocks,
                                      hipStream_t stream) {
   TMR_CHECK_ARG(tab_dev && n > 0 && total_blocks > 0, "tmr_weight_layouts_multi: empty table");
-  hipLaunchKernelGGL(wlayout_multi_k, dim3(total_blocks), dim3(NT), 0, stream, tab_dev, n);
+  hipLaunchKernelGGL(wlayout_multi_k, dim3(total_blocks), dim3(NT), 0, stream, tab_dev, n,
+                     (const float* const*)nullptr);
   TMR_CHECK_LAUNCH("weight_layouts_multi");
+  return 0;
+}
+
+TMR_API int tmr_weight_layouts_multi_scaled(const tmr_wlayout* tab_dev, const float* const* scales_dev,
+                                            int n, int total_blocks, hipStream_t stream) {
+  TMR_CHECK_ARG(tab_dev && scales_dev && n > 0 && total_blocks > 0,
+                "tmr_weight_layouts_multi_scaled: empty table");
+  hipLaunchKernelGGL(wlayout_multi_k, dim3(total_blocks), dim3(NT), 0, stream, tab_dev, n,
+                     scales_dev);
+  TMR_CHECK_LAUNCH("weight_layouts_multi_scaled");
   return 0;
 }
 

@@ -663,8 +663,9 @@ def col_sum(x, rows, cols, ld, out=None, beta=0.0):
 class _LayoutRecord:
     def __init__(self, owner):
         self.lookup = {}     # request key -> returned tensor
-        self.rows = []       # table rows (w ptr, out tensor, k, c, rs, cpad, kind, bf16)
+        self.rows = []       # table rows (w ptr, out tensor, k, c, rs, cpad, kind, bf16[, scale])
         self.table = None    # device table (uint8 bytes of _WL_DTYPE rows)
+        self.scales = None   # device pointers of the rows' scale tensors (a frozen-BN session)
         self.blocks = 0
         self.valid = True
         # the owner's parameters at recording time: (weakref, data_ptr)
@@ -730,6 +731,9 @@ def layout_session(owner, key):
     recording = rec is None or not rec.valid or rec.table is None or not rec.live()
     if recording:
         rec = recs[key] = _LayoutRecord(owner)
+    elif rec.scales is not None:
+        call("tmr_weight_layouts_multi_scaled", rec.table, rec.scales, len(rec.rows), rec.blocks,
+             stream_ptr())
     else:
         call("tmr_weight_layouts_multi", rec.table, len(rec.rows), rec.blocks, stream_ptr())
     st = _session()
@@ -743,12 +747,16 @@ def layout_session(owner, key):
             epb = int(query("tmr_weight_layouts_epb"))
             tab = np.zeros(len(rec.rows), dtype=_WL_DTYPE)
             b0 = 0
-            for j, (wp, out, k, c, rs, cpad, kind, b16) in enumerate(rec.rows):
+            for j, (wp, out, k, c, rs, cpad, kind, b16) in enumerate(r[:8] for r in rec.rows):
                 n = out.numel()
                 tab[j] = (wp, out.data_ptr(), n, b0, k, c, rs, cpad, kind, b16)
                 b0 += (n + epb - 1) // epb
             rec.table = torch.from_numpy(tab.view(np.uint8).copy()).to(rec.rows[0][1].device)
             rec.blocks = b0
+            # (scaled rows: the frozen-BN step's dgrad weights, weight_to_crsk_scaled)
+            sp = [r[8].data_ptr() if len(r) > 8 else 0 for r in rec.rows]
+            if any(sp):
+                rec.scales = torch.tensor(sp, dtype=torch.int64).to(rec.rows[0][1].device)
 
 
 def _layout(key, convert, rows):
@@ -796,6 +804,31 @@ def weight_to_crsk(w, bf16=True):
         return out
     return _layout((w.data_ptr(), "crsk", k, c, r * s, c, int(bf16)), convert,
                    lambda out: [(w.data_ptr(), out, k, c, r * s, c, 1, int(bf16))])
+
+
+def weight_to_crsk_scaled(w, scale):
+    """weight_to_crsk(w, bf16=False) times scale[k] per output channel -> (Cin, R, S, Cout) fp32:
+    the dgrad operand of a frozen-BN unit, whose dy = g*scale is folded into the weights.  The
+    session refreshes it from the current w and scale (the same `scale` tensor every step: the
+    trunk's coefficient buffer) in its one launch."""
+    k, c, r, s = w.shape
+    _req(w, "w"); _req(scale, "scale")
+    if scale.numel() != k:
+        raise RuntimeError("weight_to_crsk_scaled: %d scales for %d output channels"
+                           % (scale.numel(), k))
+
+    def convert():
+        out = _empty((c, r, s, k), w)
+        epb = int(query("tmr_weight_layouts_epb"))
+        tab = np.zeros(1, dtype=_WL_DTYPE)
+        tab[0] = (w.data_ptr(), out.data_ptr(), out.numel(), 0, k, c, r * s, c, 1, 0)
+        tab = torch.from_numpy(tab.view(np.uint8).copy()).to(w.device)
+        sp = torch.tensor([scale.data_ptr()], dtype=torch.int64).to(w.device)
+        call("tmr_weight_layouts_multi_scaled", tab, sp, 1, (out.numel() + epb - 1) // epb,
+             stream_ptr())
+        return out
+    return _layout((w.data_ptr(), "crsk_s", k, c, r * s, c, scale.data_ptr()), convert,
+                   lambda out: [(w.data_ptr(), out, k, c, r * s, c, 1, 0, scale)])
 
 
 def weight_to_crsk_grouped(w, groups, bf16=True):
@@ -1048,6 +1081,147 @@ def bn_bwd(dz, y, z, mean, inv, gamma, relu, want_dres=False, dres_out=None, sca
     call("tmr_bn_bwd_x", dz, y, z if relu else None, scale, shift, mean, inv, gamma, dy, dres,
          dgamma, dbeta, rows, c, int(relu), ws, ctypes.c_size_t(nb), int(bf16), stream_ptr())
     return dy, dres, dgamma, dbeta
+
+
+# ------------------------------------------------------- frozen batch norm
+_FROZEN_DTYPE = np.dtype([("gamma", "<u8"), ("beta", "<u8"), ("mean", "<u8"), ("var", "<u8"),
+                          ("scale", "<u8"), ("shift", "<u8"), ("inv", "<u8"), ("c", "<i4"),
+                          ("eps", "<f4")])   # include/tmr.h tmr_bn_frozen_entry (64 bytes)
+
+
+def bn_frozen_table(bns):
+    """The device table and coefficient buffer of tmr_bn_frozen_params for a list of BatchNorm2d
+    modules -> (table, buf, views): buf one fp32 tensor of 3 * sum(c), views[i] = (scale, shift,
+    inv) of bns[i].  The table holds the modules' parameter and buffer addresses: rebuild it when
+    any of them moves."""
+    dev = bns[0].running_mean.device
+    total = sum(bn.num_features for bn in bns)
+    buf = torch.empty((3 * total,), dtype=f32, device=dev)
+    tab = np.zeros(len(bns), dtype=_FROZEN_DTYPE)
+    views, off = [], 0
+    for i, bn in enumerate(bns):
+        c = bn.num_features
+        for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+            _req(t, "BatchNorm tensor")
+        if c % 4:   # (keeps every view 16-B aligned)
+            raise RuntimeError("bn_frozen_table: channels %d must be a multiple of 4" % c)
+        v = tuple(buf[off + j * c: off + (j + 1) * c] for j in range(3))
+        off += 3 * c
+        tab[i] = (bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                  bn.running_var.data_ptr(), v[0].data_ptr(), v[1].data_ptr(), v[2].data_ptr(),
+                  c, bn.eps)
+        views.append(v)
+    return torch.from_numpy(tab.view(np.uint8).copy()).to(dev), buf, views
+
+
+def bn_frozen_params(table, n):
+    """scale, shift and inv of every BatchNorm of a bn_frozen_table in one launch."""
+    call("tmr_bn_frozen_params", table, int(n), stream_ptr())
+
+
+def _frozen_mask(mask, z, bits, y):
+    if mask == 1:
+        _req(z, "z")
+        if z.shape != y.shape:
+            raise RuntimeError("bn_frozen_bwd: z shape %s != %s" % (tuple(z.shape), tuple(y.shape)))
+        return z
+    if mask == 3:
+        if bits is None or bits.dtype != torch.int32 or bits.numel() * 32 < y.numel():
+            raise RuntimeError("bn_frozen_bwd: mask 3 takes the int32 ReLU-mask bits of y's shape")
+        return bits
+    if mask not in (0, 2):
+        raise RuntimeError("bn_frozen_bwd: bad mask %r" % (mask,))
+    return None
+
+
+def bn_frozen_bwd(g, y, scale, shift, mean, mask, z=None, bits=None, want_dy=True,
+                  dres_inplace=False, want_sums=True):
+    """Frozen-BN backward of one unit in one pass (tmr_bn_frozen_bwd) -> (dy, parts, nparts).
+    mask 0: g already masked; 1: z > 0; 2: fmaf(y, scale, shift) > 0; 3: the ReLU-mask bits.
+    dres_inplace: the masked gradient overwrites g (the identity branch's gradient).
+    want_dy=False: no dy (the caller folds the scale into its conv operands); want_sums=False:
+    no partials (affine=False), parts is None.  bn_frozen_finalize turns parts into dgamma, dbeta."""
+    _req(g, "g"); _req(y, "y")
+    if g.shape != y.shape:
+        raise RuntimeError("bn_frozen_bwd: g shape %s != y %s" % (tuple(g.shape), tuple(y.shape)))
+    c = y.shape[-1]
+    rows = y.numel() // c
+    zm = _frozen_mask(mask, z, bits, y)
+    dy = torch.empty_like(y) if want_dy else None
+    parts, nparts = None, 0
+    if want_sums:
+        nparts = query("tmr_bn_frozen_bwd_parts", rows, c)
+        parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
+    call("tmr_bn_frozen_bwd", g, zm, int(mask), y, scale, shift, mean, dy,
+         g if dres_inplace else None, parts,
+         ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), rows, c, int(want_sums),
+         stream_ptr())
+    return dy, parts, nparts
+
+
+def bn_frozen_bwd_ds(g, y, scale, shift, mean, yd, scale_d, mean_d, mask, z=None, bits=None,
+                     want_dy=True, dres_inplace=False, want_sums=True):
+    """bn_frozen_bwd for a downsample block's bn3 (y) and downsample BN (y_ds), which share g, in
+    one read of g (tmr_bn_frozen_bwd_ds) -> (dy, dy_ds, parts, parts_ds, nparts)."""
+    _req(g, "g"); _req(y, "y"); _req(yd, "y_ds")
+    if not (g.shape == y.shape == yd.shape):
+        raise RuntimeError("bn_frozen_bwd_ds: g, y and y_ds must have one shape")
+    c = y.shape[-1]
+    rows = y.numel() // c
+    zm = _frozen_mask(mask, z, bits, y)
+    dy = torch.empty_like(y) if want_dy else None
+    dyd = torch.empty_like(yd) if want_dy else None
+    parts = parts_d = None
+    nparts = 0
+    if want_sums:
+        nparts = query("tmr_bn_frozen_bwd_parts", rows, c)
+        parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
+        parts_d = torch.empty_like(parts)
+    call("tmr_bn_frozen_bwd_ds", g, zm, int(mask), y, scale, shift, mean, dy, yd, scale_d, mean_d,
+         dyd, g if dres_inplace else None, parts, parts_d,
+         ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), rows, c, int(want_sums),
+         stream_ptr())
+    return dy, dyd, parts, parts_d, nparts
+
+
+def bn_frozen_bwd_maxpool(dyp, am, y, scale, shift, mean, want_sums=True):
+    """The stem's frozen-BN backward: MaxPool2d(3,2,1) backward (gathered from the pooled gradient
+    and argmax), the ReLU mask from fmaf(y, scale, shift), dy = g*scale and the partial sums in
+    one pass (tmr_bn_frozen_bwd_maxpool) -> (dy, parts, nparts)."""
+    _req(dyp, "dyp"); _req(y, "y"); _req(am, "argmax", torch.uint8)
+    n, h, w, c = y.shape
+    _, ho, wo, _ = dyp.shape
+    dy = torch.empty_like(y)
+    parts, nparts = None, 0
+    if want_sums:
+        nparts = query("tmr_bn_frozen_bwd_maxpool_parts", n, h, w, c)
+        parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
+    call("tmr_bn_frozen_bwd_maxpool", dyp, am, n, h, w, ho, wo, y, scale, shift, mean, dy, parts,
+         ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), c, int(want_sums), stream_ptr())
+    return dy, parts, nparts
+
+
+def bn_frozen_finalize(parts, nparts, inv):
+    """(sum g, sum g*(y - mean)) partials -- bn_frozen_bwd*'s or conv_dgrad_bnbwd's -- ->
+    (dgamma = inv * sum g*(y - mean), dbeta = sum g) (tmr_bn_frozen_finalize)."""
+    c = inv.numel()
+    nb = query("tmr_bn_parts_ws_bytes", int(nparts), c)
+    ws = torch.empty(((nb + 7) // 8,), dtype=torch.float64, device=inv.device)
+    dgamma = _empty((c,), inv); dbeta = _empty((c,), inv)
+    call("tmr_bn_frozen_finalize", parts, int(nparts), c, inv, dgamma, dbeta, ws,
+         ctypes.c_size_t(ws.numel() * 8), stream_ptr())
+    return dgamma, dbeta
+
+
+def scale_rows(w, scale):
+    """w[k] *= scale[k] in place over the leading dimension (tmr_scale_rows): dW of a frozen-BN
+    unit whose wgrad ran on the masked gradient g instead of dy = g*scale."""
+    _req(w, "w"); _req(scale, "scale")
+    k = w.shape[0]
+    if scale.numel() != k:
+        raise RuntimeError("scale_rows: %d scales for %d rows" % (scale.numel(), k))
+    call("tmr_scale_rows", w, scale, k, ctypes.c_long(w.numel() // k), stream_ptr())
+    return w
 
 
 # ------------------------------------------------------------------- pooling

@@ -236,7 +236,7 @@ def _infer16(share):
 
 def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None, math="fp32",
              defer=False, branch=None, nbt=None, dual=False, groups=1, y16=False, bwd16=False,
-             x16=None):
+             x16=None, frozen=None, fold=False):
     """conv (NHWC implicit GEMM) -> BN -> (+residual) -> (ReLU); returns z.
 
     Train mode only: ``defer`` returns (y, scale, shift) instead of applying the BN -- the
@@ -248,8 +248,16 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
     (eval mode, bf16 activations: the shares' infer_act16): x and residual bf16, z rounded once
     to bf16.  ``bwd16`` (train mode with recs, math "fp32": the BWD16 step): the forward of
     math "fp32", returning (z fp32, z bf16 copy) unless deferred, and a record for a bf16-math
-    backward -- ``x16`` the bf16 copy of x (None: the stem's NHWC4 input), the bf16 CRSK weights."""
+    backward -- ``x16`` the bf16 copy of x (None: the stem's NHWC4 input), the bf16 CRSK weights.
+    ``frozen`` (train mode, math "fp32": the frozen-BN step, _frozen_coefs): this BN's (scale,
+    shift, inv) of the running statistics -- the conv stores y without a statistics epilogue and
+    the apply forms below take the eval coefficients; ``fold``: the unit's masked gradient will
+    come from a fused dgrad, so its own dgrad reads CRSK weights pre-scaled by scale[k]
+    (dy = g*scale is never formed)."""
     w = conv.weight
+    if frozen is not None and not (training and math == "fp32" and groups == 1 and not dual
+                                   and not y16 and not bwd16):
+        raise RuntimeError("frozen BatchNorm is the train-mode fp32 step of an ungrouped conv")
     k, c, r, s = w.shape
     if bwd16 and not (training and recs is not None and math == "fp32" and groups == 1
                       and not dual and not y16):
@@ -264,7 +272,12 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
     if groups > 1 and not training and not y16:
         raise RuntimeError("grouped convs run in the train-mode trunk and the bf16-activation "
                            "inference trunk (y16) only")
-    if training:
+    if training and frozen is not None:
+        # no statistics: the running ones, through the coefficients of the step's one launch
+        y = ops.conv_fwd(x, wk, stride, pad, c_real=c, math=math)
+        scale, shift, inv = frozen
+        mean = bn.running_mean
+    elif training:
         # batch statistics come out of the conv epilogue (no separate pass over y)
         y, stats, nparts = ops.conv_fwd_bnstats(x, wk, stride, pad, c_real=c * groups, math=math,
                                                 y16=_act16(math), groups=groups)
@@ -319,6 +332,8 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
         # the dgrad view of a bf16-operand conv reads the transposed weights (LDS-DMA engine)
         if bwd16:   # (the stem's 3 input channels: no dgrad)
             wt = ops.weight_to_crsk(w.detach().contiguous()) if c % 8 == 0 else None
+        elif frozen is not None and fold:
+            wt = ops.weight_to_crsk_scaled(w.detach().contiguous(), scale)
         elif groups > 1 and ((_full16(math) and x.dtype == torch.bfloat16) or _dma32(math)):
             wt = ops.weight_to_crsk_grouped(w.detach().contiguous(), groups,
                                             bf16=x.dtype == torch.bfloat16)
@@ -334,7 +349,7 @@ def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None,
                      "scale": scale, "shift": shift, "mean": mean, "inv": inv,
                      "stride": stride, "pad": pad, "relu": relu, "conv": conv, "bn": bn,
                      "c_real": c, "math": "bf16" if bwd16 else math, "groups": groups,
-                     "res": has_res, "dy16": bwd16})
+                     "res": has_res, "dy16": bwd16, "fold": bool(frozen is not None and fold)})
     if defer:
         return y, scale, shift
     return (z, z16) if bwd16 else z
@@ -443,18 +458,93 @@ def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need
     return dx, dres, fused
 
 
+# ------------------------------------------------------------------ frozen BatchNorm
+# share -> (signature, table, buffer, {bn: (scale, shift, inv)}): the device table of
+# tmr_bn_frozen_params and the coefficient buffer it fills, rebuilt when a BN tensor moves
+_FROZEN = weakref.WeakKeyDictionary()
+
+
+def _share_bns(share):
+    return [m for m in share.modules() if isinstance(m, nn.BatchNorm2d)]
+
+
+def _bn_modes(share):
+    """The BN modules' common mode -> "train" / "eval"; a share whose BN modules disagree, or
+    whose bn_frozen flag a BN in train mode contradicts, raises."""
+    modes = {m.training for m in _share_bns(share)}
+    if len(modes) > 1:
+        raise RuntimeError("the trunk's BatchNorm modules disagree (some in eval mode, some in "
+                           "train mode): use tmrnet_amd.freeze_bn / unfreeze_bn on the whole trunk")
+    if getattr(share, "bn_frozen", False) and True in modes:
+        raise RuntimeError("bn_frozen is set but the trunk's BatchNorm modules are in train mode: "
+                           "call tmrnet_amd.freeze_bn again, or unfreeze_bn")
+    return "train" if True in modes else "eval"
+
+
+def _frozen_step(share):
+    """The frozen-BN train step applies: bn_frozen on a train-mode fp32 ResNet-50 share."""
+    return bool(getattr(share, "bn_frozen", False) and share.training
+                and share.precision == "fp32")
+
+
+def _frozen_coefs(share):
+    """{bn: (scale, shift, inv)} of every BN of the share, computed by ONE launch from the current
+    weight / bias / running statistics (ops.bn_frozen_params)."""
+    bns = _share_bns(share)
+    sig = tuple(t.data_ptr() for bn in bns
+                for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
+    ent = _FROZEN.get(share)
+    if ent is None or ent[0] != sig:
+        table, buf, views = ops.bn_frozen_table(bns)
+        ent = _FROZEN[share] = (sig, table, buf, dict(zip(bns, views)))
+    ops.bn_frozen_params(ent[1], len(bns))
+    return ent[3]
+
+
+def _bn_wants_grad(bn):
+    return bn.weight.requires_grad or bn.bias.requires_grad
+
+
+def _frozen_affine(rec, parts, grads):
+    """dgamma / dbeta of a frozen unit from partial sums (its own pass's, or a fused dgrad's)."""
+    if parts is not None and _bn_wants_grad(rec["bn"]):
+        grads[rec["bn"].weight], grads[rec["bn"].bias] = ops.bn_frozen_finalize(
+            parts[0], parts[1], rec["inv"])
+
+
+def _frozen_unit_bwd(rec, g, grads, dy=None, parts=None, **kw):
+    """wgrad and dgrad of one frozen-BN unit.  dy: its real output gradient g*scale (a unit of the
+    single-pass kernels).  Otherwise g is the masked gradient from a fused dgrad (`parts` its
+    partial sums -> the BN gradients): the wgrad runs on g and dW's rows take scale[k], the dgrad
+    reads the pre-scaled CRSK weights (rec["fold"]) -- no elementwise pass forms dy."""
+    _frozen_affine(rec, parts, grads)
+    if dy is not None:
+        if rec["fold"]:
+            raise RuntimeError("frozen BN: a real dy meets pre-scaled dgrad weights")
+        return _conv_bn_bwd(rec, None, grads, dy=dy, **kw)
+    if not rec["fold"] and kw.get("need_dx", True):
+        raise RuntimeError("frozen BN: a folded unit needs its pre-scaled dgrad weights")
+    out = _conv_bn_bwd(rec, None, grads, dy=g, **kw)
+    ops.scale_rows(grads[rec["conv"].weight], rec["scale"])
+    return out
+
+
 class TrunkFn(torch.autograd.Function):
     """Whole ResNet-50 trunk as one autograd node: x NHWC4 (F,224,224,4) -> (F,2048)."""
 
     @staticmethod
     def forward(ctx, x4, share, keep, *params):
+        _bn_modes(share)
+        # the frozen-BN step: every BN's coefficients in one launch, before the layout session's
+        # launch scales the dgrad weights by them (a session of its own: it holds those copies)
+        fz = _frozen_coefs(share) if _frozen_step(share) else None
         # every conv weight layout of the step in one launch (ops.layout_session)
-        with ops.layout_session(share, ("resnet50", share.training, bool(keep),
-                                 share.precision, _infer16(share))):
-            return TrunkFn._forward(ctx, x4, share, keep, params)
+        key = ("resnet50", share.training, bool(keep), share.precision, _infer16(share))
+        with ops.layout_session(share, key + ("frozen",) if fz is not None else key):
+            return TrunkFn._forward(ctx, x4, share, keep, params, fz)
 
     @staticmethod
-    def _forward(ctx, x4, share, keep, params):
+    def _forward(ctx, x4, share, keep, params, fz=None):
         training = share.training
         keep = keep and training
         recs = [] if keep else None
@@ -477,7 +567,8 @@ class TrunkFn(torch.autograd.Function):
             # share.bn1 + relu applied inside the maxpool (the backward recomputes the ReLU
             # mask from y, so the stem's BN output is never needed)
             y0, sc0, sh0 = _conv_bn(xs, conv1, bn1, 2, 3, True, training, recs=recs, math=mt,
-                                    defer=True, nbt=nbt, bwd16=bw)
+                                    defer=True, nbt=nbt, bwd16=bw,
+                                    frozen=fz[bn1] if fz is not None else None)
             if bw:
                 p, h16, am = ops.maxpool_fwd_bn_dual(y0, sc0, sh0)
             else:
@@ -503,33 +594,42 @@ class TrunkFn(torch.autograd.Function):
             h16 = None   # (bw: the bf16 copy of the block input, the wgrads' operand)
         z1h = z2h = None
         blocks = []
+        last = layers[-1][-1]
+
+        def fzk(bn, blk=None):
+            # the frozen step's coefficients; every unit but the last block's bn3 / downsample BN
+            # (whose g arrives unmasked) folds its dy scale into its dgrad weights
+            if fz is None:
+                return {}
+            return {"frozen": fz[bn], "fold": blk is not last}
         for layer in layers:
             for blk in layer:
                 brec = [] if keep else None
                 z1 = _conv_bn(hx, blk.conv1, blk.bn1, 1, 0, True, training, recs=brec, math=mt,
-                              nbt=nbt, y16=i16, bwd16=bw, x16=h16)
+                              nbt=nbt, y16=i16, bwd16=bw, x16=h16, **fzk(blk.bn1))
                 if bw:
                     z1, z1h = z1
                 z2 = _conv_bn(z1, blk.conv2, blk.bn2, blk.stride, 1, True, training, recs=brec,
-                              math=mt, nbt=nbt, y16=i16, bwd16=bw, x16=z1h)
+                              math=mt, nbt=nbt, y16=i16, bwd16=bw, x16=z1h, **fzk(blk.bn2))
                 if bw:
                     z2, z2h = z2
                 if blk.downsample is not None:
                     # train: the branch's BN is applied inside the BN3 pass (bn_apply2)
                     idn = _conv_bn(hx, blk.downsample[0], blk.downsample[1], blk.stride, 0, False,
                                    training, recs=brec, math=mt, defer=training, nbt=nbt,
-                                   y16=i16, bwd16=bw, x16=h16)
+                                   y16=i16, bwd16=bw, x16=h16, **fzk(blk.downsample[1], blk))
                 else:
                     if h is None:
                         raise RuntimeError("identity residual of the stem output (no downsample)")
                     idn = h
                 if isinstance(idn, tuple):
                     h = _conv_bn(z2, blk.conv3, blk.bn3, 1, 0, True, training, branch=idn,
-                                 recs=brec, math=mt, nbt=nbt, dual=f16, bwd16=bw, x16=z2h)
+                                 recs=brec, math=mt, nbt=nbt, dual=f16, bwd16=bw, x16=z2h,
+                                 **fzk(blk.bn3, blk))
                 else:
                     h = _conv_bn(z2, blk.conv3, blk.bn3, 1, 0, True, training, residual=idn,
                                  recs=brec, math=mt, nbt=nbt, dual=f16, y16=i16, bwd16=bw,
-                                 x16=z2h)
+                                 x16=z2h, **fzk(blk.bn3, blk))
                 if bw:
                     h, h16 = h
                     hx = h
@@ -540,8 +640,10 @@ class TrunkFn(torch.autograd.Function):
                     h, hx = h if f16 else (h, h)
                 blocks.append((blk, brec))
         feat = ops.avgpool_fwd(h)
-        ops.counters_add_one(nbt)
+        if nbt:   # (none under frozen BN: no counter moves)
+            ops.counters_add_one(nbt)
         ctx.keep = keep
+        ctx.frozen = fz is not None
         if keep:
             ctx.share = share
             ctx.params = params
@@ -555,6 +657,8 @@ class TrunkFn(torch.autograd.Function):
     def backward(ctx, dfeat):
         if not ctx.keep:
             raise RuntimeError("trunk backward needs train mode and a forward with grad enabled")
+        if ctx.frozen:
+            return TrunkFn._backward_frozen(ctx, dfeat)
         grads = {}
         g = ops.avgpool_bwd(dfeat.contiguous(), ctx.last_hw)   # grad at the last block output
         blocks = ctx.blocks
@@ -623,6 +727,78 @@ class TrunkFn(torch.autograd.Function):
         ctx.blocks = ctx.stem = None
         return (None, None, None) + tuple(out)
 
+    @staticmethod
+    def _backward_frozen(ctx, dfeat):
+        """The frozen-BN step's backward: no BN-backward projection anywhere.  The last block's
+        bn3 (g unmasked from the avgpool) and the stem (g through the maxpool) take one pass of
+        tmr_bn_frozen_bwd / _maxpool; every other unit's g comes masked, with its partial sums,
+        from the fused dgrad that produced it, and its dy = g*scale lives in the conv operands
+        (_frozen_unit_bwd).  A downsample BN needs sum g*(y_ds - mean_ds) of its own: one
+        sums-only pass over (g, y_ds), skipped with affine=False."""
+        grads = {}
+        g = ops.avgpool_bwd(dfeat.contiguous(), ctx.last_hw)   # grad at the last block output
+        blocks = ctx.blocks
+        pending = None     # the fused dgrad's partial sums of g (None: g is unmasked)
+        ready = get_grad_ready(ctx.share)   # ddp.GradAllReduce.grads_ready, or None
+        while blocks:
+            blk, brec = blocks.pop()
+            has_ds = blk.downsample is not None
+            r1, r2 = brec[0], brec[1]
+            rd = brec[2] if has_ds else None
+            r3 = brec[-1]
+            prev3 = blocks[-1][1][-1] if blocks else None
+            dy3 = dyd = None
+            if pending is None:
+                # g unmasked: mask (the block output's bits), dres in place, dy's and sums at once
+                s3 = _bn_wants_grad(r3["bn"])
+                mk = dict(mask=3, bits=r3["zbits"]) if r3.get("zbits") is not None else \
+                    dict(mask=1, z=r3["z"])
+                if has_ds:
+                    sums = s3 or _bn_wants_grad(rd["bn"])
+                    dy3, dyd, p3, pd, npp = ops.bn_frozen_bwd_ds(
+                        g, r3["y"], r3["scale"], r3["shift"], r3["mean"], rd["y"], rd["scale"],
+                        rd["mean"], dres_inplace=True, want_sums=sums, **mk)
+                    _frozen_affine(r3, (p3, npp) if sums else None, grads)
+                    _frozen_affine(rd, (pd, npp) if sums else None, grads)
+                else:
+                    dy3, p3, npp = ops.bn_frozen_bwd(g, r3["y"], r3["scale"], r3["shift"],
+                                                     r3["mean"], dres_inplace=True, want_sums=s3,
+                                                     **mk)
+                    _frozen_affine(r3, (p3, npp) if s3 else None, grads)
+                dz2, _, fz2 = _frozen_unit_bwd(r3, None, grads, dy=dy3, fuse_prev=r2)
+                del dy3
+            else:
+                if has_ds and _bn_wants_grad(rd["bn"]):
+                    _, pd, npp = ops.bn_frozen_bwd(g, rd["y"], rd["scale"], rd["shift"],
+                                                   rd["mean"], mask=0, want_dy=False)
+                    _frozen_affine(rd, (pd, npp), grads)
+                dz2, _, fz2 = _frozen_unit_bwd(r3, g, grads, parts=pending, fuse_prev=r2)
+            dres = g   # masked: the identity branch's gradient
+            dz1, _, fz1 = _frozen_unit_bwd(r2, dz2, grads, parts=fz2, fuse_prev=r1)
+            del dz2
+            if has_ds:
+                dx, _, _ = _frozen_unit_bwd(rd, dres, grads, dy=dyd)
+                del dyd
+                dx, _, pending = _frozen_unit_bwd(r1, dz1, grads, parts=fz1, dx_out=dx,
+                                                  dx_beta=1.0, fuse_prev=prev3)
+            else:
+                dx, _, pending = _frozen_unit_bwd(r1, dz1, grads, parts=fz1, dx_out=dres,
+                                                  dx_beta=1.0, fuse_prev=prev3)
+            del dz1, brec, dres
+            g = dx
+            if ready is not None:   # this block's parameter grads are final: start their exchange
+                ready([(p, grads[p]) for p in blk.parameters() if p in grads])
+        am, stem_hw = ctx.pool
+        st = ctx.stem[0]
+        ss = _bn_wants_grad(st["bn"])
+        dy0, p0, np0 = ops.bn_frozen_bwd_maxpool(g, am, st["y"], st["scale"], st["shift"],
+                                                 st["mean"], want_sums=ss)
+        _frozen_affine(st, (p0, np0) if ss else None, grads)
+        _frozen_unit_bwd(st, None, grads, dy=dy0, need_dx=False)
+        out = [grads.get(p) for p in ctx.params]
+        ctx.blocks = ctx.stem = None
+        return (None, None, None) + tuple(out)
+
 
 _CHILD_NAMES = ("conv1", "bn1", "relu", "maxpool", "layer1", "layer2", "layer3", "layer4",
                 "avgpool")
@@ -646,6 +822,9 @@ class ResNet50Share(nn.Sequential):
         # eval mode under precision "bf16", opt-in: bf16 activations (TrunkFn._forward i16; the
         # default keeps every eval path's fp32 activations and bits)
         self.infer_act16 = False
+        # frozen BatchNorm (tmrnet_amd.freeze_bn): the BN modules stay in eval mode whatever
+        # train(mode) says, and a train-mode step runs on the running statistics
+        self.bn_frozen = False
         mods = (nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False), nn.BatchNorm2d(64),
                 nn.ReLU(inplace=True), nn.MaxPool2d(3, stride=2, padding=1),
                 _make_layer(64, 64, 3, 1), _make_layer(256, 128, 4, 2),
@@ -665,6 +844,13 @@ class ResNet50Share(nn.Sequential):
         ch = list(self.children())
         return ch[0], ch[1], ch[4:8]
 
+    def train(self, mode=True):
+        super().train(mode)
+        if getattr(self, "bn_frozen", False):
+            for m in _share_bns(self):
+                m.training = False
+        return self
+
     def features_nhwc4(self, x4):
         """x4: (F,224,224,4) fp32 NHWC, 4th channel zero -> (F,2048)."""
         params = list(self.parameters())
@@ -682,3 +868,53 @@ class ResNet50Share(nn.Sequential):
 
 def resnet50_share():
     return ResNet50Share()
+
+
+def _share_of(model):
+    """The trunk of a package model: the model itself, its `share` or its `res`."""
+    from .resnest import ResNeSt50Share
+    kinds = (ResNet50Share, ResNeSt50Share)
+    if isinstance(model, kinds):
+        return model
+    for name in ("share", "res"):
+        m = getattr(model, name, None)
+        if isinstance(m, kinds):
+            return m
+    raise TypeError("freeze_bn / unfreeze_bn take a ResNet50Share or a package model that holds "
+                    "one as .share or .res, got %s" % type(model).__name__)
+
+
+def freeze_bn(model_or_share, affine=True):
+    """Freeze the trunk's BatchNorm: every BatchNorm2d of the share goes to eval mode and stays
+    there through train() / eval() (share.bn_frozen = True); a train-mode step then normalises
+    with the running statistics, writes none of them, and back-propagates dy = g*scale.
+    affine=False also stops training the BN weights and biases (requires_grad=False;
+    torchvision's FrozenBatchNorm2d).  ResNet-50 shares of precision "fp32" only.  Call it after
+    load_checkpoint and before the optimizer is built.  Returns its argument."""
+    from .resnest import ResNeSt50Share
+    share = _share_of(model_or_share)
+    if isinstance(share, ResNeSt50Share):
+        raise ValueError("freeze_bn: frozen BatchNorm exists for the ResNet-50 trunk "
+                         "(precision 'fp32') only, not for a ResNeSt-50 share")
+    if share.precision != "fp32":
+        raise ValueError("freeze_bn: frozen BatchNorm exists for precision 'fp32' only, not for "
+                         "%r" % (share.precision,))
+    share.bn_frozen = True
+    for m in _share_bns(share):
+        m.training = False
+        if not affine:
+            m.weight.requires_grad_(False)
+            m.bias.requires_grad_(False)
+    return model_or_share
+
+
+def unfreeze_bn(model_or_share):
+    """Undo freeze_bn: clear share.bn_frozen, put the BatchNorm modules back to share.training
+    and their weights and biases back to requires_grad=True.  Returns its argument."""
+    share = _share_of(model_or_share)
+    share.bn_frozen = False
+    for m in _share_bns(share):
+        m.training = share.training
+        m.weight.requires_grad_(True)
+        m.bias.requires_grad_(True)
+    return model_or_share
