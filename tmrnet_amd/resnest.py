@@ -43,8 +43,10 @@ import math
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, trunk
 from ._lib import call, stream_ptr
+from .trunk import (_TrainUnits, _act16, _backward_blocks, _backward_head, _backward_tail,
+                    _conv_bn_eval, _conv_bwd, _infer16, _unit_bwd, _unit_dy)
 
 
 def _bn_train_or_eval(y, bn, training):
@@ -279,33 +281,30 @@ class ResNeStTrunkFn(torch.autograd.Function):
 
     @staticmethod
     def _forward(ctx, x4, share, keep, params):
-        from .trunk import _conv_bn, _act16
         mt = share.precision
         a16 = _act16(mt)
-        nbt = []
-        stem = []
+        # (records are built whatever `keep` says: the units' apply forms do not follow grad mode)
+        st = _TrainUnits(mt, True)
         c = share.conv1
         # the stem input: under bf16 activations the NHWC4 fp32 frames themselves for the direct
         # 3x3/2 stem conv (direct3.hip: rounded to bf16 as it is staged), or an NHWC8 bf16 copy
         # for the LDS-DMA engine (ops.engine_only, tests: its 8-channel pieces)
         xs = ops.nhwc4_to_bf16x8(x4) if (a16 and ops.engine_forced()) else x4
-        z = _conv_bn(xs, c[0], c[1], 2, 1, True, True, recs=stem, math=mt, nbt=nbt)
-        z = _conv_bn(z, c[3], c[4], 1, 1, True, True, recs=stem, math=mt, nbt=nbt)
+        z, _, s0 = st.unit(xs, c[0], c[1], 2, 1, True)
+        z, _, s1 = st.unit(z, c[3], c[4], 1, 1, True)
         # share.bn1 + relu applied inside the maxpool (its backward recomputes the mask from y)
-        y0, sc0, sh0 = _conv_bn(z, c[6], share.bn1, 1, 1, True, True, recs=stem, math=mt,
-                                defer=True, nbt=nbt)
+        (y0, sc0, sh0), s2 = st.deferred(z, c[6], share.bn1, 1, 1, True)
         h, am = ops.maxpool_fwd_bn(y0, sc0, sh0)
         stem_hw = (y0.shape[1], y0.shape[2])
         blocks = []
         for layer in (share.layer1, share.layer2, share.layer3, share.layer4):
             for blk in layer:
-                rec = {"blk": blk, "in_hw": (h.shape[1], h.shape[2])}
-                r1, r2, r3, rd = [], [], [], []
-                z1 = _conv_bn(h, blk.conv1, blk.bn1, 1, 0, True, True, recs=r1, math=mt, nbt=nbt)
+                rec = {"in_hw": (h.shape[1], h.shape[2]), "rd": None}
+                z1, _, rec["r1"] = st.unit(h, blk.conv1, blk.bn1, 1, 0, True)
                 sp = blk.conv2
-                y2, sc2, sh2 = _conv_bn(z1, sp.conv, sp.bn0, sp.stride, 1, True, True, recs=r2,
-                                        math=mt, defer=True, nbt=nbt, groups=sp.radix)
-                out, spl = _splat_fwd(sp, y2, sc2, sh2, nbt)
+                (y2, sc2, sh2), rec["r2"] = st.deferred(z1, sp.conv, sp.bn0, sp.stride, 1, True,
+                                                        groups=sp.radix)
+                out, rec["spl"] = _splat_fwd(sp, y2, sc2, sh2, st.nbt)
                 if blk.avd:
                     rec["avd_hw"] = (out.shape[1], out.shape[2])
                     out = ops.avgpool2d_fwd(out, 3, blk.avd_stride, 1, True, False)
@@ -315,91 +314,69 @@ class ResNeStTrunkFn(torch.autograd.Function):
                     if pool.kernel_size != 1:
                         rec["pool"] = (pool.kernel_size, pool.stride)
                         xr = ops.avgpool2d_fwd(h, pool.kernel_size, pool.stride, 0, False, True)
-                    idn = _conv_bn(xr, dconv, dbn, 1, 0, False, True, recs=rd, math=mt, defer=True,
-                                   nbt=nbt)
-                    h = _conv_bn(out, blk.conv3, blk.bn3, 1, 0, True, True, branch=idn, recs=r3,
-                                 math=mt, nbt=nbt)
+                    idn, rec["rd"] = st.deferred(xr, dconv, dbn, 1, 0, False)
+                    h, _, rec["r3"] = st.unit(out, blk.conv3, blk.bn3, 1, 0, True, branch=idn)
                 else:
-                    h = _conv_bn(out, blk.conv3, blk.bn3, 1, 0, True, True, residual=h, recs=r3,
-                                 math=mt, nbt=nbt)
-                rec.update(r1=r1[0], r2=r2[0], r3=r3[0], rd=rd[0] if rd else None, spl=spl)
-                blocks.append(rec)
+                    h, _, rec["r3"] = st.unit(out, blk.conv3, blk.bn3, 1, 0, True, residual=h)
+                blocks.append((blk, rec))
         feat = ops.avgpool_fwd(h)
-        ops.counters_add_one(nbt)
+        ops.counters_add_one(st.nbt)
         ctx.keep = keep
         if keep:
             ctx.share, ctx.params = share, params
-            ctx.stem, ctx.pool, ctx.blocks = stem, (am, stem_hw), blocks
+            ctx.stem, ctx.pool, ctx.blocks = [s0, s1, s2], (am, stem_hw), blocks
             ctx.last_hw = (h.shape[1], h.shape[2])
         return feat
 
     @staticmethod
     def backward(ctx, dfeat):
-        from . import trunk
-        from .trunk import _conv_bn_bwd, get_grad_ready
-        if not ctx.keep:
-            raise RuntimeError("trunk backward needs train mode and a forward with grad enabled")
         grads = {}
-        g = ops.avgpool_bwd(dfeat.contiguous(), ctx.last_hw)   # grad at the last block output
-        blocks = ctx.blocks
+        g = _backward_head(ctx, dfeat)   # grad at the last block output
         pending = None     # BN-backward partials of g from the fused dgrad that produced it
-        ready = get_grad_ready(ctx.share)
-        while blocks:
-            rec = blocks.pop()
-            blk = rec["blk"]
-            prev3 = blocks[-1]["r3"] if blocks else None
+        for blk, rec, prev3 in _backward_blocks(ctx, grads, lambda rec: rec["r3"]):
             # bn3 (+ReLU) backward; g (owned) becomes the masked gradient = the residual branch's
-            r3, rd, dyd = rec["r3"], rec["rd"], None
+            r1, r2, r3, rd, dyd = rec["r1"], rec["r2"], rec["r3"], rec["rd"], None
             if rd is not None and pending is not None and trunk._ds_dual(g, r3, rd):
                 # bn3 and the downsample BN share g: one apply pass (trunk.DS_DUAL)
                 dy3, dg3, db3, dyd, dgd, dbd = ops.bn_bwd_parts_ds(
-                    g, r3["y"], pending[0], pending[1], r3["mean"], r3["inv"],
-                    r3["bn"].weight.detach(), rd["y"], rd["mean"], rd["inv"],
-                    rd["bn"].weight.detach())
-                grads[r3["bn"].weight], grads[r3["bn"].bias] = dg3, db3
-                grads[rd["bn"].weight], grads[rd["bn"].bias] = dgd, dbd
-                dout, _, _ = _conv_bn_bwd(r3, None, grads, dy=dy3)
+                    g, r3.y, pending[0], pending[1], r3.mean, r3.inv, r3.bn.weight.detach(),
+                    rd.y, rd.mean, rd.inv, rd.bn.weight.detach())
+                grads[r3.bn.weight], grads[r3.bn.bias] = dg3, db3
+                grads[rd.bn.weight], grads[rd.bn.bias] = dgd, dbd
                 dres = g
-                del dy3
             else:
-                dout, dres, _ = _conv_bn_bwd(r3, g, grads, want_dres=True, dres_inplace=True,
-                                             parts=pending)
+                dy3, _, dres = _unit_dy(r3, g, grads, parts=pending, want_dres=True,
+                                        dres_inplace=True)
+            dout, _ = _conv_bwd(r3, dy3, grads)
+            del dy3
             if blk.avd:
                 dout = ops.avgpool2d_bwd(dout, rec["avd_hw"], 3, blk.avd_stride, 1, True)
             # split attention + bn0 backward -> dy of the grouped conv
-            r2 = rec["r2"]
             dy2 = _splat_bwd(blk.conv2, rec["spl"], r2, dout, grads)
             del dout
             # (relu(bn1)'s gradient stored bf16 by the grouped dgrad: trunk.G16, round 4)
-            dz1, _, fz1 = _conv_bn_bwd(r2, None, grads, dy=dy2, fuse_prev=rec["r1"], g16=True)
+            dz1, fz1 = _conv_bwd(r2, dy2, grads, fuse_prev=r1, g16=True)
             del dy2
             if rd is not None:
-                if dyd is not None:
-                    dxr, _, _ = _conv_bn_bwd(rd, None, grads, dy=dyd)
-                    del dyd
-                else:
-                    dxr, _, _ = _conv_bn_bwd(rd, dres, grads)
+                if dyd is None:
+                    dyd, _, _ = _unit_dy(rd, dres, grads)
+                dres, _ = _conv_bwd(rd, dyd, grads)
+                del dyd
                 if "pool" in rec:
                     k, st = rec["pool"]
-                    dxr = ops.avgpool2d_bwd(dxr, rec["in_hw"], k, st, 0, False)
-                # (trunk.R16: the sum is returned as a new bf16 tensor when dxr is fp32)
-                dx, _, pending = _conv_bn_bwd(rec["r1"], dz1, grads, parts=fz1, dx_out=dxr,
-                                              dx_beta=1.0, fuse_prev=prev3, r16=True)
-            else:
-                dx, _, pending = _conv_bn_bwd(rec["r1"], dz1, grads, parts=fz1, dx_out=dres,
-                                              dx_beta=1.0, fuse_prev=prev3, r16=True)
-            del dz1, dres, rec
-            g = dx
-            if ready is not None:   # this block's parameter grads are final: start their exchange
-                ready([(p, grads[p]) for p in blk.parameters() if p in grads])
-        am, stem_hw = ctx.pool
+                    dres = ops.avgpool2d_bwd(dres, rec["in_hw"], k, st, 0, False)
+            # (trunk.R16: the sum is returned as a new bf16 tensor when dres is fp32)
+            g, pending = _unit_bwd(r1, dz1, grads, parts=fz1, dx_out=dres, dx_beta=1.0,
+                                   fuse_prev=prev3, r16=True)
+            del dz1, dres, rec, r1, r2, r3, rd
+        am, _ = ctx.pool
         st = ctx.stem
-        d2, _, f2 = _conv_bn_bwd(st[2], None, grads, pool=(g, am), fuse_prev=st[1])
-        d1, _, f1 = _conv_bn_bwd(st[1], d2, grads, parts=f2, fuse_prev=st[0])
-        _conv_bn_bwd(st[0], d1, grads, parts=f1, need_dx=False)
-        out = [grads.get(p) for p in ctx.params]
-        ctx.blocks = ctx.stem = None
-        return (None, None, None) + tuple(out)
+        dy, _, _ = _unit_dy(st[2], g, grads, pool=am)
+        d2, f2 = _conv_bwd(st[2], dy, grads, fuse_prev=st[1])
+        del dy
+        d1, f1 = _unit_bwd(st[1], d2, grads, parts=f2, fuse_prev=st[0])
+        _unit_bwd(st[0], d1, grads, parts=f1, need_dx=False)
+        return _backward_tail(ctx, grads)
 
 
 def _splat_fwd(sp, y2, sc, sh, nbt):
@@ -431,7 +408,8 @@ def _splat_fwd(sp, y2, sc, sh, nbt):
 
 def _splat_bwd(sp, spl, r2, dout, grads):
     """Backward of the split attention and of bn0 + ReLU -> dy2 (the grouped conv's output
-    gradient, dtype of y2); writes the fc1 / bn1 / fc2 / bn0 parameter gradients."""
+    gradient, dtype of y2); writes the fc1 / bn1 / fc2 / bn0 gradients.  r2: bn0's y, scale,
+    shift, mean, inv by key (the grouped conv's Unit, or a plain mapping)."""
     y2 = r2["y"]
     n, hh, ww, c2 = y2.shape
     C = c2 // 2
@@ -457,10 +435,9 @@ def _splat_bwd(sp, spl, r2, dout, grads):
 def _features_infer16(share, x4):
     """The bf16-activation inference trunk (eval mode, precision "bf16",
     share.infer_act16): every stored activation bf16, rounded once where it is stored.  Fused conv
-    units (trunk._conv_bn y16: BN, residual and ReLU in the conv epilogue), the radix-2 grouped
+    units (trunk._conv_bn_eval y16: BN, residual and ReLU in the conv epilogue), the radix-2 grouped
     3x3 as one grouped unit, the GAP in fp32, the attention MLP in one launch, and the weighted
     sum -- with the avd pool of strided blocks -- in one pass over the stored x2."""
-    from .trunk import _conv_bn
     mt = share.precision
     ident = share.__dict__.setdefault("_infer16_identity", {})
 
@@ -472,8 +449,8 @@ def _features_infer16(share, x4):
         return ident[key]
 
     def unit(x, conv, bn, stride, pad, relu, residual=None, groups=1):
-        return _conv_bn(x, conv, bn, stride, pad, relu, False, residual=residual, math=mt,
-                        groups=groups, y16=True)
+        return _conv_bn_eval(x, conv, bn, stride, pad, relu, mt, residual=residual, y16=True,
+                             groups=groups)
 
     c = share.conv1
     z = unit(ops.nhwc4_to_bf16x8(x4), c[0], c[1], 2, 1, True)
@@ -509,7 +486,6 @@ def _features_infer16(share, x4):
 
 def _trunk_node_ok(share):
     """The whole-trunk node covers fp32 math and bf16 math under the bf16-activation contract."""
-    from .trunk import _act16
     return share.precision == "fp32" or _act16(share.precision)
 
 
@@ -647,7 +623,6 @@ class ResNeSt50Share(nn.Sequential):
             # grad mode is off inside autograd.Function.forward: decide here whether to save
             keep = torch.is_grad_enabled() and any(p.requires_grad for p in params)
             return ResNeStTrunkFn.apply(x4, self, keep, *params)
-        from .trunk import _infer16
         if _infer16(self):
             with torch.no_grad(), ops.layout_session(self, ("resnest50", "infer16",
                                                             self.precision)):

@@ -14,6 +14,13 @@ backward pass (BN backward, dgrad, wgrad) in reverse layer order.
 BN semantics follow nn.BatchNorm2d in train mode: batch mean / biased variance
 for normalisation, running stats updated with momentum and the unbiased
 variance, num_batches_tracked += 1; eval mode uses running stats.
+
+The other step kinds, each specified by the block comment named:
+  * precision "bf16": bf16 conv operands and activations (BF16_STORE, FULL16, ACT16, G16, R16);
+  * precision "bf16-bwd": the fp32 forward, bf16 operands in the backward convs only (BWD16);
+  * frozen BatchNorm (freeze_bn): a train step on the running statistics ("frozen BatchNorm");
+  * infer16: eval mode with bf16 activations, opt-in (_infer16, TrunkFn._forward_eval).
+How the units of a step are put together: "the conv+BN unit" below, DESIGN.md §29.
 """
 import os
 import weakref
@@ -156,14 +163,9 @@ def _ds_fold(g, r3, rd):
     produce dy (WGRAD_BNBWD_DS) -> (fold3, foldd)."""
     # (fp32 math only: the BWD16 step's g is fp32 but its wgrads run in bf16 math on a bf16 dy)
     if not (WGRAD_BNBWD and WGRAD_BNBWD_DS and g.dtype == torch.float32
-            and r3["math"] == "fp32" and rd["math"] == "fp32" and g.numel() >= WGRAD_BNBWD_DS_MIN):
+            and r3.math == "fp32" and rd.math == "fp32" and g.numel() >= WGRAD_BNBWD_DS_MIN):
         return False, False
-
-    def ok(rec):
-        kr, ks = rec["conv"].weight.shape[2:]
-        return (rec.get("groups", 1) == 1 and
-                ops.conv_wgrad_bnbwd_ok(rec["x"], g, rec["y"], kr, ks, rec["stride"], rec["pad"]))
-    return ok(r3), ok(rd)
+    return _wgrad_dy_ok(r3, g), _wgrad_dy_ok(rd, g)
 
 
 def _ds_dual(g, r3, rd):
@@ -171,16 +173,16 @@ def _ds_dual(g, r3, rd):
     would write (fp32 y under bf16 storage writes bf16 dy: not this path -- except the BWD16
     step's records, whose fp32 g / y / y_ds in, bf16 dy's out form is _ds_dy16), 8-channel
     multiples."""
-    y = r3["y"]
-    return (DS_DUAL and g.is_contiguous() and g.dtype == y.dtype == rd["y"].dtype
-            and y.shape == rd["y"].shape and y.shape[-1] % 8 == 0
-            and (_ds_dy16(r3, rd) or not (_store16(r3["math"]) and y.dtype == torch.float32)))
+    y = r3.y
+    return (DS_DUAL and g.is_contiguous() and g.dtype == y.dtype == rd.y.dtype
+            and y.shape == rd.y.shape and y.shape[-1] % 8 == 0
+            and (_ds_dy16(r3, rd) or not (_store16(r3.math) and y.dtype == torch.float32)))
 
 
 def _ds_dy16(r3, rd):
     """The BWD16 step's downsample blocks: fp32 g, y3, y_ds, both dy's stored bf16
     (ops.bn_bwd_parts_ds(dy16=True))."""
-    return bool(r3.get("dy16") and rd.get("dy16") and r3["y"].dtype == torch.float32)
+    return bool(r3.dy16 and rd.dy16 and r3.y.dtype == torch.float32)
 
 # the fp32 block outputs' ReLU masks as bits for the mask-3 dgrads (round 2: 3622 -> 3634 frames/s,
 # profiles/r2/bench_r3a/).  The bf16-activation step re-reads its 2-byte z instead: bits measured no
@@ -234,228 +236,319 @@ def _infer16(share):
                 and getattr(share, "infer_act16", False))
 
 
-def _conv_bn(x, conv, bn, stride, pad, relu, training, residual=None, recs=None, math="fp32",
-             defer=False, branch=None, nbt=None, dual=False, groups=1, y16=False, bwd16=False,
-             x16=None, frozen=None, fold=False):
-    """conv (NHWC implicit GEMM) -> BN -> (+residual) -> (ReLU); returns z.
+# ------------------------------------------------------------------ the conv+BN unit
+class Unit:
+    """What the forward of one conv+BN unit leaves for its backward.  Built by _TrainUnits._run
+    only; every field is set for every unit, None where the step kind has no such tensor."""
+    __slots__ = (
+        "conv", "bn",      # the parameter containers
+        "x",       # the conv's input as the wgrad reads it (bf16-bwd: its bf16 copy x16, but the
+                   # stem's NHWC4 fp32 input)
+        "wk",      # KRSC weights (_krsc)
+        "wt",      # the dgrad's transposed CRSK copy (_dgrad_weights); None: the dgrad reads wk
+        "y",       # the conv output
+        "z",       # the BN output of a residual unit (the ReLU mask); None without a residual,
+                   # for a deferred unit, and in the bf16-bwd step once the bits replace it
+        "zbits",   # the ReLU mask as bits: fp32 block outputs of a recorded step, else None
+        "scale", "shift", "mean", "inv",   # BN coefficients and statistics (frozen: running)
+        "stride", "pad", "relu",
+        "c_real",  # real input channels per group
+        "math",    # ops.MATH of the backward convs (bf16-bwd: "bf16" after a forward in "fp32")
+        "groups",
+        "res",     # a residual or a branch was added before the ReLU (mask from z, not from y)
+        "dy16",    # the bf16-bwd step: dy is stored bf16 whatever `math` stores
+        "fold")    # frozen step: wt carries scale[k], the unit's dy = g*scale is never formed
 
-    Train mode only: ``defer`` returns (y, scale, shift) instead of applying the BN -- the
-    consumer applies it on load (the downsample branch inside its block's BN3 pass, the stem
-    inside the maxpool); ``branch`` = such a deferred (y, scale, shift) used as the residual.
-    ``dual`` (block outputs under
-    _full16): returns (z fp32, z bf16 copy).  ``groups``: a grouped conv
-    (train mode, or eval mode with y16; ResNeSt's radix-2 3x3, tmr_conv_desc.groups).  ``y16``
-    (eval mode, bf16 activations: the shares' infer_act16): x and residual bf16, z rounded once
-    to bf16.  ``bwd16`` (train mode with recs, math "fp32": the BWD16 step): the forward of
-    math "fp32", returning (z fp32, z bf16 copy) unless deferred, and a record for a bf16-math
-    backward -- ``x16`` the bf16 copy of x (None: the stem's NHWC4 input), the bf16 CRSK weights.
-    ``frozen`` (train mode, math "fp32": the frozen-BN step, _frozen_coefs): this BN's (scale,
-    shift, inv) of the running statistics -- the conv stores y without a statistics epilogue and
-    the apply forms below take the eval coefficients; ``fold``: the unit's masked gradient will
-    come from a fused dgrad, so its own dgrad reads CRSK weights pre-scaled by scale[k]
-    (dy = g*scale is never formed)."""
-    w = conv.weight
-    if frozen is not None and not (training and math == "fp32" and groups == 1 and not dual
-                                   and not y16 and not bwd16):
-        raise RuntimeError("frozen BatchNorm is the train-mode fp32 step of an ungrouped conv")
+    def __init__(self, **fields):
+        for name in self.__slots__:
+            setattr(self, name, fields[name])
+
+    def __getitem__(self, name):   # (resnest._splat_bwd reads bn0's operands by key)
+        return getattr(self, name)
+
+
+def _krsc(w, cs, s16, groups=1):
+    """The forward's KRSC weights of an OIHW conv weight for an input of cs stored channels."""
     k, c, r, s = w.shape
-    if bwd16 and not (training and recs is not None and math == "fp32" and groups == 1
-                      and not dual and not y16):
-        raise RuntimeError("bwd16 is the train-mode fp32 forward of an ungrouped conv with a "
-                           "recorded backward")
-    cs = x.shape[3]
-    s16 = _store16(math)
     if r == 1 and s == 1 and c == cs and not s16:
-        wk = w.detach().contiguous().view(k, 1, 1, c)   # OIHW == KRSC for 1x1
-    else:   # (grouped: torch's (K, C/G, R, S) -> stacked per-group KRSC blocks (K, R, S, C/G))
-        wk = ops.weight_to_krsc(w.detach().contiguous(), cpad=cs // groups, bf16=s16)
-    if groups > 1 and not training and not y16:
+        return w.detach().contiguous().view(k, 1, 1, c)   # OIHW == KRSC for 1x1
+    # (grouped: torch's (K, C/G, R, S) -> stacked per-group KRSC blocks (K, R, S, C/G))
+    return ops.weight_to_krsc(w.detach().contiguous(), cpad=cs // groups, bf16=s16)
+
+
+def _conv_bn_eval(x, conv, bn, stride, pad, relu, math, residual=None, y16=False, groups=1):
+    """The eval unit: running-stat BN, residual and ReLU in the conv epilogue (one launch; same
+    arithmetic as conv_fwd + bn_apply) -> z.  ``y16`` (the shares' infer_act16): x and residual
+    bf16, z rounded once to bf16.  ``groups``: ResNeSt's radix-2 3x3, with y16 only."""
+    if groups > 1 and not y16:
         raise RuntimeError("grouped convs run in the train-mode trunk and the bf16-activation "
                            "inference trunk (y16) only")
-    if training and frozen is not None:
-        # no statistics: the running ones, through the coefficients of the step's one launch
-        y = ops.conv_fwd(x, wk, stride, pad, c_real=c, math=math)
-        scale, shift, inv = frozen
-        mean = bn.running_mean
-    elif training:
-        # batch statistics come out of the conv epilogue (no separate pass over y)
-        y, stats, nparts = ops.conv_fwd_bnstats(x, wk, stride, pad, c_real=c * groups, math=math,
-                                                y16=_act16(math), groups=groups)
-        mean, inv, scale, shift = ops.bn_finalize(
-            stats, nparts, bn.weight.detach(), bn.bias.detach(), bn.running_mean,
-            bn.running_var, _bn_momentum(bn), bn.eps)
-        # num_batches_tracked += 1; the trunk batches these into one launch (nbt list)
-        if nbt is None:
-            bn.num_batches_tracked.add_(1)
+    w = conv.weight
+    wk = _krsc(w, x.shape[3], _store16(math), groups)
+    scale, shift = ops.bn_eval_params(bn.weight.detach(), bn.bias.detach(), bn.running_mean,
+                                      bn.running_var, bn.eps)
+    return ops.conv_fwd_fused(x, wk, stride, pad, scale, shift, residual, relu,
+                              c_real=w.shape[1], math=math, y16=y16, groups=groups)
+
+
+def _bn_apply_form(y, scale, shift, residual, branch, relu, bits, copy16, s16):
+    """The BatchNorm apply pass of a train unit -> (z, zbits, z16).  bits: also the ReLU mask as
+    bits (a residual unit with ReLU); copy16: also a bf16 copy of z; branch: a deferred (y, scale,
+    shift) as the residual, its BN applied on load; s16: a non-residual z is stored bf16."""
+    if bits and copy16:
+        if branch is not None:
+            return ops.bn_apply2_bits_dual(y, scale, shift, branch[0], branch[1], branch[2])
+        return ops.bn_apply_bits_dual(y, scale, shift, residual)
+    if bits:
+        if branch is not None:
+            return ops.bn_apply2_bits(y, scale, shift, branch[0], branch[1], branch[2]) + (None,)
+        return ops.bn_apply_bits(y, scale, shift, residual) + (None,)
+    if branch is not None:
+        z = ops.bn_apply2(y, scale, shift, branch[0], branch[1], branch[2], relu, dual=copy16)
+        return (z[0], None, z[1]) if copy16 else (z, None, None)
+    if copy16:
+        z, z16 = ops.bn_apply_dual(y, scale, shift, residual, relu)
+        return z, None, z16
+    # a non-residual unit's output is only ever a conv operand (next conv's forward and wgrad; the
+    # backward recomputes its ReLU mask from y): bf16 under bf16 math (with bf16 activations every
+    # z is bf16: the dtype of y decides)
+    return ops.bn_apply(y, scale, shift, residual, relu, bf16=s16 and residual is None), None, None
+
+
+def _dgrad_weights(w, x, math, groups, bwd16, scale):
+    """The transposed weight copy a unit's dgrad reads (LDS-DMA engine), or None (the dgrad takes
+    the KRSC weights; the stem's 3 input channels: no dgrad).  scale: the frozen step's fold."""
+    c = w.shape[1]
+    if bwd16:
+        return ops.weight_to_crsk(w.detach().contiguous()) if c % 8 == 0 else None
+    if scale is not None:
+        return ops.weight_to_crsk_scaled(w.detach().contiguous(), scale)
+    x16 = _full16(math) and x.dtype == torch.bfloat16
+    if groups > 1 and (x16 or _dma32(math)):
+        return ops.weight_to_crsk_grouped(w.detach().contiguous(), groups, bf16=x16)
+    if x16:
+        return ops.weight_to_crsk(w.detach().contiguous())
+    if _dma32(math) and c % 8 == 0 and x.dtype == torch.float32:
+        return ops.weight_to_crsk(w.detach().contiguous(), bf16=False)
+    return None
+
+
+class _TrainUnits:
+    """The train-mode forward units of one step, with what is constant over the forward: ``math``
+    of the forward convs, ``keep`` (record the units for a backward), ``bwd16`` (the BWD16 step: a
+    bf16 copy of every z and records for a bf16-math backward), ``frozen`` (the frozen-BN step's
+    {bn: (scale, shift, inv)}, _frozen_coefs: no statistics epilogue, the running statistics'
+    coefficients).  ``nbt``: the units' num_batches_tracked, for one ops.counters_add_one."""
+
+    def __init__(self, math, keep, bwd16=False, frozen=None):
+        if (bwd16 or frozen is not None) and math != "fp32":
+            raise RuntimeError("the bf16-bwd and the frozen-BN steps run an fp32 forward")
+        self.math, self.keep, self.bwd16, self.frozen = math, keep, bwd16, frozen
+        self.nbt = []
+
+    def unit(self, x, conv, bn, stride, pad, relu, **kw):
+        """conv -> BN -> (+residual | +branch) -> (ReLU) -> (z, z16, record); z16: the bf16 copy
+        of z under ``dual`` (block outputs under _full16) and in the BWD16 step, else None."""
+        _, z, z16, rec = self._run(x, conv, bn, stride, pad, relu, False, **kw)
+        return z, z16, rec
+
+    def deferred(self, x, conv, bn, stride, pad, relu, **kw):
+        """conv and the BN coefficients only -> ((y, scale, shift), record): the consumer applies
+        the BN on load (the downsample branch inside its block's BN3 pass as ``branch``, the stem
+        inside the maxpool, ResNeSt's bn0 inside the split attention)."""
+        branch, _, _, rec = self._run(x, conv, bn, stride, pad, relu, True, **kw)
+        return branch, rec
+
+    def _run(self, x, conv, bn, stride, pad, relu, defer, residual=None, branch=None, dual=False,
+             groups=1, x16=None, fold=True):
+        """``groups``: a grouped conv (ResNeSt's radix-2 3x3).  ``x16`` (BWD16 step): the bf16
+        copy of x for the record (None: the stem's NHWC4 input).  ``fold`` (frozen step): the
+        unit's masked gradient will come from a fused dgrad, so its own dgrad reads CRSK weights
+        pre-scaled by scale[k]."""
+        math, bwd16, frozen = self.math, self.bwd16, self.frozen
+        w = conv.weight
+        c = w.shape[1]
+        if groups > 1 and (bwd16 or frozen is not None):
+            raise RuntimeError("the bf16-bwd and the frozen-BN steps have no grouped conv")
+        s16 = _store16(math)
+        wk = _krsc(w, x.shape[3], s16, groups)
+        if frozen is not None:
+            # no statistics: the running ones, through the coefficients of the step's one launch
+            y = ops.conv_fwd(x, wk, stride, pad, c_real=c, math=math)
+            scale, shift, inv = frozen[bn]
+            mean = bn.running_mean
         else:
-            nbt.append(bn.num_batches_tracked)
-    else:
-        # eval: running-stat BN, residual and ReLU in the conv epilogue (one launch, no y pass;
-        # same arithmetic as conv_fwd + bn_apply)
-        scale, shift = ops.bn_eval_params(bn.weight.detach(), bn.bias.detach(), bn.running_mean,
-                                          bn.running_var, bn.eps)
-        return ops.conv_fwd_fused(x, wk, stride, pad, scale, shift, residual, relu, c_real=c,
-                                  math=math, y16=y16, groups=groups)
-    # fp32 block outputs on the LDS-DMA path also record their ReLU mask as bits: the dgrad that
-    # produces their gradient reads 1 bit instead of z's 4 bytes (mask 3)
-    zbits = None
-    # (bf16 activations too: the bits of the rounded z, tmr_bn_apply_bits_a16)
-    bits = (recs is not None and relu and not dual and _dma32(math) and y.dtype == torch.float32
-            and (residual is not None or branch is not None))
-    z16 = None
-    if defer:
-        z = None
-    elif bwd16 and bits and branch is not None:
-        z, zbits, z16 = ops.bn_apply2_bits_dual(y, scale, shift, branch[0], branch[1], branch[2])
-    elif bwd16 and bits:
-        z, zbits, z16 = ops.bn_apply_bits_dual(y, scale, shift, residual)
-    elif bwd16:
-        if residual is not None or branch is not None:
-            raise RuntimeError("bwd16: a residual unit without ReLU has no dual apply")
-        z, z16 = ops.bn_apply_dual(y, scale, shift, None, relu)
-    elif branch is not None and bits:
-        z, zbits = ops.bn_apply2_bits(y, scale, shift, branch[0], branch[1], branch[2])
-    elif bits:
-        z, zbits = ops.bn_apply_bits(y, scale, shift, residual)
-    elif branch is not None:
-        z = ops.bn_apply2(y, scale, shift, branch[0], branch[1], branch[2], relu, dual=dual)
-    elif dual:
-        z = ops.bn_apply_dual(y, scale, shift, residual, relu)
-    else:
-        # a non-residual unit's output is only ever a conv operand (next conv's forward and
-        # wgrad; the backward recomputes its ReLU mask from y): bf16 under bf16 math (with bf16
-        # activations every z is bf16: the dtype of y decides)
-        z = ops.bn_apply(y, scale, shift, residual, relu, bf16=s16 and residual is None)
-    if recs is not None:
-        # without a residual the backward recomputes the ReLU mask from y (scale/shift)
+            # batch statistics come out of the conv epilogue (no separate pass over y)
+            y, stats, nparts = ops.conv_fwd_bnstats(x, wk, stride, pad, c_real=c * groups,
+                                                    math=math, y16=_act16(math), groups=groups)
+            mean, inv, scale, shift = ops.bn_finalize(
+                stats, nparts, bn.weight.detach(), bn.bias.detach(), bn.running_mean,
+                bn.running_var, _bn_momentum(bn), bn.eps)
+            self.nbt.append(bn.num_batches_tracked)
         has_res = residual is not None or branch is not None
-        # the dgrad view of a bf16-operand conv reads the transposed weights (LDS-DMA engine)
-        if bwd16:   # (the stem's 3 input channels: no dgrad)
-            wt = ops.weight_to_crsk(w.detach().contiguous()) if c % 8 == 0 else None
-        elif frozen is not None and fold:
-            wt = ops.weight_to_crsk_scaled(w.detach().contiguous(), scale)
-        elif groups > 1 and ((_full16(math) and x.dtype == torch.bfloat16) or _dma32(math)):
-            wt = ops.weight_to_crsk_grouped(w.detach().contiguous(), groups,
-                                            bf16=x.dtype == torch.bfloat16)
-        elif _full16(math) and x.dtype == torch.bfloat16:
-            wt = ops.weight_to_crsk(w.detach().contiguous())
-        elif _dma32(math) and c % 8 == 0 and x.dtype == torch.float32:
-            wt = ops.weight_to_crsk(w.detach().contiguous(), bf16=False)
-        else:   # (the stem's 3 input channels: no dgrad)
-            wt = None
-        # bwd16: the backward's conv views read the bf16 copies in bf16 math, dy stored bf16
-        recs.append({"x": x16 if (bwd16 and x16 is not None) else x, "wk": wk, "wt": wt, "y": y,
-                     "z": (z[0] if dual else z) if has_res else None, "zbits": zbits,
-                     "scale": scale, "shift": shift, "mean": mean, "inv": inv,
-                     "stride": stride, "pad": pad, "relu": relu, "conv": conv, "bn": bn,
-                     "c_real": c, "math": "bf16" if bwd16 else math, "groups": groups,
-                     "res": has_res, "dy16": bwd16, "fold": bool(frozen is not None and fold)})
-    if defer:
-        return y, scale, shift
-    return (z, z16) if bwd16 else z
+        # fp32 block outputs on the LDS-DMA path also record their ReLU mask as bits: the dgrad
+        # that produces their gradient reads 1 bit instead of z's 4 bytes (mask 3)
+        bits = (self.keep and relu and not dual and _dma32(math) and y.dtype == torch.float32
+                and has_res)
+        z = zbits = z16 = None
+        if not defer:
+            if bwd16 and has_res and not bits:
+                raise RuntimeError("bwd16: a residual unit without ReLU has no dual apply")
+            z, zbits, z16 = _bn_apply_form(y, scale, shift, residual, branch, relu, bits,
+                                           dual or bwd16, s16)
+        rec = None
+        if self.keep:
+            folded = bool(frozen is not None and fold)
+            # bwd16: the backward's conv views read the bf16 copies in bf16 math, dy stored bf16
+            rec = Unit(conv=conv, bn=bn, x=x16 if (bwd16 and x16 is not None) else x, wk=wk,
+                       wt=_dgrad_weights(w, x, math, groups, bwd16, scale if folded else None),
+                       y=y, z=z if has_res else None, zbits=zbits, scale=scale, shift=shift,
+                       mean=mean, inv=inv, stride=stride, pad=pad, relu=relu, c_real=c,
+                       math="bf16" if bwd16 else math, groups=groups, res=has_res, dy16=bwd16,
+                       fold=folded)
+        return (y, scale, shift), z, z16, rec
 
 
-def _conv_bn_bwd(rec, dz, grads, want_dres=False, dx_out=None, dx_beta=0.0, need_dx=True,
-                 dres_inplace=False, parts=None, fuse_prev=None, pool=None, dy=None, g16=False,
-                 r16=False, fold=False, gcoef=None):
-    """BN backward, wgrad, dgrad (optionally accumulated into dx_out) of one conv+BN unit.
+def _wgrad_dy_ok(rec, g):
+    """The fused wgrad (tmr_conv2d_wgrad_bnbwd) serves this unit's operands."""
+    kr, ks = rec.conv.weight.shape[2:]
+    return (rec.groups == 1 and
+            ops.conv_wgrad_bnbwd_ok(rec.x, g, rec.y, kr, ks, rec.stride, rec.pad))
 
+
+def _wgrad_dy(rec, g, coef):
+    """The fused wgrad: dy = A*g + B*y + C from the masked gradient g, the unit's y and the
+    coefficients of its BN backward's reductions, formed while loading -> (dy, dw)."""
+    kr, ks = rec.conv.weight.shape[2:]
+    dw, dy = ops.conv_wgrad_bnbwd(rec.x, g, rec.y, coef, kr, ks, rec.stride, rec.pad,
+                                  c_real=rec.c_real)
+    return dy, dw
+
+
+def _unit_dy(rec, dz, grads, parts=None, pool=None, want_dres=False, dres_inplace=False,
+             fold=False):
+    """The BatchNorm backward of one unit: writes the BN gradients -> (dy, dw, dres); dw only
+    where the fused wgrad formed dy, dres (the identity branch's gradient) only if wanted.
     parts: dz was produced by a fused dgrad (conv_dgrad_bnbwd): it is already ReLU-masked and
     `parts` holds its BN-backward partial sums.  Otherwise the ReLU mask comes from the saved z,
     or is recomputed from y when there was no residual.  dres_inplace: the pre-activation
-    gradient (the identity branch's) overwrites dz and is returned as dres.
+    gradient overwrites dz and is returned as dres.
+    pool: the argmax of the maxpool that consumed this unit's output (the stems); dz is the
+    pooled gradient, gathered inside the BN backward.
+    fold: with parts, the fp32 wgrad may produce dy itself (WGRAD_BNBWD) where the library serves
+    the unit; the ResNet-50 trunk's units only (records of math "fp32": not the BWD16 step's)."""
+    bn = rec.bn
+    gamma = bn.weight.detach()
+    # dy feeds only this conv's dgrad / wgrad (the BWD16 step's records always store it bf16)
+    s16 = rec.dy16 or _store16(rec.math)
+    dw = dres = None
+    if pool is not None:
+        # maxpool backward + ReLU mask + BN backward without writing dz
+        dy, dg, db = ops.bn_bwd_maxpool(dz, pool, rec.y, rec.scale, rec.shift, rec.mean, rec.inv,
+                                        gamma, bf16=s16)
+    elif parts is None:
+        dy, dres, dg, db = ops.bn_bwd(dz, rec.y, rec.z, rec.mean, rec.inv, gamma, rec.relu,
+                                      want_dres=want_dres, dres_out=dz if dres_inplace else None,
+                                      scale=rec.scale, shift=rec.shift, bf16=s16)
+    else:
+        if fold and WGRAD_BNBWD and rec.math == "fp32" and _wgrad_dy_ok(rec, dz):
+            coef, dg, db = ops.bn_bwd_parts_coef(rec.y, parts[0], parts[1], rec.mean, rec.inv,
+                                                 gamma)
+            dy, dw = _wgrad_dy(rec, dz, coef)
+        else:
+            dy, dg, db = ops.bn_bwd_parts(dz, rec.y, parts[0], parts[1], rec.mean, rec.inv,
+                                          gamma, bf16=s16)
+        dres = dz if want_dres else None
+    grads[bn.weight] = dg
+    grads[bn.bias] = db
+    return dy, dw, dres
+
+
+def _conv_bwd(rec, dy, grads, dw=None, dx_out=None, dx_beta=0.0, need_dx=True, fuse_prev=None,
+              g16=False, r16=False):
+    """wgrad (unless dw came with dy, _wgrad_dy) and dgrad (optionally accumulated into dx_out)
+    of one unit from its conv's output gradient dy -> (dx, fused).
+
     fuse_prev: the unit whose BN output gradient this unit's dgrad produces -- its mask and
-    partial sums are then computed in the dgrad epilogue; returned as the third value.
-    pool: (pooled gradient, argmax) of the maxpool that consumed this unit's output (the stem);
-    dz is then gathered from it inside the BN backward.
-    dy: the conv's output gradient computed by the caller (ResNeSt's split-attention backward
-    writes the grouped conv's dy with bn0's backward folded in): only wgrad and dgrad run here.
+    partial sums are then computed in the dgrad epilogue; `fused` = those (parts, nparts).
     g16: the fused dgrad may store fuse_prev's masked gradient as bf16 (TMR_IO_G16) when that unit
     has no residual and the dgrad runs on the bf16 LDS-DMA engine (the bf16-activation step).
     r16: the same for fuse_prev a block output (R16): the dgrad adds into dx_out (bf16 in place,
-    or fp32 read and a new bf16 tensor returned).
-    fold: with parts, the fp32 wgrad may produce dy itself (WGRAD_BNBWD) where the library serves
-    the unit; the ResNet-50 trunk's units only (records of math "fp32": not the BWD16 step's).
-    gcoef: (g, coef) in place of dy -- the caller ran the BN backward's reductions
-    (ops.bn_bwd_parts_ds_coef) and the fused wgrad produces dy from the masked gradient g, this
-    unit's y and its coefficients; only wgrad and dgrad run here."""
-    conv, bn = rec["conv"], rec["bn"]
-    # dy feeds only this conv's dgrad / wgrad (the BWD16 step's records always store it bf16)
-    s16 = rec.get("dy16", False) or _store16(rec["math"])
-    dy_given = dy is not None or gcoef is not None
-    dw = None
-    kr, ks = conv.weight.shape[2:]
-    if gcoef is not None:
-        dw, dy = ops.conv_wgrad_bnbwd(rec["x"], gcoef[0], rec["y"], gcoef[1], kr, ks, rec["stride"],
-                                      rec["pad"], c_real=rec["c_real"])
-        dres = None
-    elif dy_given:
-        dres = None
-    elif pool is not None:
-        # the stem: maxpool backward + ReLU mask + BN backward without writing dz
-        dy, dg, db = ops.bn_bwd_maxpool(pool[0], pool[1], rec["y"], rec["scale"], rec["shift"],
-                                        rec["mean"], rec["inv"], bn.weight.detach(), bf16=s16)
-        dres = None
-    elif (parts is not None and fold and WGRAD_BNBWD and rec["math"] == "fp32"
-          and rec.get("groups", 1) == 1
-          and ops.conv_wgrad_bnbwd_ok(rec["x"], dz, rec["y"], kr, ks, rec["stride"], rec["pad"])):
-        coef, dg, db = ops.bn_bwd_parts_coef(rec["y"], parts[0], parts[1], rec["mean"],
-                                             rec["inv"], bn.weight.detach())
-        dw, dy = ops.conv_wgrad_bnbwd(rec["x"], dz, rec["y"], coef, kr, ks, rec["stride"],
-                                      rec["pad"], c_real=rec["c_real"])
-        dres = dz if want_dres else None
-    elif parts is not None:
-        dy, dg, db = ops.bn_bwd_parts(dz, rec["y"], parts[0], parts[1], rec["mean"], rec["inv"],
-                                      bn.weight.detach(), bf16=s16)
-        dres = dz if want_dres else None
-    else:
-        dy, dres, dg, db = ops.bn_bwd(dz, rec["y"], rec["z"], rec["mean"], rec["inv"],
-                                      bn.weight.detach(), rec["relu"], want_dres=want_dres,
-                                      dres_out=dz if dres_inplace else None,
-                                      scale=rec["scale"], shift=rec["shift"], bf16=s16)
-    if not dy_given:
-        grads[bn.weight] = dg
-        grads[bn.bias] = db
-    x = rec["x"]
-    k, c, r, s = conv.weight.shape
-    grp = rec.get("groups", 1)
-    grads[conv.weight] = dw if dw is not None else ops.conv_wgrad(
-        x, dy, r, s, rec["stride"], rec["pad"], c_real=rec["c_real"], math=rec["math"],
-        groups=grp)
-    dx, fused = None, None
-    if need_dx:
-        hw = (x.shape[1], x.shape[2])
-        wt = rec.get("wt") is not None
-        wdg = rec["wt"] if wt else rec["wk"]
-        if fuse_prev is not None:
-            p = fuse_prev
-            mask = (1 if p.get("res", p["z"] is not None) else 2) if p["relu"] else 0
-            zm = p["z"]
-            if mask == 1 and wt and p.get("zbits") is not None:
-                mask, zm = 3, p["zbits"]   # the ReLU mask as bits (LDS-DMA dgrad)
-            elif mask == 1 and zm is None:   # (the BWD16 step keeps only the bits)
-                raise RuntimeError("a residual unit's ReLU mask needs its saved z or its bits on "
-                                   "the LDS-DMA dgrad")
-            bf8 = (wt and p["y"].dtype == torch.bfloat16 and
-                   (p["y"].shape[-1] // grp) % 8 == 0)
-            # (a grouped dgrad -- ResNeSt's radix-2 conv -- stores its per-group channel slices bf16
-            # too; the residual accumulation stays ungrouped)
-            gb = (g16 and G16 and mask == 2 and dx_out is None and dx_beta == 0.0 and bf8)
-            rb = (r16 and R16 and mask in (1, 3) and dx_out is not None and dx_beta == 1.0 and bf8
-                  and grp == 1)
-            old = None
-            if rb and dx_out.dtype != torch.bfloat16:   # fp32 old dx -> a new bf16 dx
-                old, dx_out = dx_out, None
-            dx, pp, npp = ops.conv_dgrad_bnbwd(dy, wdg, hw, rec["stride"], rec["pad"],
-                                               p["y"], p["mean"], mask, z=zm,
-                                               scale=p["scale"], shift=p["shift"], out=dx_out,
-                                               beta=dx_beta, math=rec["math"],
-                                               wt=wt, groups=grp, g16=gb or rb, old=old)
-            fused = (pp, npp)
-        else:
-            dx = ops.conv_dgrad(dy, wdg, hw, rec["stride"], rec["pad"], out=dx_out,
-                                beta=dx_beta, math=rec["math"], wt=wt, groups=grp)
-    return dx, dres, fused
+    or fp32 read and a new bf16 tensor returned)."""
+    x = rec.x
+    r, s = rec.conv.weight.shape[2:]
+    grp = rec.groups
+    grads[rec.conv.weight] = dw if dw is not None else ops.conv_wgrad(
+        x, dy, r, s, rec.stride, rec.pad, c_real=rec.c_real, math=rec.math, groups=grp)
+    if not need_dx:
+        return None, None
+    hw = (x.shape[1], x.shape[2])
+    wt = rec.wt is not None
+    wdg = rec.wt if wt else rec.wk
+    if fuse_prev is None:
+        return ops.conv_dgrad(dy, wdg, hw, rec.stride, rec.pad, out=dx_out, beta=dx_beta,
+                              math=rec.math, wt=wt, groups=grp), None
+    p = fuse_prev
+    mask = (1 if p.res else 2) if p.relu else 0
+    zm = p.z
+    if mask == 1 and wt and p.zbits is not None:
+        mask, zm = 3, p.zbits   # the ReLU mask as bits (LDS-DMA dgrad)
+    elif mask == 1 and zm is None:   # (the BWD16 step keeps only the bits)
+        raise RuntimeError("a residual unit's ReLU mask needs its saved z or its bits on "
+                           "the LDS-DMA dgrad")
+    bf8 = wt and p.y.dtype == torch.bfloat16 and (p.y.shape[-1] // grp) % 8 == 0
+    # (a grouped dgrad -- ResNeSt's radix-2 conv -- stores its per-group channel slices bf16
+    # too; the residual accumulation stays ungrouped)
+    gb = g16 and G16 and mask == 2 and dx_out is None and dx_beta == 0.0 and bf8
+    rb = (r16 and R16 and mask in (1, 3) and dx_out is not None and dx_beta == 1.0 and bf8
+          and grp == 1)
+    old = None
+    if rb and dx_out.dtype != torch.bfloat16:   # fp32 old dx -> a new bf16 dx
+        old, dx_out = dx_out, None
+    dx, pp, npp = ops.conv_dgrad_bnbwd(dy, wdg, hw, rec.stride, rec.pad, p.y, p.mean, mask,
+                                       z=zm, scale=p.scale, shift=p.shift, out=dx_out,
+                                       beta=dx_beta, math=rec.math, wt=wt, groups=grp,
+                                       g16=gb or rb, old=old)
+    return dx, (pp, npp)
+
+
+def _unit_bwd(rec, dz, grads, parts=None, fold=False, **conv):
+    """_unit_dy then _conv_bwd (its keywords) of a unit whose dy nothing else reads."""
+    dy, dw, _ = _unit_dy(rec, dz, grads, parts=parts, fold=fold)
+    return _conv_bwd(rec, dy, grads, dw=dw, **conv)
+
+
+# ------------------------------------------------------------------ the backward's block loop
+def _backward_blocks(ctx, grads, last_unit):
+    """The skeleton of a trunk backward: pops ctx.blocks' (block module, its records) last to
+    first and yields (block, records, last_unit(the previous block's records) -- the unit whose
+    BN output gradient is this block's dx; None for the first block).  After the loop body the
+    block's gradients are final: the gradient-ready hook (get_grad_ready) starts their exchange."""
+    blocks = ctx.blocks
+    ready = get_grad_ready(ctx.share)
+    while blocks:
+        blk, recs = blocks.pop()
+        prev = last_unit(blocks[-1][1]) if blocks else None
+        yield blk, recs, prev
+        # (this frame must not keep the popped records alive past the body: once the body's own
+        # references go, the block's saved tensors die -- that bounds the step's peak memory)
+        del recs, prev
+        if ready is not None:
+            ready([(p, grads[p]) for p in blk.parameters() if p in grads])
+
+
+def _backward_head(ctx, dfeat):
+    """-> the gradient at the last block's output."""
+    if not ctx.keep:
+        raise RuntimeError("trunk backward needs train mode and a forward with grad enabled")
+    return ops.avgpool_bwd(dfeat.contiguous(), ctx.last_hw)
+
+
+def _backward_tail(ctx, grads):
+    """The autograd result for (x4, share, keep, *params); drops the saved records."""
+    out = tuple(grads.get(p) for p in ctx.params)
+    ctx.blocks = ctx.stem = None
+    return (None, None, None) + out
 
 
 # ------------------------------------------------------------------ frozen BatchNorm
@@ -507,26 +600,28 @@ def _bn_wants_grad(bn):
 
 def _frozen_affine(rec, parts, grads):
     """dgamma / dbeta of a frozen unit from partial sums (its own pass's, or a fused dgrad's)."""
-    if parts is not None and _bn_wants_grad(rec["bn"]):
-        grads[rec["bn"].weight], grads[rec["bn"].bias] = ops.bn_frozen_finalize(
-            parts[0], parts[1], rec["inv"])
+    if parts is not None and _bn_wants_grad(rec.bn):
+        grads[rec.bn.weight], grads[rec.bn.bias] = ops.bn_frozen_finalize(
+            parts[0], parts[1], rec.inv)
 
 
-def _frozen_unit_bwd(rec, g, grads, dy=None, parts=None, **kw):
-    """wgrad and dgrad of one frozen-BN unit.  dy: its real output gradient g*scale (a unit of the
-    single-pass kernels).  Otherwise g is the masked gradient from a fused dgrad (`parts` its
-    partial sums -> the BN gradients): the wgrad runs on g and dW's rows take scale[k], the dgrad
-    reads the pre-scaled CRSK weights (rec["fold"]) -- no elementwise pass forms dy."""
+def _frozen_unit_bwd(rec, g, grads, parts=None, **conv):
+    """wgrad and dgrad (_conv_bwd's keywords) of a frozen-BN unit whose g came masked from a fused
+    dgrad (`parts` -> the BN gradients): the wgrad runs on g and dW's rows take scale[k], the
+    dgrad reads the pre-scaled CRSK weights (rec.fold) -- no pass forms dy = g*scale."""
     _frozen_affine(rec, parts, grads)
-    if dy is not None:
-        if rec["fold"]:
-            raise RuntimeError("frozen BN: a real dy meets pre-scaled dgrad weights")
-        return _conv_bn_bwd(rec, None, grads, dy=dy, **kw)
-    if not rec["fold"] and kw.get("need_dx", True):
+    if not rec.fold:
         raise RuntimeError("frozen BN: a folded unit needs its pre-scaled dgrad weights")
-    out = _conv_bn_bwd(rec, None, grads, dy=g, **kw)
-    ops.scale_rows(grads[rec["conv"].weight], rec["scale"])
+    out = _conv_bwd(rec, g, grads, **conv)
+    ops.scale_rows(grads[rec.conv.weight], rec.scale)
     return out
+
+
+def _frozen_dy_bwd(rec, dy, grads, **conv):
+    """The same for a unit of the single-pass kernels, which wrote its real dy = g*scale."""
+    if rec.fold:
+        raise RuntimeError("frozen BN: a real dy meets pre-scaled dgrad weights")
+    return _conv_bwd(rec, dy, grads, **conv)
 
 
 class TrunkFn(torch.autograd.Function):
@@ -545,187 +640,156 @@ class TrunkFn(torch.autograd.Function):
 
     @staticmethod
     def _forward(ctx, x4, share, keep, params, fz=None):
-        training = share.training
-        keep = keep and training
-        recs = [] if keep else None
-        nbt = []   # BatchNorm num_batches_tracked counters, incremented together at the end
+        keep = keep and share.training
         conv1, bn1, layers = share.trunk_parts()
         mt = _fwd_math(share.precision)
+        ctx.keep = keep
+        ctx.frozen = fz is not None
+        if not share.training:
+            return TrunkFn._forward_eval(x4, conv1, bn1, layers, mt, _infer16(share))
         # the BWD16 step: the fp32 forward plus the bf16 copies its bf16-math backward reads
-        # (without a backward to record -- eval, no grad -- it is the fp32 path itself)
+        # (without a backward to record -- no grad -- it is the fp32 path itself)
         bw = bool(keep and share.precision == BWD16)
-        a16 = training and _act16(mt)            # every activation bf16: no fp32 copies
-        f16 = training and _full16(mt) and not a16
-        # eval mode, opt-in (share.infer_act16): every stored activation bf16, rounded once after
-        # BN (+residual) (+ReLU) by the conv's epilogue; the block output is the next block's
-        # operand and identity
-        i16 = _infer16(share)
-        if training:
-            # bf16 activations: the stem reads an NHWC8 bf16 copy of its input (8-channel
-            # pieces: the LDS-DMA engine; exact, the bf16 math rounds x anyway)
-            xs = ops.nhwc4_to_bf16x8(x4) if (a16 and ops.engine_forced()) else x4
-            # share.bn1 + relu applied inside the maxpool (the backward recomputes the ReLU
-            # mask from y, so the stem's BN output is never needed)
-            y0, sc0, sh0 = _conv_bn(xs, conv1, bn1, 2, 3, True, training, recs=recs, math=mt,
-                                    defer=True, nbt=nbt, bwd16=bw,
-                                    frozen=fz[bn1] if fz is not None else None)
-            if bw:
-                p, h16, am = ops.maxpool_fwd_bn_dual(y0, sc0, sh0)
-            else:
-                p, am = ops.maxpool_fwd_bn(y0, sc0, sh0, bf16=f16)
-            stem_hw = (y0.shape[1], y0.shape[2])
-        elif i16:
-            # bf16-activation inference: the stem reads the NHWC8 bf16 copy of its input on the
-            # LDS-DMA engine; its bf16 output is already >= 0, so the bf16 maxpool with an
-            # identity BatchNorm is exact
-            z = _conv_bn(ops.nhwc4_to_bf16x8(x4), conv1, bn1, 2, 3, True, training, math=mt,
-                         y16=True)
-            p, am = ops.maxpool_fwd_bn(z, torch.ones_like(bn1.running_mean),
-                                       torch.zeros_like(bn1.running_mean))
-            stem_hw = (z.shape[1], z.shape[2])
+        a16 = _act16(mt)                    # every activation bf16: no fp32 copies
+        f16 = _full16(mt) and not a16
+        st = _TrainUnits(mt, keep, bwd16=bw, frozen=fz)
+        # bf16 activations: the stem reads an NHWC8 bf16 copy of its input (8-channel pieces: the
+        # LDS-DMA engine; exact, the bf16 math rounds x anyway)
+        xs = ops.nhwc4_to_bf16x8(x4) if (a16 and ops.engine_forced()) else x4
+        # share.bn1 + relu applied inside the maxpool (the backward recomputes the ReLU mask from
+        # y, so the stem's BN output is never needed)
+        (y0, sc0, sh0), r0 = st.deferred(xs, conv1, bn1, 2, 3, True, fold=False)
+        h16 = None   # (bw: the bf16 copy of the block input, the wgrads' operand)
+        if bw:
+            p, h16, am = ops.maxpool_fwd_bn_dual(y0, sc0, sh0)
         else:
-            z = _conv_bn(x4, conv1, bn1, 2, 3, True, training, recs=recs, math=mt, nbt=nbt)
-            p, am = ops.maxpool_fwd(z)
-            stem_hw = (z.shape[1], z.shape[2])
+            p, am = ops.maxpool_fwd_bn(y0, sc0, sh0, bf16=f16)
         # h: the block input as the identity residual (fp32), hx: as the conv operand (the bf16
         # copy under f16; the maxpool output is only ever a conv operand)
         h, hx = (None, p) if f16 else (p, p)
-        if not bw:
-            h16 = None   # (bw: the bf16 copy of the block input, the wgrads' operand)
-        z1h = z2h = None
         blocks = []
         last = layers[-1][-1]
-
-        def fzk(bn, blk=None):
-            # the frozen step's coefficients; every unit but the last block's bn3 / downsample BN
-            # (whose g arrives unmasked) folds its dy scale into its dgrad weights
-            if fz is None:
-                return {}
-            return {"frozen": fz[bn], "fold": blk is not last}
         for layer in layers:
             for blk in layer:
-                brec = [] if keep else None
-                z1 = _conv_bn(hx, blk.conv1, blk.bn1, 1, 0, True, training, recs=brec, math=mt,
-                              nbt=nbt, y16=i16, bwd16=bw, x16=h16, **fzk(blk.bn1))
-                if bw:
-                    z1, z1h = z1
-                z2 = _conv_bn(z1, blk.conv2, blk.bn2, blk.stride, 1, True, training, recs=brec,
-                              math=mt, nbt=nbt, y16=i16, bwd16=bw, x16=z1h, **fzk(blk.bn2))
-                if bw:
-                    z2, z2h = z2
+                z1, z1h, r1 = st.unit(hx, blk.conv1, blk.bn1, 1, 0, True, x16=h16)
+                z2, z2h, r2 = st.unit(z1, blk.conv2, blk.bn2, blk.stride, 1, True, x16=z1h)
+                # the frozen step: every unit but the last block's bn3 / downsample BN (whose g
+                # arrives unmasked) folds its dy scale into its dgrad weights
+                fold = blk is not last
+                rd = None
                 if blk.downsample is not None:
-                    # train: the branch's BN is applied inside the BN3 pass (bn_apply2)
-                    idn = _conv_bn(hx, blk.downsample[0], blk.downsample[1], blk.stride, 0, False,
-                                   training, recs=brec, math=mt, defer=training, nbt=nbt,
-                                   y16=i16, bwd16=bw, x16=h16, **fzk(blk.downsample[1], blk))
+                    # the branch's BN is applied inside the BN3 pass (bn_apply2)
+                    idn, rd = st.deferred(hx, blk.downsample[0], blk.downsample[1], blk.stride, 0,
+                                          False, x16=h16, fold=fold)
+                    h, hc, r3 = st.unit(z2, blk.conv3, blk.bn3, 1, 0, True, branch=idn, dual=f16,
+                                        x16=z2h, fold=fold)
                 else:
                     if h is None:
                         raise RuntimeError("identity residual of the stem output (no downsample)")
                     idn = h
-                if isinstance(idn, tuple):
-                    h = _conv_bn(z2, blk.conv3, blk.bn3, 1, 0, True, training, branch=idn,
-                                 recs=brec, math=mt, nbt=nbt, dual=f16, bwd16=bw, x16=z2h,
-                                 **fzk(blk.bn3, blk))
-                else:
-                    h = _conv_bn(z2, blk.conv3, blk.bn3, 1, 0, True, training, residual=idn,
-                                 recs=brec, math=mt, nbt=nbt, dual=f16, y16=i16, bwd16=bw,
-                                 x16=z2h, **fzk(blk.bn3, blk))
+                    h, hc, r3 = st.unit(z2, blk.conv3, blk.bn3, 1, 0, True, residual=idn,
+                                        dual=f16, x16=z2h, fold=fold)
+                hx = hc if f16 else h
                 if bw:
-                    h, h16 = h
-                    hx = h
+                    h16 = hc
                     if blocks:   # the previous block output's fp32 z: its mask is in the bits
-                        blocks[-1][1][-1]["z"] = None
+                        blocks[-1][1][-1].z = None
                     del z1, z2, idn   # (their fp32 z's were only this block's forward operands)
-                else:
-                    h, hx = h if f16 else (h, h)
-                blocks.append((blk, brec))
+                blocks.append((blk, [r1, r2, rd, r3]))
         feat = ops.avgpool_fwd(h)
-        if nbt:   # (none under frozen BN: no counter moves)
-            ops.counters_add_one(nbt)
-        ctx.keep = keep
-        ctx.frozen = fz is not None
+        if st.nbt:   # (none under frozen BN: no counter moves)
+            ops.counters_add_one(st.nbt)
         if keep:
             ctx.share = share
             ctx.params = params
-            ctx.stem = recs
-            ctx.pool = (am, stem_hw)
+            ctx.stem = [r0]
+            ctx.pool = (am, (y0.shape[1], y0.shape[2]))
             ctx.blocks = blocks
             ctx.last_hw = (h.shape[1], h.shape[2])
         return feat
 
     @staticmethod
+    def _forward_eval(x4, conv1, bn1, layers, mt, i16):
+        """Eval mode.  i16 (opt-in, share.infer_act16): every stored activation bf16, rounded once
+        after BN (+residual) (+ReLU) by the conv's epilogue; the block output is the next block's
+        operand and identity."""
+        if i16:
+            # the stem reads the NHWC8 bf16 copy of its input on the LDS-DMA engine; its bf16
+            # output is already >= 0, so the bf16 maxpool with an identity BatchNorm is exact
+            z = _conv_bn_eval(ops.nhwc4_to_bf16x8(x4), conv1, bn1, 2, 3, True, mt, y16=True)
+            p, am = ops.maxpool_fwd_bn(z, torch.ones_like(bn1.running_mean),
+                                       torch.zeros_like(bn1.running_mean))
+        else:
+            z = _conv_bn_eval(x4, conv1, bn1, 2, 3, True, mt)
+            p, am = ops.maxpool_fwd(z)
+        h = p
+        for layer in layers:
+            for blk in layer:
+                z1 = _conv_bn_eval(h, blk.conv1, blk.bn1, 1, 0, True, mt, y16=i16)
+                z2 = _conv_bn_eval(z1, blk.conv2, blk.bn2, blk.stride, 1, True, mt, y16=i16)
+                idn = h
+                if blk.downsample is not None:
+                    idn = _conv_bn_eval(h, blk.downsample[0], blk.downsample[1], blk.stride, 0,
+                                        False, mt, y16=i16)
+                h = _conv_bn_eval(z2, blk.conv3, blk.bn3, 1, 0, True, mt, residual=idn, y16=i16)
+        return ops.avgpool_fwd(h)
+
+    @staticmethod
     def backward(ctx, dfeat):
-        if not ctx.keep:
-            raise RuntimeError("trunk backward needs train mode and a forward with grad enabled")
         if ctx.frozen:
             return TrunkFn._backward_frozen(ctx, dfeat)
         grads = {}
-        g = ops.avgpool_bwd(dfeat.contiguous(), ctx.last_hw)   # grad at the last block output
-        blocks = ctx.blocks
+        g = _backward_head(ctx, dfeat)   # grad at the last block output
         pending = None     # BN-backward partials of g when the dgrad that produced it was fused
-        ready = get_grad_ready(ctx.share)   # ddp.GradAllReduce.grads_ready, or None
-        while blocks:
-            blk, brec = blocks.pop()
-            has_ds = blk.downsample is not None
-            r1, r2 = brec[0], brec[1]
-            rd = brec[2] if has_ds else None
-            r3 = brec[-1]
-            # the previous block's last unit: its BN output gradient is this block's dx
-            prev3 = blocks[-1][1][-1] if blocks else None
+        for blk, brec, prev3 in _backward_blocks(ctx, grads, lambda recs: recs[-1]):
+            r1, r2, rd, r3 = brec   # (rd: None without a downsample)
+            has_ds = rd is not None
             # g (owned here) becomes the masked pre-ReLU gradient = the identity-branch grad
-            dyd = gcd = None
-            if (has_ds and _ds_dual(g, r3, rd) and pending is not None):
+            dw3 = dyd = dwd = cd = None
+            if has_ds and _ds_dual(g, r3, rd) and pending is not None:
                 # (g came masked from the next block's fused dgrad)
-                bargs = (g, r3["y"], pending[0], pending[1], r3["mean"], r3["inv"],
-                         r3["bn"].weight.detach(), rd["y"], rd["mean"], rd["inv"],
-                         rd["bn"].weight.detach())
+                bargs = (g, r3.y, pending[0], pending[1], r3.mean, r3.inv,
+                         r3.bn.weight.detach(), rd.y, rd.mean, rd.inv, rd.bn.weight.detach())
                 f3, fd = _ds_fold(g, r3, rd)
-                gc3 = None
                 if f3 or fd:
                     # the served units' wgrads produce their dy themselves (g outlives both: dres)
                     c3, dg3, db3, cd, dgd, dbd, dy3, dyd = ops.bn_bwd_parts_ds(
                         *bargs, fold3=f3, foldd=fd)
-                    gc3 = (g, c3) if f3 else None
-                    gcd = (g, cd) if fd else None
+                    if f3:
+                        dy3, dw3 = _wgrad_dy(r3, g, c3)
+                    if not fd:
+                        cd = None
                 else:
                     dy3, dg3, db3, dyd, dgd, dbd = ops.bn_bwd_parts_ds(
                         *bargs, dy16=_ds_dy16(r3, rd))
-                grads[r3["bn"].weight], grads[r3["bn"].bias] = dg3, db3
-                grads[rd["bn"].weight], grads[rd["bn"].bias] = dgd, dbd
-                dz2, _, fz2 = _conv_bn_bwd(r3, None, grads, fuse_prev=r2, g16=True, dy=dy3, gcoef=gc3)
+                grads[r3.bn.weight], grads[r3.bn.bias] = dg3, db3
+                grads[rd.bn.weight], grads[rd.bn.bias] = dgd, dbd
                 dres = g
-                del dy3, gc3
             else:
-                dz2, dres, fz2 = _conv_bn_bwd(r3, g, grads, want_dres=True, dres_inplace=True,
-                                              parts=pending, fuse_prev=r2, g16=True, fold=True)
-            dz1, _, fz1 = _conv_bn_bwd(r2, dz2, grads, parts=fz2, fuse_prev=r1, g16=True,
-                                      fold=True)
+                dy3, dw3, dres = _unit_dy(r3, g, grads, parts=pending, want_dres=True,
+                                          dres_inplace=True, fold=True)
+            dz2, fz2 = _conv_bwd(r3, dy3, grads, dw=dw3, fuse_prev=r2, g16=True)
+            del dy3
+            dz1, fz1 = _unit_bwd(r2, dz2, grads, parts=fz2, fold=True, fuse_prev=r1, g16=True)
             del dz2
             if has_ds:
                 # the strided downsample dgrad writes dx (its tap-less parity classes as zeros),
                 # the stride-1 conv1 dgrad accumulates into it with the fused BN backward
                 # (measured 51.1 vs 51.6 ms of dgrads per C2 step against the other order,
                 # profiles/r3/bench_r4f/)
-                if dyd is not None or gcd is not None:
-                    dx, _, _ = _conv_bn_bwd(rd, None, grads, dy=dyd, gcoef=gcd)
-                    del dyd, gcd
-                else:
-                    dx, _, _ = _conv_bn_bwd(rd, dres, grads)
-                dx, _, pending = _conv_bn_bwd(r1, dz1, grads, parts=fz1, dx_out=dx, dx_beta=1.0,
-                                              fuse_prev=prev3, r16=True, fold=True)
-            else:
-                dx, _, pending = _conv_bn_bwd(r1, dz1, grads, parts=fz1, dx_out=dres, dx_beta=1.0,
-                                              fuse_prev=prev3, r16=True, fold=True)
+                if cd is not None:
+                    dyd, dwd = _wgrad_dy(rd, dres, cd)
+                elif dyd is None:
+                    dyd, dwd, _ = _unit_dy(rd, dres, grads)
+                dres, _ = _conv_bwd(rd, dyd, grads, dw=dwd)
+                del dyd
+            g, pending = _unit_bwd(r1, dz1, grads, parts=fz1, fold=True, dx_out=dres,
+                                   dx_beta=1.0, fuse_prev=prev3, r16=True)
             del dz1, brec, dres
-            g = dx
-            if ready is not None:   # this block's parameter grads are final: start their exchange
-                ready([(p, grads[p]) for p in blk.parameters() if p in grads])
-        dh = g
-        am, stem_hw = ctx.pool
-        _conv_bn_bwd(ctx.stem[0], None, grads, need_dx=False, pool=(dh, am))
-        out = [grads.get(p) for p in ctx.params]
-        ctx.blocks = ctx.stem = None
-        return (None, None, None) + tuple(out)
+        am, _ = ctx.pool
+        dy0, _, _ = _unit_dy(ctx.stem[0], g, grads, pool=am)
+        _conv_bwd(ctx.stem[0], dy0, grads, need_dx=False)
+        return _backward_tail(ctx, grads)
 
     @staticmethod
     def _backward_frozen(ctx, dfeat):
@@ -736,68 +800,56 @@ class TrunkFn(torch.autograd.Function):
         (_frozen_unit_bwd).  A downsample BN needs sum g*(y_ds - mean_ds) of its own: one
         sums-only pass over (g, y_ds), skipped with affine=False."""
         grads = {}
-        g = ops.avgpool_bwd(dfeat.contiguous(), ctx.last_hw)   # grad at the last block output
-        blocks = ctx.blocks
+        g = _backward_head(ctx, dfeat)   # grad at the last block output
         pending = None     # the fused dgrad's partial sums of g (None: g is unmasked)
-        ready = get_grad_ready(ctx.share)   # ddp.GradAllReduce.grads_ready, or None
-        while blocks:
-            blk, brec = blocks.pop()
-            has_ds = blk.downsample is not None
-            r1, r2 = brec[0], brec[1]
-            rd = brec[2] if has_ds else None
-            r3 = brec[-1]
-            prev3 = blocks[-1][1][-1] if blocks else None
-            dy3 = dyd = None
+        for blk, brec, prev3 in _backward_blocks(ctx, grads, lambda recs: recs[-1]):
+            r1, r2, rd, r3 = brec   # (rd: None without a downsample)
+            has_ds = rd is not None
+            dyd = None
             if pending is None:
                 # g unmasked: mask (the block output's bits), dres in place, dy's and sums at once
-                s3 = _bn_wants_grad(r3["bn"])
-                mk = dict(mask=3, bits=r3["zbits"]) if r3.get("zbits") is not None else \
-                    dict(mask=1, z=r3["z"])
+                s3 = _bn_wants_grad(r3.bn)
+                mk = dict(mask=3, bits=r3.zbits) if r3.zbits is not None else \
+                    dict(mask=1, z=r3.z)
                 if has_ds:
-                    sums = s3 or _bn_wants_grad(rd["bn"])
+                    sums = s3 or _bn_wants_grad(rd.bn)
                     dy3, dyd, p3, pd, npp = ops.bn_frozen_bwd_ds(
-                        g, r3["y"], r3["scale"], r3["shift"], r3["mean"], rd["y"], rd["scale"],
-                        rd["mean"], dres_inplace=True, want_sums=sums, **mk)
+                        g, r3.y, r3.scale, r3.shift, r3.mean, rd.y, rd.scale, rd.mean,
+                        dres_inplace=True, want_sums=sums, **mk)
                     _frozen_affine(r3, (p3, npp) if sums else None, grads)
                     _frozen_affine(rd, (pd, npp) if sums else None, grads)
                 else:
-                    dy3, p3, npp = ops.bn_frozen_bwd(g, r3["y"], r3["scale"], r3["shift"],
-                                                     r3["mean"], dres_inplace=True, want_sums=s3,
-                                                     **mk)
+                    dy3, p3, npp = ops.bn_frozen_bwd(g, r3.y, r3.scale, r3.shift, r3.mean,
+                                                     dres_inplace=True, want_sums=s3, **mk)
                     _frozen_affine(r3, (p3, npp) if s3 else None, grads)
-                dz2, _, fz2 = _frozen_unit_bwd(r3, None, grads, dy=dy3, fuse_prev=r2)
+                dz2, fz2 = _frozen_dy_bwd(r3, dy3, grads, fuse_prev=r2)
                 del dy3
             else:
-                if has_ds and _bn_wants_grad(rd["bn"]):
-                    _, pd, npp = ops.bn_frozen_bwd(g, rd["y"], rd["scale"], rd["shift"],
-                                                   rd["mean"], mask=0, want_dy=False)
+                if has_ds and _bn_wants_grad(rd.bn):
+                    _, pd, npp = ops.bn_frozen_bwd(g, rd.y, rd.scale, rd.shift, rd.mean, mask=0,
+                                                   want_dy=False)
                     _frozen_affine(rd, (pd, npp), grads)
-                dz2, _, fz2 = _frozen_unit_bwd(r3, g, grads, parts=pending, fuse_prev=r2)
+                dz2, fz2 = _frozen_unit_bwd(r3, g, grads, parts=pending, fuse_prev=r2)
             dres = g   # masked: the identity branch's gradient
-            dz1, _, fz1 = _frozen_unit_bwd(r2, dz2, grads, parts=fz2, fuse_prev=r1)
+            dz1, fz1 = _frozen_unit_bwd(r2, dz2, grads, parts=fz2, fuse_prev=r1)
             del dz2
             if has_ds:
-                dx, _, _ = _frozen_unit_bwd(rd, dres, grads, dy=dyd)
-                del dyd
-                dx, _, pending = _frozen_unit_bwd(r1, dz1, grads, parts=fz1, dx_out=dx,
-                                                  dx_beta=1.0, fuse_prev=prev3)
-            else:
-                dx, _, pending = _frozen_unit_bwd(r1, dz1, grads, parts=fz1, dx_out=dres,
-                                                  dx_beta=1.0, fuse_prev=prev3)
+                if dyd is not None:
+                    dres, _ = _frozen_dy_bwd(rd, dyd, grads)
+                    del dyd
+                else:
+                    dres, _ = _frozen_unit_bwd(rd, dres, grads)
+            g, pending = _frozen_unit_bwd(r1, dz1, grads, parts=fz1, dx_out=dres, dx_beta=1.0,
+                                          fuse_prev=prev3)
             del dz1, brec, dres
-            g = dx
-            if ready is not None:   # this block's parameter grads are final: start their exchange
-                ready([(p, grads[p]) for p in blk.parameters() if p in grads])
-        am, stem_hw = ctx.pool
+        am, _ = ctx.pool
         st = ctx.stem[0]
-        ss = _bn_wants_grad(st["bn"])
-        dy0, p0, np0 = ops.bn_frozen_bwd_maxpool(g, am, st["y"], st["scale"], st["shift"],
-                                                 st["mean"], want_sums=ss)
+        ss = _bn_wants_grad(st.bn)
+        dy0, p0, np0 = ops.bn_frozen_bwd_maxpool(g, am, st.y, st.scale, st.shift, st.mean,
+                                                 want_sums=ss)
         _frozen_affine(st, (p0, np0) if ss else None, grads)
-        _frozen_unit_bwd(st, None, grads, dy=dy0, need_dx=False)
-        out = [grads.get(p) for p in ctx.params]
-        ctx.blocks = ctx.stem = None
-        return (None, None, None) + tuple(out)
+        _frozen_dy_bwd(st, dy0, grads, need_dx=False)
+        return _backward_tail(ctx, grads)
 
 
 _CHILD_NAMES = ("conv1", "bn1", "relu", "maxpool", "layer1", "layer2", "layer3", "layer4",
@@ -819,7 +871,7 @@ class ResNet50Share(nn.Sequential):
         if precision not in ("fp32", "bf16", BWD16):
             raise ValueError("precision must be 'fp32', 'bf16' or 'bf16-bwd', got %r" % (precision,))
         self.precision = precision
-        # eval mode under precision "bf16", opt-in: bf16 activations (TrunkFn._forward i16; the
+        # eval mode under precision "bf16", opt-in: bf16 activations (TrunkFn._forward_eval i16; the
         # default keeps every eval path's fp32 activations and bits)
         self.infer_act16 = False
         # frozen BatchNorm (tmrnet_amd.freeze_bn): the BN modules stay in eval mode whatever
