@@ -53,6 +53,8 @@ Entry point -> kernels / template rungs reached:
                          (c/8 a power of two, aligned), stem_bwd_apply<float | __bf16> (else)
   tmr_bn_bwd_maxpool_a16 stem_bwd_partial_pooled<__bf16>, stem_bwd_apply8q<__bf16, __bf16>,
                          stem_bwd_apply<__bf16, __bf16>
+  tmr_bn_frozen_bwd_ds   bn_frozen_bwd8_k<0 | 2, true> (every other frozen rung:
+                         tests/test_frozen_bn_gpu.py; all 103: profiles/bn_dispatch/rungs.md)
 """
 import ctypes
 import functools
@@ -571,6 +573,29 @@ def test_bwd_parts_ds(dev, poison, rows, c, bf16):
         else:
             assert rel_err(dy, dy64) < E_BWD
         assert rel_err(dgm, dg64) < E_BWD and rel_err(dbt, db64) < E_BWD
+
+
+@gpu
+@pytest.mark.parametrize("mask", [0, 2])
+def test_frozen_bwd_ds_mask(dev, poison, mask):
+    """tmr_bn_frozen_bwd_ds with mask 2 (bn_frozen_bwd8_k<2, true>, the one rung of bn.hip that no
+    other test reaches, profiles/bn_dispatch/rungs.md) and mask 0 (<0, true>, elsewhere run but not
+    compared): g as it is or masked by y * scale + shift > 0, then dy = g scale, dy_ds = g scale_ds
+    and the partial sums of g, g (y - mean), g (y_ds - mean_ds)."""
+    rows, c = 3, 8
+    k = _bwd_case(rows, c)
+    gm, _ = _masked(k, "", mask)
+    f = lambda n: up(k[n], dev)
+    # (gamma_d serves as the downsample BN's scale: an arbitrary fp32 vector)
+    dy, dyd, parts, parts_d, nparts = ops.bn_frozen_bwd_ds(
+        f("dz"), f("y"), f("scale"), f("shift"), f("mean"), f("yd"), f("gamma_d"), f("mean_d"), mask=mask)
+    assert no_nan(dy) and no_nan(dyd)
+    assert rel_err(dy, gm * k["scale"]) < E_BWD and rel_err(dyd, gm * k["gamma_d"]) < E_BWD
+    for p, y, mean in ((parts, "y", "mean"), (parts_d, "yd", "mean_d")):
+        assert p.shape == (nparts, c, 2) and no_nan(p)
+        sums = p.double().sum(0)
+        assert rel_err(sums[:, 0], gm.sum(0)) < E_BWD
+        assert rel_err(sums[:, 1], (gm * (k[y] - k[mean])).sum(0)) < E_BWD
 
 
 # ------------------------------------------------------------------ 5. stem

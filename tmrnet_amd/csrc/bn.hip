@@ -1058,9 +1058,6 @@ __global__ __launch_bounds__(NT) void stem_bwd_apply8q(const PoolGeo pg, int h, 
 // 12 B per element at 4.8 TB/s, the 8-wide BN passes at 5.6-5.9).  Same arithmetic per element:
 // z and the bits identical to bn_apply_bits_k's.  The loop runs whole waves (the bit words are
 // gathered across 4 lanes).
-#ifndef TMR_BN_BITS8
-#define TMR_BN_BITS8 1   // 0: the 4-wide form only (A/B build)
-#endif
 // DUAL (the fp32-forward / bf16-backward step, tmr_bn_apply_bits_dual): also a bf16 (RNE) copy z16
 // of z, one 16-B store per group -- the block output as the next convs' wgrad operand.
 template <bool RES, bool DUAL = false>
@@ -1188,6 +1185,231 @@ int ew_blocks(long n4) {
   return (int)(b > 0 ? b : 1);
 }
 
+// ---- host dispatch layer ------------------------------------------------------
+// A run-time flag becomes a template argument by reaching a generic lambda as a
+// std::integral_constant: with_bool(relu, [&](auto RELU) { ... kernel<RELU> ... }).  Only the tags
+// a call site hands on are instantiated, so a site that collapses a combination (write-back only
+// where there is a mask) says so in its template argument.  Everything inlines.
+template <bool B> using Bool = std::bool_constant<B>;
+template <int I> using Int = std::integral_constant<int, I>;
+
+template <typename F>
+auto with_bool(bool b, F&& f) {
+  return b ? f(Bool<true>{}) : f(Bool<false>{});
+}
+template <typename F>
+auto with_bools(bool a, bool b, F&& f) {
+  return with_bool(a, [&](auto A) { return with_bool(b, [&](auto B) { return f(A, B); }); });
+}
+// v in [0, N)
+template <int N, typename F>
+auto with_int(int v, F&& f) {
+  if constexpr (N == 1) return f(Int<0>{});
+  else return v == N - 1 ? f(Int<N - 1>{}) : with_int<N - 1>(v, f);
+}
+template <int N, typename F>
+auto with_int_bool(int v, bool b, F&& f) {
+  return with_int<N>(v, [&](auto I) { return with_bool(b, [&](auto B) { return f(I, B); }); });
+}
+
+template <typename T> struct arg_of { using type = T; };
+// One launch and TMR_CHECK_LAUNCH's test: 0, or 2 with "<name>: launch failed: ..." set.  The
+// arguments convert implicitly to the kernel's parameter types (nullptr, an int for a long); a
+// kernel's default arguments do not reach a function pointer and are passed.
+template <typename... KA>
+int launch(const char* name, void (*k)(KA...), dim3 grid, dim3 block, hipStream_t stream,
+           typename arg_of<KA>::type... a) {
+  hipLaunchKernelGGL(k, grid, block, 0, stream, a...);
+  TMR_CHECK_LAUNCH(name);
+  return 0;
+}
+
+// every pointer 16-B aligned (null counts as aligned)
+template <typename... P>
+bool aligned16(const P*... p) {
+  return ((uintptr_t(0) | ... | (uintptr_t)p) & 15) == 0;
+}
+// the 8-wide forms' condition: 8 channels per thread in 16-B pieces (else the 4-wide forms)
+template <typename... P>
+bool wide8(int c, const P*... p) {
+  return c % 8 == 0 && aligned16(p...);
+}
+
+// the element-wise grid over rows x c in groups of w = 4 or 8 channels
+struct Ew {
+  long n;   // groups (n4 / n8)
+  int nb;   // blocks
+  int cw;   // groups per row (c / 4, c / 8)
+};
+Ew ew_grid(long rows, int c, int w) {
+  const long n = rows * c / w;
+  return {n, ew_blocks(n), c / w};
+}
+
+// ---- shared stages --------------------------------------------------------------------------
+// level 1 of the slab reduction of per-block partials into ws (KIND as parts_slab_k)
+template <int KIND>
+int parts_slabs(const SlabPlan& sp, const void* parts, int nparts, int c, void* ws,
+                hipStream_t stream) {
+  return launch("bn_parts_slab", parts_slab_k<KIND>, dim3(sp.groups, sp.nslabs), 256, stream,
+                parts, nparts, c, sp.rows, (double*)ws);
+}
+
+// The BatchNorm backward's reduction from a fused dgrad's partials: dgamma, dbeta and the
+// coefficients of dy = A*g + B*y + C, 3 * c floats [A | B | C] in ws at
+// tmr_bn_parts_coef_offset(nparts, c).  -> the coefficients, nullptr after a failed launch.
+float* parts_coef(const void* parts, int nparts, int rows, int c, const float* mean,
+                  const float* inv, const float* gamma, float* dgamma, float* dbeta, void* ws,
+                  hipStream_t stream) {
+  const SlabPlan sp = slab_plan(nparts, c);
+  float* coef = (float*)((char*)ws + slab_ws_bytes(nparts, c));
+  if (parts_slabs<1>(sp, parts, nparts, c, ws, stream)) return nullptr;
+  if (launch("bn_bwd_final_slabs", bwd_final_slabs_k, sp.groups, SLAB_CH * SLAB_PH, stream,
+             (const double*)ws, sp.nslabs, rows, c, mean, inv, gamma, dgamma, dbeta, coef))
+    return nullptr;
+  return coef;
+}
+
+// the workspace of a reduction over rows (ws_need): [nrb][c][2] double partials, then [A | B | C]
+struct RowWs {
+  Plan p;
+  double* part;
+  float* coef;
+};
+RowWs row_ws(int rows, int c, void* ws) {
+  const Plan p = make_plan(rows, c);
+  return {p, (double*)ws, (float*)((char*)ws + (size_t)p.nrb * c * 2 * sizeof(double))};
+}
+int bwd_final(const RowWs& r, int rows, int c, const float* mean, const float* inv,
+              const float* gamma, float* dgamma, float* dbeta, hipStream_t stream) {
+  return launch("bn_bwd_final", bn_bwd_final, c, NT, stream, r.part, r.p.nrb, rows, c, mean, inv,
+                gamma, dgamma, dbeta, r.coef);
+}
+
+// The BatchNorm backward's reduction over the rows of (g, y): bn_bwd_partial<MASK, WB> (MASK: the
+// ReLU mask applied to g on the way, WB: the masked g written back), then bn_bwd_final: dgamma,
+// dbeta and [A | B | C] behind the partials in ws.  -> the coefficients, nullptr after a failed
+// launch.
+template <int MASK, bool WB, typename TG, typename TY>
+float* rows_coef(const char* name, TG* g, const TY* y, typename arg_of<const TY*>::type z,
+                 const float* scale,
+                 const float* shift, const float* mean, const float* inv, const float* gamma,
+                 float* dgamma, float* dbeta, int rows, int c, void* ws, hipStream_t stream) {
+  const RowWs r = row_ws(rows, c, ws);
+  if (launch(name, bn_bwd_partial<MASK, WB, TY, TG>, dim3(r.p.nrb, r.p.cblocks), NT, stream, g, y, z,
+             scale, shift, mean, rows, c, r.p.rpb, r.p.cthreads, r.part))
+    return nullptr;
+  if (bwd_final(r, rows, c, mean, inv, gamma, dgamma, dbeta, stream)) return nullptr;
+  return r.coef;
+}
+
+// dy = A*g + B*y + C of an fp32 g that needs no mask: 8 channels per thread where wide8 holds
+// (bf16 y: bn_bwd_apply8_a16), else bn_bwd_apply<0, false> (the same fmaf sequence)
+template <typename TY, typename TD>
+int apply_coef(const float* g, const TY* y, const float* coef, TD* dy, int rows, int c,
+               hipStream_t stream) {
+  if (wide8(c, g, y, dy)) {
+    const Ew e = ew_grid(rows, c, 8);
+    if constexpr (std::is_same_v<TY, __bf16>)
+      return launch("bn_bwd_apply", bn_bwd_apply8_a16<float>, e.nb, NT, stream, g, y, coef, dy,
+                    e.n, e.cw);
+    else
+      return launch("bn_bwd_apply", bn_bwd_apply8_k<float, TY, TD>, e.nb, NT, stream, g, y, coef,
+                    dy, e.n, e.cw);
+  }
+  const Ew e = ew_grid(rows, c, 4);
+  return launch("bn_bwd_apply", bn_bwd_apply<0, false, TD, TY>, e.nb, NT, stream, g, y, nullptr,
+                nullptr, nullptr, coef, dy, nullptr, e.n, e.cw);
+}
+
+PoolGeo pool_geo(const float* dyp, const uint8_t* argmax, int h, int w, int ho, int wo) {
+  PoolGeo pg;
+  pg.dyp = dyp; pg.am = (const uchar4*)argmax;
+  pg.dHW = make_fastdiv((uint32_t)(h * w)); pg.dW = make_fastdiv((uint32_t)w);
+  pg.ho = ho; pg.wo = wo;
+  return pg;
+}
+
+// tmr_bn_bwd(_x) (TY float) and tmr_bn_bwd_a16 (TY, TD __bf16): the row reduction, then the apply
+template <typename TY, typename TD>
+int bn_bwd_impl(const char* name, const float* dz, const TY* y, const TY* z, const float* scale,
+                const float* shift, const float* save_mean, const float* save_invstd,
+                const float* gamma, TD* dy, float* dres, float* dgamma, float* dbeta, int rows,
+                int c, int relu, void* ws, size_t ws_bytes, hipStream_t stream) {
+  TMR_CHECK_ARG(c % 4 == 0 && c >= 4, "%s: channels %d must be a multiple of 4", name, c);
+  TMR_CHECK_ARG(rows > 0, "%s: empty input", name);
+  TMR_CHECK_ARG(plan_covers(c), "%s: unsupported channel count %d", name, c);
+  TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "%s: workspace too small", name);
+  TMR_CHECK_ARG(!relu || z || (scale && shift),
+                "%s: relu backward needs the saved output z or the forward scale/shift", name);
+  int mask = relu ? (z ? 1 : 2) : 0;
+  // in-place identity-branch gradient (dres == dz): pass 1 masks dz itself -- a write-back only
+  // where there is a mask -- and pass 2 reads it unmasked
+  const bool inplace = dres == dz;
+  const float* coef = with_int_bool<3>(mask, inplace, [&](auto M, auto WB) {
+    return rows_coef<M, (M != 0 && WB)>("bn_bwd_partial", const_cast<float*>(dz), y, z, scale,
+                                        shift, save_mean, save_invstd, gamma, dgamma, dbeta, rows,
+                                        c, ws, stream);
+  });
+  if (!coef) return 2;
+  if (inplace) {
+    mask = 0;
+    dres = nullptr;
+  }
+  if constexpr (std::is_same_v<TY, __bf16>) {
+    // no mask left to apply (the downsample branch's BN, or a mask already written back): the
+    // 8-wide apply of the parts path (same coefficients, same fmaf sequence)
+    if (!dres && mask == 0 && wide8(c, dz, y, dy)) return apply_coef(dz, y, coef, dy, rows, c, stream);
+  }
+  const Ew e = ew_grid(rows, c, 4);
+  return with_int_bool<3>(mask, dres != nullptr, [&](auto M, auto DRES) {
+    return launch("bn_bwd_apply", bn_bwd_apply<M, DRES, TD, TY>, e.nb, NT, stream, dz, y, z, scale,
+                  shift, coef, dy, dres, e.n, e.cw);
+  });
+}
+
+// tmr_bn_bwd_maxpool(_x) (TY float) and tmr_bn_bwd_maxpool_a16 (TY, TD __bf16)
+template <typename TY, typename TD>
+int bn_bwd_maxpool_impl(const char* name, const float* dyp, const uint8_t* argmax, int n, int h,
+                        int w, int ho, int wo, const TY* y, const float* scale, const float* shift,
+                        const float* save_mean, const float* save_invstd, const float* gamma,
+                        TD* dy, float* dgamma, float* dbeta, int c, void* ws, size_t ws_bytes,
+                        hipStream_t stream) {
+  const long rows_l = (long)n * h * w;
+  TMR_CHECK_ARG(c % 4 == 0 && c >= 4 && rows_l > 0 && rows_l < 0x7fffffffL,
+                "%s: bad shape n=%d h=%d w=%d c=%d", name, n, h, w, c);
+  TMR_CHECK_ARG(ho == (h + 2 - 3) / 2 + 1 && wo == (w + 2 - 3) / 2 + 1,
+                "%s: pooled %dx%d is not MaxPool2d(3,2,1) of %dx%d", name, ho, wo, h, w);
+  const int rows = (int)rows_l;
+  TMR_CHECK_ARG(plan_covers(c), "%s: unsupported channel count %d", name, c);
+  TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "%s: workspace too small", name);
+  const PoolGeo pg = pool_geo(dyp, argmax, h, w, ho, wo);
+  // partials over the pooled rows (fewer than the input rows: the workspace of `rows` suffices)
+  const int prows = n * ho * wo;
+  const RowWs r = row_ws(prows, c, ws);
+  if (const int rc = launch("stem_bwd_partial_pooled", stem_bwd_partial_pooled<TY>,
+                            dim3(r.p.nrb, r.p.cblocks), NT, stream, pg, h, w, y, scale, shift,
+                            save_mean, prows, c, r.p.rpb, r.p.cthreads,
+                            make_fastdiv((uint32_t)(ho * wo)), make_fastdiv((uint32_t)wo), r.part))
+    return rc;
+  if (const int rc = bwd_final(r, rows, c, save_mean, save_invstd, gamma, dgamma, dbeta, stream))
+    return rc;
+  const Ew e = ew_grid(rows_l, c, 4);
+  const int c8 = c / 8;
+  // 8 channels per thread, per 2x2 input quad (its candidate pooled outputs gathered once; the
+  // per-pixel form it replaced was bound by 2.25 gathers per pixel), else one pixel and 4 channels
+  if (wide8(c, dyp, y, dy) && (c8 & (c8 - 1)) == 0 && e.n / 2 < 0x7fffffffL &&
+      ((uintptr_t)argmax & 7) == 0) {
+    const int qh = (h + 1) / 2, qw = (w + 1) / 2;
+    const int nq = n * qh * qw * c8;
+    return launch("stem_bwd_apply", stem_bwd_apply8q<TY, TD>, ew_blocks(nq), NT, stream, pg, h, w,
+                  make_fastdiv((uint32_t)(qh * qw)), make_fastdiv((uint32_t)qw), y, scale, shift,
+                  r.coef, dy, nq, __builtin_ctz(c8));
+  }
+  return launch("stem_bwd_apply", stem_bwd_apply<TD, TY>, e.nb, NT, stream, pg, y, scale, shift,
+                r.coef, dy, e.n, e.cw);
+}
+
 }  // namespace
 
 TMR_API size_t tmr_bn_ws_bytes(int rows, int c) {
@@ -1207,11 +1429,11 @@ TMR_API int tmr_bn_fwd_stats(const float* y, int rows, int c, const float* gamma
   TMR_CHECK_ARG(rows > 0, "tmr_bn_fwd_stats: empty input");
   TMR_CHECK_ARG(plan_covers(c), "tmr_bn_fwd_stats: unsupported channel count %d", c);
   TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "tmr_bn_fwd_stats: workspace too small");
-  Plan p = make_plan(rows, c);
+  const Plan p = make_plan(rows, c);
   float4* part = (float4*)ws;
-  hipLaunchKernelGGL(bn_stats_partial, dim3(p.nrb, p.cblocks), dim3(NT), 0, stream, y, rows, c,
-                     p.rpb, p.cthreads, part);
-  TMR_CHECK_LAUNCH("bn_stats_partial");
+  if (const int rc = launch("bn_stats_partial", bn_stats_partial, dim3(p.nrb, p.cblocks), NT,
+                            stream, y, rows, c, p.rpb, p.cthreads, part))
+    return rc;
   return tmr_bn_finalize(part, p.nrb, c, gamma, beta, running_mean, running_var, momentum, eps,
                          save_mean, save_invstd, scale, shift, stream);
 }
@@ -1221,11 +1443,9 @@ TMR_API int tmr_bn_finalize(const void* partials, int nparts, int c, const float
                             float momentum, float eps, float* save_mean, float* save_invstd,
                             float* scale, float* shift, hipStream_t stream) {
   TMR_CHECK_ARG(nparts > 0 && c > 0, "tmr_bn_finalize: empty partials");
-  hipLaunchKernelGGL(bn_finalize_k, dim3(c), dim3(NT), 0, stream, (const float4*)partials,
-                     nparts, c, gamma, beta, running_mean, running_var, momentum, eps, save_mean,
-                     save_invstd, scale, shift);
-  TMR_CHECK_LAUNCH("bn_finalize");
-  return 0;
+  return launch("bn_finalize", bn_finalize_k, c, NT, stream, (const float4*)partials, nparts, c,
+                gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd,
+                scale, shift);
 }
 
 TMR_API size_t tmr_bn_parts_ws_bytes(int nparts, int c) {
@@ -1252,24 +1472,17 @@ TMR_API int tmr_bn_finalize_ws(const void* partials, int nparts, int c, const fl
   TMR_CHECK_ARG(nparts > 0 && c > 0, "tmr_bn_finalize_ws: empty partials");
   TMR_CHECK_ARG(ws && ws_bytes >= slab_ws_bytes(nparts, c), "tmr_bn_finalize_ws: workspace too small");
   const SlabPlan p = slab_plan(nparts, c);
-  hipLaunchKernelGGL(parts_slab_k<0>, dim3(p.groups, p.nslabs), dim3(256), 0, stream, partials,
-                     nparts, c, p.rows, (double*)ws);
-  TMR_CHECK_LAUNCH("bn_parts_slab");
-  hipLaunchKernelGGL(finalize_slabs_k, dim3(p.groups), dim3(SLAB_CH * SLAB_PH), 0, stream,
-                     (const double*)ws, p.nslabs, (const float4*)partials, c, gamma, beta,
-                     running_mean, running_var, momentum, eps, save_mean, save_invstd, scale,
-                     shift);
-  TMR_CHECK_LAUNCH("bn_finalize_slabs");
-  return 0;
+  if (const int rc = parts_slabs<0>(p, partials, nparts, c, ws, stream)) return rc;
+  return launch("bn_finalize_slabs", finalize_slabs_k, p.groups, SLAB_CH * SLAB_PH, stream,
+                (const double*)ws, p.nslabs, (const float4*)partials, c, gamma, beta, running_mean,
+                running_var, momentum, eps, save_mean, save_invstd, scale, shift);
 }
 
 TMR_API int tmr_bn_eval_params(const float* gamma, const float* beta, const float* running_mean,
                                const float* running_var, float eps, int c, float* scale,
                                float* shift, hipStream_t stream) {
-  hipLaunchKernelGGL(bn_eval_params_k, dim3(cdiv(c, 256)), dim3(256), 0, stream, gamma, beta,
-                     running_mean, running_var, eps, c, scale, shift);
-  TMR_CHECK_LAUNCH("bn_eval_params");
-  return 0;
+  return launch("bn_eval_params", bn_eval_params_k, cdiv(c, 256), 256, stream, gamma, beta,
+                running_mean, running_var, eps, c, scale, shift);
 }
 
 TMR_API int tmr_bn_apply(const float* y, const float* scale, const float* shift,
@@ -1282,26 +1495,16 @@ TMR_API int tmr_bn_apply_x(const float* y, const float* scale, const float* shif
                            const float* residual, void* zv, int rows, int c, int relu,
                            int out_bf16, hipStream_t stream) {
   TMR_CHECK_ARG(c % 4 == 0, "tmr_bn_apply: channels %d must be a multiple of 4", c);
-  long n4 = (long)rows * c / 4;
-  int nb = ew_blocks(n4);
-  int c4 = c / 4;
-  if (out_bf16) {
-    TMR_CHECK_ARG(!residual, "tmr_bn_apply_x: a bf16 output is for conv-operand-only tensors (no residual)");
-    if (relu) hipLaunchKernelGGL((bn_apply_k<false, true, __bf16>), dim3(nb), dim3(NT), 0, stream, y, scale, shift, residual, (__bf16*)zv, n4, c4);
-    else hipLaunchKernelGGL((bn_apply_k<false, false, __bf16>), dim3(nb), dim3(NT), 0, stream, y, scale, shift, residual, (__bf16*)zv, n4, c4);
-    TMR_CHECK_LAUNCH("bn_apply");
-    return 0;
-  }
-  float* z = (float*)zv;
-  if (residual) {
-    if (relu) hipLaunchKernelGGL((bn_apply_k<true, true>), dim3(nb), dim3(NT), 0, stream, y, scale, shift, residual, z, n4, c4);
-    else hipLaunchKernelGGL((bn_apply_k<true, false>), dim3(nb), dim3(NT), 0, stream, y, scale, shift, residual, z, n4, c4);
-  } else {
-    if (relu) hipLaunchKernelGGL((bn_apply_k<false, true>), dim3(nb), dim3(NT), 0, stream, y, scale, shift, residual, z, n4, c4);
-    else hipLaunchKernelGGL((bn_apply_k<false, false>), dim3(nb), dim3(NT), 0, stream, y, scale, shift, residual, z, n4, c4);
-  }
-  TMR_CHECK_LAUNCH("bn_apply");
-  return 0;
+  TMR_CHECK_ARG(!out_bf16 || !residual,
+                "tmr_bn_apply_x: a bf16 output is for conv-operand-only tensors (no residual)");
+  const Ew e = ew_grid(rows, c, 4);
+  return with_bools(residual, relu, [&](auto RES, auto RELU) {
+    if (out_bf16)   // (no residual: RES is false here)
+      return launch("bn_apply", bn_apply_k<false, RELU, __bf16>, e.nb, NT, stream, y, scale, shift,
+                    residual, (__bf16*)zv, e.n, e.cw, nullptr);
+    return launch("bn_apply", bn_apply_k<RES, RELU>, e.nb, NT, stream, y, scale, shift, residual,
+                  (float*)zv, e.n, e.cw, nullptr);
+  });
 }
 
 TMR_API int tmr_bn_apply2(const float* y, const float* scale, const float* shift, const float* yr,
@@ -1316,22 +1519,31 @@ TMR_API int tmr_bn_apply2_x(const float* y, const float* scale, const float* shi
   TMR_CHECK_ARG(c % 4 == 0, "tmr_bn_apply2: channels %d must be a multiple of 4", c);
   TMR_CHECK_ARG(y && scale && shift && yr && rscale && rshift && z, "tmr_bn_apply2: null operand");
   TMR_CHECK_ARG(yr != z, "tmr_bn_apply2: the branch input must not alias z");
-  const long n4 = (long)rows * c / 4;
-  __bf16* h = (__bf16*)z16;
-  if (relu && h)
-    hipLaunchKernelGGL((bn_apply2_k<true, true>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, y, scale,
-                       shift, yr, rscale, rshift, z, n4, c / 4, h);
-  else if (relu)
-    hipLaunchKernelGGL((bn_apply2_k<true>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, y, scale, shift,
-                       yr, rscale, rshift, z, n4, c / 4, h);
-  else if (h)
-    hipLaunchKernelGGL((bn_apply2_k<false, true>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, y, scale,
-                       shift, yr, rscale, rshift, z, n4, c / 4, h);
-  else
-    hipLaunchKernelGGL((bn_apply2_k<false>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, y, scale, shift,
-                       yr, rscale, rshift, z, n4, c / 4, h);
-  TMR_CHECK_LAUNCH("bn_apply2");
-  return 0;
+  const Ew e = ew_grid(rows, c, 4);
+  return with_bools(relu, z16, [&](auto RELU, auto DUAL) {
+    return launch("bn_apply2", bn_apply2_k<RELU, DUAL>, e.nb, NT, stream, y, scale, shift, yr,
+                  rscale, rshift, z, e.n, e.cw, (__bf16*)z16);
+  });
+}
+
+// The forward BN + ReLU with the ReLU mask as bits, fp32: a residual or (yr, rscale, rshift), the
+// downsample branch's BN on the fly, or neither.  8-wide where wide8 holds, else 4-wide: the same
+// z and bits.
+static int bn_apply_bits(const char* name, const float* y, const float* scale, const float* shift,
+                         const float* residual, const float* yr, const float* rscale,
+                         const float* rshift, float* z, uint32_t* bits, int rows, int c,
+                         hipStream_t stream) {
+  const bool w8 = wide8(c, y, residual, yr, z);
+  const Ew e = ew_grid(rows, c, w8 ? 8 : 4);
+  if (e.n == 0) return 0;
+  return with_bools(w8, residual, [&](auto W8, auto RES) {
+    if constexpr (W8)
+      return launch(name, bn_apply_bits8_k<RES>, e.nb, NT, stream, y, scale, shift, residual, yr,
+                    rscale, rshift, z, bits, e.n, e.cw, nullptr);
+    else
+      return launch(name, bn_apply_bits_k<RES, float>, e.nb, NT, stream, y, scale, shift, residual,
+                    yr, rscale, rshift, z, bits, e.n, e.cw);
+  });
 }
 
 TMR_API int tmr_bn_apply_bits(const float* y, const float* scale, const float* shift,
@@ -1339,23 +1551,8 @@ TMR_API int tmr_bn_apply_bits(const float* y, const float* scale, const float* s
                               hipStream_t stream) {
   TMR_CHECK_ARG(c % 4 == 0 && y && scale && shift && z && bits,
                 "tmr_bn_apply_bits: null operand or channels %d not a multiple of 4", c);
-  const long n4 = (long)rows * c / 4;
-  if (n4 == 0) return 0;
-  if (TMR_BN_BITS8 && c % 8 == 0 && (((uintptr_t)y | (uintptr_t)residual | (uintptr_t)z) & 15) == 0) {
-    if (residual)
-      hipLaunchKernelGGL((bn_apply_bits8_k<true>), dim3(ew_blocks(n4 / 2)), dim3(NT), 0, stream, y,
-                         scale, shift, residual, nullptr, nullptr, nullptr, z, bits, n4 / 2, c / 8);
-    else
-      hipLaunchKernelGGL((bn_apply_bits8_k<false>), dim3(ew_blocks(n4 / 2)), dim3(NT), 0, stream, y,
-                         scale, shift, nullptr, nullptr, nullptr, nullptr, z, bits, n4 / 2, c / 8);
-  } else if (residual)
-    hipLaunchKernelGGL((bn_apply_bits_k<true, float>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, y, scale,
-                       shift, residual, nullptr, nullptr, nullptr, z, bits, n4, c / 4);
-  else
-    hipLaunchKernelGGL((bn_apply_bits_k<false, float>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, y, scale,
-                       shift, nullptr, nullptr, nullptr, nullptr, z, bits, n4, c / 4);
-  TMR_CHECK_LAUNCH("bn_apply_bits");
-  return 0;
+  return bn_apply_bits("bn_apply_bits", y, scale, shift, residual, nullptr, nullptr, nullptr, z,
+                       bits, rows, c, stream);
 }
 
 TMR_API int tmr_bn_apply2_bits(const float* y, const float* scale, const float* shift,
@@ -1364,47 +1561,36 @@ TMR_API int tmr_bn_apply2_bits(const float* y, const float* scale, const float* 
   TMR_CHECK_ARG(c % 4 == 0 && y && scale && shift && yr && rscale && rshift && z && bits,
                 "tmr_bn_apply2_bits: null operand or channels %d not a multiple of 4", c);
   TMR_CHECK_ARG(yr != z, "tmr_bn_apply2_bits: the branch input must not alias z");
-  const long n4 = (long)rows * c / 4;
-  if (n4 == 0) return 0;
-  if (TMR_BN_BITS8 && c % 8 == 0 && (((uintptr_t)y | (uintptr_t)yr | (uintptr_t)z) & 15) == 0)
-    hipLaunchKernelGGL((bn_apply_bits8_k<false>), dim3(ew_blocks(n4 / 2)), dim3(NT), 0, stream, y,
-                       scale, shift, nullptr, yr, rscale, rshift, z, bits, n4 / 2, c / 8);
-  else
-    hipLaunchKernelGGL((bn_apply_bits_k<false, float>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, y, scale,
-                       shift, nullptr, yr, rscale, rshift, z, bits, n4, c / 4);
-  TMR_CHECK_LAUNCH("bn_apply2_bits");
-  return 0;
+  return bn_apply_bits("bn_apply2_bits", y, scale, shift, nullptr, yr, rscale, rshift, z, bits,
+                       rows, c, stream);
 }
 
 // The block outputs of the fp32-forward / bf16-backward step: tmr_bn_apply_bits / _apply2_bits
 // plus the bf16 copy of z in the same pass (the 8-wide kernel only: channel counts and alignments
 // it does not serve are refused -- the step's block outputs are all 8-channel multiples).
-static int bits_dual_ok(const char* name, int c, const void* y, const void* r, const void* z,
-                        const void* z16) {
-  TMR_CHECK_ARG(c % 8 == 0 && c >= 8, "%s: channels %d must be a multiple of 8", name, c);
-  TMR_CHECK_ARG((((uintptr_t)y | (uintptr_t)r | (uintptr_t)z | (uintptr_t)z16) & 15) == 0,
-                "%s: y / residual / z / z16 must be 16-B aligned", name);
-  return 0;
+static int bn_apply_bits_dual(const char* name, const float* y, const float* scale,
+                              const float* shift, const float* residual, const float* yr,
+                              const float* rscale, const float* rshift, float* z, void* z16,
+                              uint32_t* bits, int rows, int c, hipStream_t stream) {
+  TMR_CHECK_ARG(rows >= 0, "tmr_%s: negative rows", name);
+  TMR_CHECK_ARG(!yr || yr != z, "tmr_%s: the branch input must not alias z", name);
+  TMR_CHECK_ARG(c % 8 == 0 && c >= 8, "tmr_%s: channels %d must be a multiple of 8", name, c);
+  TMR_CHECK_ARG(aligned16(y, residual, yr, z, z16),
+                "tmr_%s: y / residual / z / z16 must be 16-B aligned", name);
+  const Ew e = ew_grid(rows, c, 8);
+  if (e.n == 0) return 0;
+  return with_bool(residual, [&](auto RES) {
+    return launch(name, bn_apply_bits8_k<RES, true>, e.nb, NT, stream, y, scale, shift, residual,
+                  yr, rscale, rshift, z, bits, e.n, e.cw, (__bf16*)z16);
+  });
 }
 
 TMR_API int tmr_bn_apply_bits_dual(const float* y, const float* scale, const float* shift,
                                    const float* residual, float* z, void* z16, uint32_t* bits,
                                    int rows, int c, hipStream_t stream) {
   TMR_CHECK_ARG(y && scale && shift && z && z16 && bits, "tmr_bn_apply_bits_dual: null operand");
-  TMR_CHECK_ARG(rows >= 0, "tmr_bn_apply_bits_dual: negative rows");
-  if (const int rc = bits_dual_ok("tmr_bn_apply_bits_dual", c, y, residual, z, z16)) return rc;
-  const long n8 = (long)rows * c / 8;
-  if (n8 == 0) return 0;
-  if (residual)
-    hipLaunchKernelGGL((bn_apply_bits8_k<true, true>), dim3(ew_blocks(n8)), dim3(NT), 0, stream, y,
-                       scale, shift, residual, nullptr, nullptr, nullptr, z, bits, n8, c / 8,
-                       (__bf16*)z16);
-  else
-    hipLaunchKernelGGL((bn_apply_bits8_k<false, true>), dim3(ew_blocks(n8)), dim3(NT), 0, stream, y,
-                       scale, shift, nullptr, nullptr, nullptr, nullptr, z, bits, n8, c / 8,
-                       (__bf16*)z16);
-  TMR_CHECK_LAUNCH("bn_apply_bits_dual");
-  return 0;
+  return bn_apply_bits_dual("bn_apply_bits_dual", y, scale, shift, residual, nullptr, nullptr,
+                            nullptr, z, z16, bits, rows, c, stream);
 }
 
 TMR_API int tmr_bn_apply2_bits_dual(const float* y, const float* scale, const float* shift,
@@ -1413,15 +1599,22 @@ TMR_API int tmr_bn_apply2_bits_dual(const float* y, const float* scale, const fl
                                     hipStream_t stream) {
   TMR_CHECK_ARG(y && scale && shift && yr && rscale && rshift && z && z16 && bits,
                 "tmr_bn_apply2_bits_dual: null operand");
-  TMR_CHECK_ARG(rows >= 0, "tmr_bn_apply2_bits_dual: negative rows");
-  TMR_CHECK_ARG(yr != z, "tmr_bn_apply2_bits_dual: the branch input must not alias z");
-  if (const int rc = bits_dual_ok("tmr_bn_apply2_bits_dual", c, y, yr, z, z16)) return rc;
-  const long n8 = (long)rows * c / 8;
-  if (n8 == 0) return 0;
-  hipLaunchKernelGGL((bn_apply_bits8_k<false, true>), dim3(ew_blocks(n8)), dim3(NT), 0, stream, y,
-                     scale, shift, nullptr, yr, rscale, rshift, z, bits, n8, c / 8, (__bf16*)z16);
-  TMR_CHECK_LAUNCH("bn_apply2_bits_dual");
-  return 0;
+  return bn_apply_bits_dual("bn_apply2_bits_dual", y, scale, shift, nullptr, yr, rscale, rshift, z,
+                            z16, bits, rows, c, stream);
+}
+
+// bf16 y, residual / yr and z (4-wide only)
+static int bn_apply_bits_a16(const char* name, const void* y, const float* scale,
+                             const float* shift, const void* residual, const void* yr,
+                             const float* rscale, const float* rshift, void* z, uint32_t* bits,
+                             int rows, int c, hipStream_t stream) {
+  const Ew e = ew_grid(rows, c, 4);
+  if (e.n == 0) return 0;
+  return with_bool(residual, [&](auto RES) {
+    return launch(name, bn_apply_bits_k<RES, __bf16>, e.nb, NT, stream, (const __bf16*)y, scale,
+                  shift, (const __bf16*)residual, (const __bf16*)yr, rscale, rshift, (__bf16*)z,
+                  bits, e.n, e.cw);
+  });
 }
 
 TMR_API int tmr_bn_apply_bits_a16(const void* y, const float* scale, const float* shift,
@@ -1429,18 +1622,8 @@ TMR_API int tmr_bn_apply_bits_a16(const void* y, const float* scale, const float
                                   hipStream_t stream) {
   TMR_CHECK_ARG(c % 4 == 0 && y && scale && shift && z && bits,
                 "tmr_bn_apply_bits_a16: null operand or channels %d not a multiple of 4", c);
-  const long n4 = (long)rows * c / 4;
-  if (n4 == 0) return 0;
-  const __bf16* yb = (const __bf16*)y;
-  if (residual)
-    hipLaunchKernelGGL((bn_apply_bits_k<true, __bf16>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, yb,
-                       scale, shift, (const __bf16*)residual, nullptr, nullptr, nullptr, (__bf16*)z,
-                       bits, n4, c / 4);
-  else
-    hipLaunchKernelGGL((bn_apply_bits_k<false, __bf16>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, yb,
-                       scale, shift, nullptr, nullptr, nullptr, nullptr, (__bf16*)z, bits, n4, c / 4);
-  TMR_CHECK_LAUNCH("bn_apply_bits_a16");
-  return 0;
+  return bn_apply_bits_a16("bn_apply_bits_a16", y, scale, shift, residual, nullptr, nullptr,
+                           nullptr, z, bits, rows, c, stream);
 }
 
 TMR_API int tmr_bn_apply2_bits_a16(const void* y, const float* scale, const float* shift,
@@ -1449,13 +1632,8 @@ TMR_API int tmr_bn_apply2_bits_a16(const void* y, const float* scale, const floa
   TMR_CHECK_ARG(c % 4 == 0 && y && scale && shift && yr && rscale && rshift && z && bits,
                 "tmr_bn_apply2_bits_a16: null operand or channels %d not a multiple of 4", c);
   TMR_CHECK_ARG(yr != z, "tmr_bn_apply2_bits_a16: the branch input must not alias z");
-  const long n4 = (long)rows * c / 4;
-  if (n4 == 0) return 0;
-  hipLaunchKernelGGL((bn_apply_bits_k<false, __bf16>), dim3(ew_blocks(n4)), dim3(NT), 0, stream,
-                     (const __bf16*)y, scale, shift, nullptr, (const __bf16*)yr, rscale, rshift,
-                     (__bf16*)z, bits, n4, c / 4);
-  TMR_CHECK_LAUNCH("bn_apply2_bits_a16");
-  return 0;
+  return bn_apply_bits_a16("bn_apply2_bits_a16", y, scale, shift, nullptr, yr, rscale, rshift, z,
+                           bits, rows, c, stream);
 }
 
 TMR_API int tmr_bn_apply_dual(const float* y, const float* scale, const float* shift,
@@ -1463,32 +1641,17 @@ TMR_API int tmr_bn_apply_dual(const float* y, const float* scale, const float* s
                               hipStream_t stream) {
   TMR_CHECK_ARG(c % 4 == 0, "tmr_bn_apply_dual: channels %d must be a multiple of 4", c);
   TMR_CHECK_ARG(y && scale && shift && z && z16, "tmr_bn_apply_dual: null operand");
-  const long n4 = (long)rows * c / 4;
-  const int nb = ew_blocks(n4), c4 = c / 4;
   __bf16* h = (__bf16*)z16;
   // 8 channels per thread (16-B pieces of z16 too), else the 4-wide form: the same values
-  if (c % 8 == 0 && (((uintptr_t)y | (uintptr_t)residual | (uintptr_t)z | (uintptr_t)z16) & 15) == 0) {
-    const long n8 = n4 / 2;
-    const int nb8 = ew_blocks(n8), c8 = c / 8;
-    if (residual) {
-      if (relu) hipLaunchKernelGGL((bn_apply_dual8_k<true, true>), dim3(nb8), dim3(NT), 0, stream, y, scale, shift, residual, z, h, n8, c8);
-      else hipLaunchKernelGGL((bn_apply_dual8_k<true, false>), dim3(nb8), dim3(NT), 0, stream, y, scale, shift, residual, z, h, n8, c8);
-    } else {
-      if (relu) hipLaunchKernelGGL((bn_apply_dual8_k<false, true>), dim3(nb8), dim3(NT), 0, stream, y, scale, shift, residual, z, h, n8, c8);
-      else hipLaunchKernelGGL((bn_apply_dual8_k<false, false>), dim3(nb8), dim3(NT), 0, stream, y, scale, shift, residual, z, h, n8, c8);
-    }
-    TMR_CHECK_LAUNCH("bn_apply_dual");
-    return 0;
-  }
-  if (residual) {
-    if (relu) hipLaunchKernelGGL((bn_apply_k<true, true, float, true>), dim3(nb), dim3(NT), 0, stream, y, scale, shift, residual, z, n4, c4, h);
-    else hipLaunchKernelGGL((bn_apply_k<true, false, float, true>), dim3(nb), dim3(NT), 0, stream, y, scale, shift, residual, z, n4, c4, h);
-  } else {
-    if (relu) hipLaunchKernelGGL((bn_apply_k<false, true, float, true>), dim3(nb), dim3(NT), 0, stream, y, scale, shift, residual, z, n4, c4, h);
-    else hipLaunchKernelGGL((bn_apply_k<false, false, float, true>), dim3(nb), dim3(NT), 0, stream, y, scale, shift, residual, z, n4, c4, h);
-  }
-  TMR_CHECK_LAUNCH("bn_apply_dual");
-  return 0;
+  const bool w8 = wide8(c, y, residual, z, z16);
+  const Ew e = ew_grid(rows, c, w8 ? 8 : 4);
+  return with_bools(residual, relu, [&](auto RES, auto RELU) {
+    if (w8)
+      return launch("bn_apply_dual", bn_apply_dual8_k<RES, RELU>, e.nb, NT, stream, y, scale,
+                    shift, residual, z, h, e.n, e.cw);
+    return launch("bn_apply_dual", bn_apply_k<RES, RELU, float, true>, e.nb, NT, stream, y, scale,
+                  shift, residual, z, e.n, e.cw, h);
+  });
 }
 
 TMR_API int tmr_bn_bwd(const float* dz, const float* y, const float* z, const float* scale,
@@ -1504,56 +1667,11 @@ TMR_API int tmr_bn_bwd_x(const float* dz, const float* y, const float* z, const 
                          const float* gamma, void* dyv, float* dres, float* dgamma, float* dbeta,
                          int rows, int c, int relu, void* ws, size_t ws_bytes, int out_bf16,
                          hipStream_t stream) {
-  TMR_CHECK_ARG(c % 4 == 0 && c >= 4, "tmr_bn_bwd: channels %d must be a multiple of 4", c);
-  TMR_CHECK_ARG(rows > 0, "tmr_bn_bwd: empty input");
-  TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd: unsupported channel count %d", c);
-  TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "tmr_bn_bwd: workspace too small");
-  TMR_CHECK_ARG(!relu || z || (scale && shift),
-                "tmr_bn_bwd: relu backward needs the saved output z or the forward scale/shift");
-  int mask = relu ? (z ? 1 : 2) : 0;
-  Plan p = make_plan(rows, c);
-  double* part = (double*)ws;
-  float* coef = (float*)((char*)ws + (size_t)p.nrb * c * 2 * sizeof(double));
-  const dim3 pg(p.nrb, p.cblocks);
-  float* dzw = const_cast<float*>(dz);
-  if (dres == dz) {
-    // in-place identity-branch gradient: pass 1 masks dz itself, pass 2 reads it unmasked
-    if (mask == 1)
-      hipLaunchKernelGGL((bn_bwd_partial<1, true>), pg, dim3(NT), 0, stream, dzw, y, z, scale, shift, save_mean, rows, c, p.rpb, p.cthreads, part);
-    else if (mask == 2)
-      hipLaunchKernelGGL((bn_bwd_partial<2, true>), pg, dim3(NT), 0, stream, dzw, y, z, scale, shift, save_mean, rows, c, p.rpb, p.cthreads, part);
-    else
-      hipLaunchKernelGGL((bn_bwd_partial<0>), pg, dim3(NT), 0, stream, dzw, y, z, scale, shift, save_mean, rows, c, p.rpb, p.cthreads, part);
-    mask = 0;
-    dres = nullptr;
-  } else if (mask == 1)
-    hipLaunchKernelGGL((bn_bwd_partial<1>), pg, dim3(NT), 0, stream, dzw, y, z, scale, shift, save_mean, rows, c, p.rpb, p.cthreads, part);
-  else if (mask == 2)
-    hipLaunchKernelGGL((bn_bwd_partial<2>), pg, dim3(NT), 0, stream, dzw, y, z, scale, shift, save_mean, rows, c, p.rpb, p.cthreads, part);
-  else
-    hipLaunchKernelGGL((bn_bwd_partial<0>), pg, dim3(NT), 0, stream, dzw, y, z, scale, shift, save_mean, rows, c, p.rpb, p.cthreads, part);
-  TMR_CHECK_LAUNCH("bn_bwd_partial");
-  hipLaunchKernelGGL(bn_bwd_final, dim3(c), dim3(NT), 0, stream, part, p.nrb, rows, c,
-                     save_mean, save_invstd, gamma, dgamma, dbeta, coef);
-  TMR_CHECK_LAUNCH("bn_bwd_final");
-  long n4 = (long)rows * c / 4;
-  int nb = ew_blocks(n4);
-  int c4 = c / 4;
-#define TMR_BN_APPLY(M, D)                                                                     \
-  if (out_bf16)                                                                                  \
-    hipLaunchKernelGGL((bn_bwd_apply<M, D, __bf16>), dim3(nb), dim3(NT), 0, stream, dz, y, z,    \
-                       scale, shift, coef, (__bf16*)dyv, dres, n4, c4);                          \
-  else                                                                                           \
-    hipLaunchKernelGGL((bn_bwd_apply<M, D>), dim3(nb), dim3(NT), 0, stream, dz, y, z, scale,     \
-                       shift, coef, (float*)dyv, dres, n4, c4)
-  if (dres) {
-    if (mask == 1) { TMR_BN_APPLY(1, true); } else if (mask == 2) { TMR_BN_APPLY(2, true); } else { TMR_BN_APPLY(0, true); }
-  } else {
-    if (mask == 1) { TMR_BN_APPLY(1, false); } else if (mask == 2) { TMR_BN_APPLY(2, false); } else { TMR_BN_APPLY(0, false); }
-  }
-#undef TMR_BN_APPLY
-  TMR_CHECK_LAUNCH("bn_bwd_apply");
-  return 0;
+  if (out_bf16)
+    return bn_bwd_impl("tmr_bn_bwd", dz, y, z, scale, shift, save_mean, save_invstd, gamma,
+                       (__bf16*)dyv, dres, dgamma, dbeta, rows, c, relu, ws, ws_bytes, stream);
+  return bn_bwd_impl("tmr_bn_bwd", dz, y, z, scale, shift, save_mean, save_invstd, gamma,
+                     (float*)dyv, dres, dgamma, dbeta, rows, c, relu, ws, ws_bytes, stream);
 }
 
 TMR_API int tmr_bn_bwd_maxpool(const float* dyp, const uint8_t* argmax, int n, int h, int w,
@@ -1566,13 +1684,6 @@ TMR_API int tmr_bn_bwd_maxpool(const float* dyp, const uint8_t* argmax, int n, i
                               save_invstd, gamma, dy, dgamma, dbeta, c, ws, ws_bytes, 0, stream);
 }
 
-static int bn_bwd_maxpool_impl(const float* dyp, const uint8_t* argmax, int n, int h, int w,
-                               int ho, int wo, const float* y, const float* scale,
-                               const float* shift, const float* save_mean,
-                               const float* save_invstd, const float* gamma, void* dyv,
-                               float* dgamma, float* dbeta, int c, void* ws, size_t ws_bytes,
-                               int out_bf16, float* coef_out, hipStream_t stream);
-
 TMR_API int tmr_bn_bwd_maxpool_x(const float* dyp, const uint8_t* argmax, int n, int h, int w,
                                  int ho, int wo, const float* y, const float* scale,
                                  const float* shift, const float* save_mean,
@@ -1581,65 +1692,13 @@ TMR_API int tmr_bn_bwd_maxpool_x(const float* dyp, const uint8_t* argmax, int n,
                                  int out_bf16, hipStream_t stream) {
   TMR_CHECK_ARG(c >= 4 && plan_covers(c), "tmr_bn_bwd_maxpool: unsupported channel count %d", c);
   TMR_CHECK_ARG(dyv, "tmr_bn_bwd_maxpool: null dy");
-  return bn_bwd_maxpool_impl(dyp, argmax, n, h, w, ho, wo, y, scale, shift, save_mean,
-                             save_invstd, gamma, dyv, dgamma, dbeta, c, ws, ws_bytes, out_bf16,
-                             nullptr, stream);
-}
-
-static int bn_bwd_maxpool_impl(const float* dyp, const uint8_t* argmax, int n, int h, int w,
-                               int ho, int wo, const float* y, const float* scale,
-                               const float* shift, const float* save_mean,
-                               const float* save_invstd, const float* gamma, void* dyv,
-                               float* dgamma, float* dbeta, int c, void* ws, size_t ws_bytes,
-                               int out_bf16, float* coef_out, hipStream_t stream) {
-  const long rows_l = (long)n * h * w;
-  TMR_CHECK_ARG(c % 4 == 0 && c >= 4 && rows_l > 0 && rows_l < 0x7fffffffL,
-                "tmr_bn_bwd_maxpool: bad shape n=%d h=%d w=%d c=%d", n, h, w, c);
-  TMR_CHECK_ARG(ho == (h + 2 - 3) / 2 + 1 && wo == (w + 2 - 3) / 2 + 1,
-                "tmr_bn_bwd_maxpool: pooled %dx%d is not MaxPool2d(3,2,1) of %dx%d", ho, wo, h, w);
-  const int rows = (int)rows_l;
-  TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd_maxpool: unsupported channel count %d", c);
-  TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "tmr_bn_bwd_maxpool: workspace too small");
-  PoolGeo pg;
-  pg.dyp = dyp; pg.am = (const uchar4*)argmax;
-  pg.dHW = make_fastdiv((uint32_t)(h * w)); pg.dW = make_fastdiv((uint32_t)w);
-  pg.ho = ho; pg.wo = wo;
-  // partials over the pooled rows (fewer than the input rows: the workspace of `rows` suffices)
-  const int prows = n * ho * wo;
-  Plan p = make_plan(prows, c);
-  double* part = (double*)ws;
-  float* coef = coef_out ? coef_out : (float*)((char*)ws + (size_t)p.nrb * c * 2 * sizeof(double));
-  hipLaunchKernelGGL(stem_bwd_partial_pooled<float>, dim3(p.nrb, p.cblocks), dim3(NT), 0, stream, pg, h, w,
-                     y, scale, shift, save_mean, prows, c, p.rpb, p.cthreads,
-                     make_fastdiv((uint32_t)(ho * wo)), make_fastdiv((uint32_t)wo), part);
-  TMR_CHECK_LAUNCH("stem_bwd_partial_pooled");
-  hipLaunchKernelGGL(bn_bwd_final, dim3(c), dim3(NT), 0, stream, part, p.nrb, rows, c,
-                     save_mean, save_invstd, gamma, dgamma, dbeta, coef);
-  TMR_CHECK_LAUNCH("bn_bwd_final");
-  if (!dyv) return 0;   // coefficients only: the stem's direct wgrad applies them on load
-  const long n4 = rows_l * c / 4;
-  const int c8 = c / 8;
-  // per 2x2 input quad, 8 channels per thread (stem_bwd_apply8q, as the bf16-activation step's
-  // stem; round 5 for fp32 y), else one pixel and 4 channels per thread
-  if (c % 8 == 0 && (c8 & (c8 - 1)) == 0 && n4 / 2 < 0x7fffffffL &&
-      (((uintptr_t)dyp | (uintptr_t)y | (uintptr_t)dyv) & 15) == 0 && ((uintptr_t)argmax & 7) == 0) {
-    const int qh = (h + 1) / 2, qw = (w + 1) / 2;
-    const int nq = n * qh * qw * c8;
-    const FastDiv dqhw = make_fastdiv((uint32_t)(qh * qw)), dqw = make_fastdiv((uint32_t)qw);
-    if (out_bf16)
-      hipLaunchKernelGGL((stem_bwd_apply8q<float, __bf16>), dim3(ew_blocks(nq)), dim3(NT), 0, stream,
-                         pg, h, w, dqhw, dqw, y, scale, shift, coef, (__bf16*)dyv, nq, __builtin_ctz(c8));
-    else
-      hipLaunchKernelGGL((stem_bwd_apply8q<float, float>), dim3(ew_blocks(nq)), dim3(NT), 0, stream,
-                         pg, h, w, dqhw, dqw, y, scale, shift, coef, (float*)dyv, nq, __builtin_ctz(c8));
-  } else if (out_bf16)
-    hipLaunchKernelGGL(stem_bwd_apply<__bf16>, dim3(ew_blocks(n4)), dim3(NT), 0, stream, pg, y, scale,
-                       shift, coef, (__bf16*)dyv, n4, c / 4);
-  else
-    hipLaunchKernelGGL(stem_bwd_apply<float>, dim3(ew_blocks(n4)), dim3(NT), 0, stream, pg, y, scale,
-                       shift, coef, (float*)dyv, n4, c / 4);
-  TMR_CHECK_LAUNCH("stem_bwd_apply");
-  return 0;
+  if (out_bf16)
+    return bn_bwd_maxpool_impl("tmr_bn_bwd_maxpool", dyp, argmax, n, h, w, ho, wo, y, scale, shift,
+                               save_mean, save_invstd, gamma, (__bf16*)dyv, dgamma, dbeta, c, ws,
+                               ws_bytes, stream);
+  return bn_bwd_maxpool_impl("tmr_bn_bwd_maxpool", dyp, argmax, n, h, w, ho, wo, y, scale, shift,
+                             save_mean, save_invstd, gamma, (float*)dyv, dgamma, dbeta, c, ws,
+                             ws_bytes, stream);
 }
 
 TMR_API int tmr_bn_bwd_parts(const float* g, const float* y, const void* parts, int nparts,
@@ -1659,36 +1718,16 @@ TMR_API int tmr_bn_bwd_parts_x(const float* g, const float* y, const void* parts
                 "tmr_bn_bwd_parts: bad shape rows=%d c=%d parts=%d", rows, c, nparts);
   TMR_CHECK_ARG(ws && ws_bytes >= tmr_bn_parts_ws_bytes(nparts, c),
                 "tmr_bn_bwd_parts: workspace too small (need tmr_bn_parts_ws_bytes)");
-  const SlabPlan sp = slab_plan(nparts, c);
-  double* slabs = (double*)ws;
-  float* coef = (float*)((char*)ws + slab_ws_bytes(nparts, c));
-  hipLaunchKernelGGL(parts_slab_k<1>, dim3(sp.groups, sp.nslabs), dim3(256), 0, stream, parts,
-                     nparts, c, sp.rows, slabs);
-  TMR_CHECK_LAUNCH("bn_parts_slab");
-  hipLaunchKernelGGL(bwd_final_slabs_k, dim3(sp.groups), dim3(SLAB_CH * SLAB_PH), 0, stream,
-                     (const double*)slabs, sp.nslabs, rows, c, save_mean, save_invstd, gamma,
-                     dgamma, dbeta, coef);
-  TMR_CHECK_LAUNCH("bn_bwd_final_slabs");
+  const float* coef = parts_coef(parts, nparts, rows, c, save_mean, save_invstd, gamma, dgamma,
+                                 dbeta, ws, stream);
+  if (!coef) return 2;
   // coefficients only (tmr_bn_bwd_maxpool's convention): the caller applies them -- the fused
   // wgrad, tmr_conv2d_wgrad_bnbwd, reads them at ws + tmr_bn_parts_coef_offset(nparts, c)
   if (!dyv) return 0;
-  const long n4 = (long)rows * c / 4;
   // (a bf16 dy of fp32 g and y -- every non-downsample unit of the fp32-forward / bf16-backward
   // step -- takes the 8-wide form too: the 4-wide one stores dy in 8-B pieces)
-  if (out_bf16 && c % 8 == 0 && (((uintptr_t)g | (uintptr_t)y | (uintptr_t)dyv) & 15) == 0)
-    hipLaunchKernelGGL((bn_bwd_apply8_k<float, float, __bf16>), dim3(ew_blocks(n4 / 2)), dim3(NT), 0,
-                       stream, g, y, coef, (__bf16*)dyv, n4 / 2, c / 8);
-  else if (out_bf16)
-    hipLaunchKernelGGL((bn_bwd_apply<0, false, __bf16, float>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, g,
-                       y, nullptr, nullptr, nullptr, coef, (__bf16*)dyv, nullptr, n4, c / 4);
-  else if (c % 8 == 0 && (((uintptr_t)g | (uintptr_t)y | (uintptr_t)dyv) & 15) == 0)
-    hipLaunchKernelGGL((bn_bwd_apply8_k<float, float, float>), dim3(ew_blocks(n4 / 2)), dim3(NT), 0,
-                       stream, g, y, coef, (float*)dyv, n4 / 2, c / 8);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply<0, false, float, float>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, g, y,
-                       nullptr, nullptr, nullptr, coef, (float*)dyv, nullptr, n4, c / 4);
-  TMR_CHECK_LAUNCH("bn_bwd_apply");
-  return 0;
+  if (out_bf16) return apply_coef(g, y, coef, (__bf16*)dyv, rows, c, stream);
+  return apply_coef(g, y, coef, (float*)dyv, rows, c, stream);
 }
 
 // ---- bf16-activation forms (TMR_MATH_BF16 train step, include/tmr.h "_a16"): y, z and the
@@ -1696,38 +1735,21 @@ TMR_API int tmr_bn_bwd_parts_x(const float* g, const float* y, const void* parts
 // here), the gradients dz / dres stay fp32, dy (a conv operand) is written bf16.  Same arithmetic
 // as the fp32 forms on the bf16 values.
 
-// the 8-wide bf16 applies: channels a multiple of 8, 16-B aligned tensors (else the 4-wide forms)
-static bool apply8_ok(int c, const void* y, const void* r, const void* z) {
-  return c % 8 == 0 && (((uintptr_t)y | (uintptr_t)r | (uintptr_t)z) & 15) == 0;
-}
-
 TMR_API int tmr_bn_apply_a16(const void* y, const float* scale, const float* shift,
                              const void* residual, void* z, int rows, int c, int relu,
                              hipStream_t stream) {
   TMR_CHECK_ARG(c % 4 == 0 && y && scale && shift && z, "tmr_bn_apply_a16: bad arguments (c %d)", c);
-  const long n4 = (long)rows * c / 4;
-  const int nb = ew_blocks(n4), c4 = c / 4;
   const __bf16 *yb = (const __bf16*)y, *rb = (const __bf16*)residual;
   __bf16* zb = (__bf16*)z;
-  if (apply8_ok(c, y, residual, z)) {   // 8 per thread (bn_apply8_a16_k)
-    const long n8 = n4 / 2;
-    const int nb8 = ew_blocks(n8), c8 = c / 8;
-    if (rb) {
-      if (relu) hipLaunchKernelGGL((bn_apply8_a16_k<true, true, false>), dim3(nb8), dim3(NT), 0, stream, yb, scale, shift, rb, nullptr, nullptr, zb, n8, c8);
-      else hipLaunchKernelGGL((bn_apply8_a16_k<true, false, false>), dim3(nb8), dim3(NT), 0, stream, yb, scale, shift, rb, nullptr, nullptr, zb, n8, c8);
-    } else {
-      if (relu) hipLaunchKernelGGL((bn_apply8_a16_k<false, true, false>), dim3(nb8), dim3(NT), 0, stream, yb, scale, shift, nullptr, nullptr, nullptr, zb, n8, c8);
-      else hipLaunchKernelGGL((bn_apply8_a16_k<false, false, false>), dim3(nb8), dim3(NT), 0, stream, yb, scale, shift, nullptr, nullptr, nullptr, zb, n8, c8);
-    }
-  } else if (rb) {
-    if (relu) hipLaunchKernelGGL((bn_apply_k<true, true, __bf16, false, __bf16>), dim3(nb), dim3(NT), 0, stream, yb, scale, shift, rb, zb, n4, c4, nullptr);
-    else hipLaunchKernelGGL((bn_apply_k<true, false, __bf16, false, __bf16>), dim3(nb), dim3(NT), 0, stream, yb, scale, shift, rb, zb, n4, c4, nullptr);
-  } else {
-    if (relu) hipLaunchKernelGGL((bn_apply_k<false, true, __bf16, false, __bf16>), dim3(nb), dim3(NT), 0, stream, yb, scale, shift, rb, zb, n4, c4, nullptr);
-    else hipLaunchKernelGGL((bn_apply_k<false, false, __bf16, false, __bf16>), dim3(nb), dim3(NT), 0, stream, yb, scale, shift, rb, zb, n4, c4, nullptr);
-  }
-  TMR_CHECK_LAUNCH("bn_apply_a16");
-  return 0;
+  const bool w8 = wide8(c, y, residual, z);   // 8 per thread (bn_apply8_a16_k)
+  const Ew e = ew_grid(rows, c, w8 ? 8 : 4);
+  return with_bools(residual, relu, [&](auto RES, auto RELU) {
+    if (w8)
+      return launch("bn_apply_a16", bn_apply8_a16_k<RES, RELU, false>, e.nb, NT, stream, yb, scale,
+                    shift, rb, nullptr, nullptr, zb, e.n, e.cw);
+    return launch("bn_apply_a16", bn_apply_k<RES, RELU, __bf16, false, __bf16>, e.nb, NT, stream,
+                  yb, scale, shift, rb, zb, e.n, e.cw, nullptr);
+  });
 }
 
 TMR_API int tmr_bn_apply2_a16(const void* y, const float* scale, const float* shift, const void* yr,
@@ -1736,24 +1758,17 @@ TMR_API int tmr_bn_apply2_a16(const void* y, const float* scale, const float* sh
   TMR_CHECK_ARG(c % 4 == 0, "tmr_bn_apply2_a16: channels %d must be a multiple of 4", c);
   TMR_CHECK_ARG(y && scale && shift && yr && rscale && rshift && z, "tmr_bn_apply2_a16: null operand");
   TMR_CHECK_ARG(yr != z, "tmr_bn_apply2_a16: the branch input must not alias z");
-  const long n4 = (long)rows * c / 4;
   const __bf16 *yb = (const __bf16*)y, *rb = (const __bf16*)yr;
-  if (apply8_ok(c, y, yr, z)) {   // 8 per thread (bn_apply8_a16_k)
-    const long n8 = n4 / 2;
-    if (relu)
-      hipLaunchKernelGGL((bn_apply8_a16_k<false, true, true>), dim3(ew_blocks(n8)), dim3(NT), 0,
-                         stream, yb, scale, shift, rb, rscale, rshift, (__bf16*)z, n8, c / 8);
-    else
-      hipLaunchKernelGGL((bn_apply8_a16_k<false, false, true>), dim3(ew_blocks(n8)), dim3(NT), 0,
-                         stream, yb, scale, shift, rb, rscale, rshift, (__bf16*)z, n8, c / 8);
-  } else if (relu)
-    hipLaunchKernelGGL((bn_apply2_k<true, false, __bf16, __bf16>), dim3(ew_blocks(n4)), dim3(NT), 0,
-                       stream, yb, scale, shift, rb, rscale, rshift, (__bf16*)z, n4, c / 4, nullptr);
-  else
-    hipLaunchKernelGGL((bn_apply2_k<false, false, __bf16, __bf16>), dim3(ew_blocks(n4)), dim3(NT), 0,
-                       stream, yb, scale, shift, rb, rscale, rshift, (__bf16*)z, n4, c / 4, nullptr);
-  TMR_CHECK_LAUNCH("bn_apply2_a16");
-  return 0;
+  __bf16* zb = (__bf16*)z;
+  const bool w8 = wide8(c, y, yr, z);   // 8 per thread (bn_apply8_a16_k)
+  const Ew e = ew_grid(rows, c, w8 ? 8 : 4);
+  return with_bool(relu, [&](auto RELU) {
+    if (w8)
+      return launch("bn_apply2_a16", bn_apply8_a16_k<false, RELU, true>, e.nb, NT, stream, yb,
+                    scale, shift, rb, rscale, rshift, zb, e.n, e.cw);
+    return launch("bn_apply2_a16", bn_apply2_k<RELU, false, __bf16, __bf16>, e.nb, NT, stream, yb,
+                  scale, shift, rb, rscale, rshift, zb, e.n, e.cw, nullptr);
+  });
 }
 
 TMR_API int tmr_bn_bwd_a16(const float* dz, const void* y, const void* z, const float* scale,
@@ -1761,57 +1776,9 @@ TMR_API int tmr_bn_bwd_a16(const float* dz, const void* y, const void* z, const 
                            const float* gamma, void* dy, float* dres, float* dgamma, float* dbeta,
                            int rows, int c, int relu, void* ws, size_t ws_bytes,
                            hipStream_t stream) {
-  TMR_CHECK_ARG(c % 4 == 0 && c >= 4, "tmr_bn_bwd_a16: channels %d must be a multiple of 4", c);
-  TMR_CHECK_ARG(rows > 0, "tmr_bn_bwd_a16: empty input");
-  TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd_a16: unsupported channel count %d", c);
-  TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "tmr_bn_bwd_a16: workspace too small");
-  TMR_CHECK_ARG(!relu || z || (scale && shift),
-                "tmr_bn_bwd_a16: relu backward needs the saved output z or the forward scale/shift");
-  int mask = relu ? (z ? 1 : 2) : 0;
-  Plan p = make_plan(rows, c);
-  double* part = (double*)ws;
-  float* coef = (float*)((char*)ws + (size_t)p.nrb * c * 2 * sizeof(double));
-  const dim3 pg(p.nrb, p.cblocks);
-  float* dzw = const_cast<float*>(dz);
-  const __bf16 *yb = (const __bf16*)y, *zb = (const __bf16*)z;
-  if (dres == dz) {
-    if (mask == 1)
-      hipLaunchKernelGGL((bn_bwd_partial<1, true, __bf16>), pg, dim3(NT), 0, stream, dzw, yb, zb, scale, shift, save_mean, rows, c, p.rpb, p.cthreads, part);
-    else if (mask == 2)
-      hipLaunchKernelGGL((bn_bwd_partial<2, true, __bf16>), pg, dim3(NT), 0, stream, dzw, yb, zb, scale, shift, save_mean, rows, c, p.rpb, p.cthreads, part);
-    else
-      hipLaunchKernelGGL((bn_bwd_partial<0, false, __bf16>), pg, dim3(NT), 0, stream, dzw, yb, zb, scale, shift, save_mean, rows, c, p.rpb, p.cthreads, part);
-    mask = 0;
-    dres = nullptr;
-  } else if (mask == 1)
-    hipLaunchKernelGGL((bn_bwd_partial<1, false, __bf16>), pg, dim3(NT), 0, stream, dzw, yb, zb, scale, shift, save_mean, rows, c, p.rpb, p.cthreads, part);
-  else if (mask == 2)
-    hipLaunchKernelGGL((bn_bwd_partial<2, false, __bf16>), pg, dim3(NT), 0, stream, dzw, yb, zb, scale, shift, save_mean, rows, c, p.rpb, p.cthreads, part);
-  else
-    hipLaunchKernelGGL((bn_bwd_partial<0, false, __bf16>), pg, dim3(NT), 0, stream, dzw, yb, zb, scale, shift, save_mean, rows, c, p.rpb, p.cthreads, part);
-  TMR_CHECK_LAUNCH("bn_bwd_partial");
-  hipLaunchKernelGGL(bn_bwd_final, dim3(c), dim3(NT), 0, stream, part, p.nrb, rows, c,
-                     save_mean, save_invstd, gamma, dgamma, dbeta, coef);
-  TMR_CHECK_LAUNCH("bn_bwd_final");
-  const long n4 = (long)rows * c / 4;
-  const int nb = ew_blocks(n4), c4 = c / 4;
-  __bf16* db = (__bf16*)dy;
-#define TMR_BN_APPLY16(M, D)                                                                    \
-  hipLaunchKernelGGL((bn_bwd_apply<M, D, __bf16, __bf16>), dim3(nb), dim3(NT), 0, stream, dz, yb, \
-                     zb, scale, shift, coef, db, dres, n4, c4)
-  if (dres) {
-    if (mask == 1) { TMR_BN_APPLY16(1, true); } else if (mask == 2) { TMR_BN_APPLY16(2, true); } else { TMR_BN_APPLY16(0, true); }
-  } else if (mask == 0 && c % 8 == 0 && (((uintptr_t)dz | (uintptr_t)y | (uintptr_t)dy) & 15) == 0) {
-    // no mask left to apply (the downsample branch's BN, or a mask already written back): the
-    // 8-wide apply of the parts path (same coefficients, same fmaf sequence)
-    hipLaunchKernelGGL(bn_bwd_apply8_a16<float>, dim3(ew_blocks(n4 / 2)), dim3(NT), 0, stream, dz,
-                       yb, coef, db, n4 / 2, c / 8);
-  } else {
-    if (mask == 1) { TMR_BN_APPLY16(1, false); } else if (mask == 2) { TMR_BN_APPLY16(2, false); } else { TMR_BN_APPLY16(0, false); }
-  }
-#undef TMR_BN_APPLY16
-  TMR_CHECK_LAUNCH("bn_bwd_apply");
-  return 0;
+  return bn_bwd_impl("tmr_bn_bwd_a16", dz, (const __bf16*)y, (const __bf16*)z, scale, shift,
+                     save_mean, save_invstd, gamma, (__bf16*)dy, dres, dgamma, dbeta, rows, c,
+                     relu, ws, ws_bytes, stream);
 }
 
 // BatchNorm backward of a unit without ReLU (the downsample branch's BN) whose output gradient is
@@ -1821,26 +1788,17 @@ TMR_API int tmr_bn_bwd_g16(const void* dz, const void* y, const float* save_mean
                            float* dbeta, int rows, int c, void* ws, size_t ws_bytes,
                            hipStream_t stream) {
   TMR_CHECK_ARG(c % 8 == 0 && c >= 8 && rows > 0, "tmr_bn_bwd_g16: bad shape rows=%d c=%d", rows, c);
-  TMR_CHECK_ARG((((uintptr_t)dz | (uintptr_t)y | (uintptr_t)dy) & 15) == 0,
-                "tmr_bn_bwd_g16: dz / y / dy must be 16-B aligned");
+  TMR_CHECK_ARG(aligned16(dz, y, dy), "tmr_bn_bwd_g16: dz / y / dy must be 16-B aligned");
   TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd_g16: unsupported channel count %d", c);
   TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "tmr_bn_bwd_g16: workspace too small");
-  Plan p = make_plan(rows, c);
-  double* part = (double*)ws;
-  float* coef = (float*)((char*)ws + (size_t)p.nrb * c * 2 * sizeof(double));
   const __bf16 *gb = (const __bf16*)dz, *yb = (const __bf16*)y;
-  hipLaunchKernelGGL((bn_bwd_partial<0, false, __bf16, const __bf16>), dim3(p.nrb, p.cblocks), dim3(NT),
-                     0, stream, gb, yb, nullptr, nullptr, nullptr, save_mean, rows, c, p.rpb,
-                     p.cthreads, part);
-  TMR_CHECK_LAUNCH("bn_bwd_partial_g16");
-  hipLaunchKernelGGL(bn_bwd_final, dim3(c), dim3(NT), 0, stream, part, p.nrb, rows, c,
-                     save_mean, save_invstd, gamma, dgamma, dbeta, coef);
-  TMR_CHECK_LAUNCH("bn_bwd_final");
-  const long n8 = (long)rows * c / 8;
-  hipLaunchKernelGGL(bn_bwd_apply8_a16<__bf16>, dim3(ew_blocks(n8)), dim3(NT), 0, stream, gb, yb,
-                     coef, (__bf16*)dy, n8, c / 8);
-  TMR_CHECK_LAUNCH("bn_bwd_apply_g16");
-  return 0;
+  const float* coef = rows_coef<0, false>("bn_bwd_partial_g16", gb, yb, nullptr, nullptr, nullptr,
+                                          save_mean, save_invstd, gamma, dgamma, dbeta, rows, c,
+                                          ws, stream);
+  if (!coef) return 2;
+  const Ew e = ew_grid(rows, c, 8);
+  return launch("bn_bwd_apply_g16", bn_bwd_apply8_a16<__bf16>, e.nb, NT, stream, gb, yb, coef,
+                (__bf16*)dy, e.n, e.cw);
 }
 
 TMR_API int tmr_bn_bwd_parts_a16(const float* g, const void* y, const void* parts, int nparts,
@@ -1851,29 +1809,10 @@ TMR_API int tmr_bn_bwd_parts_a16(const float* g, const void* y, const void* part
                 "tmr_bn_bwd_parts_a16: bad shape rows=%d c=%d parts=%d", rows, c, nparts);
   TMR_CHECK_ARG(ws && ws_bytes >= tmr_bn_parts_ws_bytes(nparts, c),
                 "tmr_bn_bwd_parts_a16: workspace too small (need tmr_bn_parts_ws_bytes)");
-  const SlabPlan sp = slab_plan(nparts, c);
-  double* slabs = (double*)ws;
-  float* coef = (float*)((char*)ws + slab_ws_bytes(nparts, c));
-  hipLaunchKernelGGL(parts_slab_k<1>, dim3(sp.groups, sp.nslabs), dim3(256), 0, stream, parts,
-                     nparts, c, sp.rows, slabs);
-  TMR_CHECK_LAUNCH("bn_parts_slab");
-  hipLaunchKernelGGL(bwd_final_slabs_k, dim3(sp.groups), dim3(SLAB_CH * SLAB_PH), 0, stream,
-                     (const double*)slabs, sp.nslabs, rows, c, save_mean, save_invstd, gamma,
-                     dgamma, dbeta, coef);
-  TMR_CHECK_LAUNCH("bn_bwd_final_slabs");
-  const long n4 = (long)rows * c / 4;
-  // 8 per thread (else the 4-wide form)
-  if (c % 8 == 0 && (((uintptr_t)g | (uintptr_t)y | (uintptr_t)dy) & 15) == 0) {
-    const long n8 = n4 / 2;
-    hipLaunchKernelGGL(bn_bwd_apply8_a16<float>, dim3(ew_blocks(n8)), dim3(NT), 0, stream, g,
-                       (const __bf16*)y, coef, (__bf16*)dy, n8, c / 8);
-  } else {
-    hipLaunchKernelGGL((bn_bwd_apply<0, false, __bf16, __bf16>), dim3(ew_blocks(n4)), dim3(NT), 0,
-                       stream, g, (const __bf16*)y, nullptr, nullptr, nullptr, coef, (__bf16*)dy,
-                       nullptr, n4, c / 4);
-  }
-  TMR_CHECK_LAUNCH("bn_bwd_apply");
-  return 0;
+  const float* coef = parts_coef(parts, nparts, rows, c, save_mean, save_invstd, gamma, dgamma,
+                                 dbeta, ws, stream);
+  if (!coef) return 2;
+  return apply_coef(g, (const __bf16*)y, coef, (__bf16*)dy, rows, c, stream);
 }
 
 TMR_API int tmr_bn_bwd_parts_g16(const void* g, const void* y, const void* parts, int nparts,
@@ -1882,25 +1821,15 @@ TMR_API int tmr_bn_bwd_parts_g16(const void* g, const void* y, const void* parts
                                  int rows, int c, void* ws, size_t ws_bytes, hipStream_t stream) {
   TMR_CHECK_ARG(c % 8 == 0 && c >= 8 && rows > 0 && nparts > 0,
                 "tmr_bn_bwd_parts_g16: bad shape rows=%d c=%d parts=%d", rows, c, nparts);
-  TMR_CHECK_ARG((((uintptr_t)g | (uintptr_t)y | (uintptr_t)dy) & 15) == 0,
-                "tmr_bn_bwd_parts_g16: g / y / dy must be 16-B aligned");
+  TMR_CHECK_ARG(aligned16(g, y, dy), "tmr_bn_bwd_parts_g16: g / y / dy must be 16-B aligned");
   TMR_CHECK_ARG(ws && ws_bytes >= tmr_bn_parts_ws_bytes(nparts, c),
                 "tmr_bn_bwd_parts_g16: workspace too small (need tmr_bn_parts_ws_bytes)");
-  const SlabPlan sp = slab_plan(nparts, c);
-  double* slabs = (double*)ws;
-  float* coef = (float*)((char*)ws + slab_ws_bytes(nparts, c));
-  hipLaunchKernelGGL(parts_slab_k<1>, dim3(sp.groups, sp.nslabs), dim3(256), 0, stream, parts,
-                     nparts, c, sp.rows, slabs);
-  TMR_CHECK_LAUNCH("bn_parts_slab");
-  hipLaunchKernelGGL(bwd_final_slabs_k, dim3(sp.groups), dim3(SLAB_CH * SLAB_PH), 0, stream,
-                     (const double*)slabs, sp.nslabs, rows, c, save_mean, save_invstd, gamma,
-                     dgamma, dbeta, coef);
-  TMR_CHECK_LAUNCH("bn_bwd_final_slabs");
-  const long n8 = (long)rows * c / 8;
-  hipLaunchKernelGGL(bn_bwd_apply8_a16<__bf16>, dim3(ew_blocks(n8)), dim3(NT), 0, stream,
-                     (const __bf16*)g, (const __bf16*)y, coef, (__bf16*)dy, n8, c / 8);
-  TMR_CHECK_LAUNCH("bn_bwd_apply_g16");
-  return 0;
+  const float* coef = parts_coef(parts, nparts, rows, c, save_mean, save_invstd, gamma, dgamma,
+                                 dbeta, ws, stream);
+  if (!coef) return 2;
+  const Ew e = ew_grid(rows, c, 8);
+  return launch("bn_bwd_apply_g16", bn_bwd_apply8_a16<__bf16>, e.nb, NT, stream, (const __bf16*)g,
+                (const __bf16*)y, coef, (__bf16*)dy, e.n, e.cw);
 }
 
 // The BatchNorm backward of a downsample block's two units that share one output gradient g (the
@@ -1950,6 +1879,14 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_ds8(const T* __restrict__ g, 
   }
 }
 
+template <typename T, typename TD>
+static int apply_ds(const void* g, const void* y, const void* yd, const float* coef,
+                    const float* coefd, void* dy, void* dyd, int rows, int c, hipStream_t stream) {
+  const Ew e = ew_grid(rows, c, 8);
+  return launch("bn_bwd_apply_ds", bn_bwd_apply_ds8<T, TD>, ew_blocks(e.n / 2), NT, stream,
+                (const T*)g, (const T*)y, (const T*)yd, coef, coefd, (TD*)dy, (TD*)dyd, e.n, e.cw);
+}
+
 TMR_API size_t tmr_bn_bwd_parts_ds_ws_bytes(int nparts, int rows, int c) {
   if (nparts <= 0 || rows <= 0 || c < 8 || c % 8) {
     tmr_set_error("tmr_bn_bwd_parts_ds_ws_bytes: bad size (parts %d, rows %d, channels %d)", nparts,
@@ -1990,67 +1927,40 @@ static int bn_bwd_parts_ds_impl(const void* g, const void* y, const void* parts,
                     gamma_d, "tmr_bn_bwd_parts_ds: null operand");
   TMR_CHECK_ARG((dy && dyd) || !bf16,
                 "tmr_bn_bwd_parts_ds: the coefficient-only and single-output forms are fp32 only");
-  TMR_CHECK_ARG((((uintptr_t)g | (uintptr_t)y | (uintptr_t)yd | (uintptr_t)dy | (uintptr_t)dyd) & 15) == 0,
+  TMR_CHECK_ARG(aligned16(g, y, yd, dy, dyd),
                 "tmr_bn_bwd_parts_ds: g / y / y_ds / dy / dy_ds must be 16-B aligned");
   const size_t a_bytes = (tmr_bn_parts_ws_bytes(nparts, c) + 255) / 256 * 256;
   TMR_CHECK_ARG(ws && ws_bytes >= a_bytes + ws_need(rows, c),
                 "tmr_bn_bwd_parts_ds: workspace too small (need tmr_bn_bwd_parts_ds_ws_bytes)");
-  // bn3: the fused dgrad's partials (tmr_bn_bwd_parts_x / _g16's kernels)
-  const SlabPlan sp = slab_plan(nparts, c);
-  double* slabs = (double*)ws;
-  float* coef = (float*)((char*)ws + slab_ws_bytes(nparts, c));
-  hipLaunchKernelGGL(parts_slab_k<1>, dim3(sp.groups, sp.nslabs), dim3(256), 0, stream, parts,
-                     nparts, c, sp.rows, slabs);
-  TMR_CHECK_LAUNCH("bn_parts_slab");
-  hipLaunchKernelGGL(bwd_final_slabs_k, dim3(sp.groups), dim3(SLAB_CH * SLAB_PH), 0, stream,
-                     (const double*)slabs, sp.nslabs, rows, c, mean, invstd, gamma, dgamma, dbeta, coef);
-  TMR_CHECK_LAUNCH("bn_bwd_final_slabs");
-  // the downsample BN: one reduction pass over (g, y_ds) (tmr_bn_bwd_x / tmr_bn_bwd_g16's kernels)
-  char* wb = (char*)ws + a_bytes;
-  Plan p = make_plan(rows, c);
-  double* part = (double*)wb;
-  float* coefd = (float*)(wb + (size_t)p.nrb * c * 2 * sizeof(double));
-  const dim3 pg(p.nrb, p.cblocks);
-  if (bf16)
-    hipLaunchKernelGGL((bn_bwd_partial<0, false, __bf16, const __bf16>), pg, dim3(NT), 0, stream,
-                       (const __bf16*)g, (const __bf16*)yd, (const __bf16*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, mean_d, rows, c, p.rpb,
-                       p.cthreads, part);
-  else
-    hipLaunchKernelGGL((bn_bwd_partial<0>), pg, dim3(NT), 0, stream, (float*)g, (const float*)yd,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, mean_d,
-                       rows, c, p.rpb, p.cthreads, part);
-  TMR_CHECK_LAUNCH("bn_bwd_partial");
-  hipLaunchKernelGGL(bn_bwd_final, dim3(c), dim3(NT), 0, stream, part, p.nrb, rows, c, mean_d,
-                     invstd_d, gamma_d, dgamma_d, dbeta_d, coefd);
-  TMR_CHECK_LAUNCH("bn_bwd_final");
-  const long n8 = (long)rows * c / 8;
+  // bn3: the fused dgrad's partials
+  const float* coef = parts_coef(parts, nparts, rows, c, mean, invstd, gamma, dgamma, dbeta, ws,
+                                 stream);
+  if (!coef) return 2;
+  // the downsample BN: one reduction pass over (g, y_ds), behind bn3's workspace
+  void* wsd = (char*)ws + a_bytes;
+  const float* coefd =
+      bf16 ? rows_coef<0, false>("bn_bwd_partial", (const __bf16*)g, (const __bf16*)yd, nullptr,
+                                 nullptr, nullptr, mean_d, invstd_d, gamma_d, dgamma_d, dbeta_d,
+                                 rows, c, wsd, stream)
+           : rows_coef<0, false>("bn_bwd_partial", (float*)g, (const float*)yd, nullptr, nullptr,
+                                 nullptr, mean_d, invstd_d, gamma_d, dgamma_d, dbeta_d, rows, c,
+                                 wsd, stream);
+  if (!coefd) return 2;
   if (!dy || !dyd) {
     // one output: the single-output apply on that unit's coefficient block (12 B per element;
     // bn_bwd_apply_ds8's fmaf sequence, so the values of the dual pass); none: coefficients only
+    const Ew e = ew_grid(rows, c, 8);
     if (dy)
-      hipLaunchKernelGGL((bn_bwd_apply8_k<float, float, float>), dim3(ew_blocks(n8)), dim3(NT), 0,
-                         stream, (const float*)g, (const float*)y, coef, (float*)dy, n8, c / 8);
-    else if (dyd)
-      hipLaunchKernelGGL((bn_bwd_apply8_k<float, float, float>), dim3(ew_blocks(n8)), dim3(NT), 0,
-                         stream, (const float*)g, (const float*)yd, coefd, (float*)dyd, n8, c / 8);
-    TMR_CHECK_LAUNCH("bn_bwd_apply");
+      return launch("bn_bwd_apply", bn_bwd_apply8_k<float, float, float>, e.nb, NT, stream,
+                    (const float*)g, (const float*)y, coef, (float*)dy, e.n, e.cw);
+    if (dyd)
+      return launch("bn_bwd_apply", bn_bwd_apply8_k<float, float, float>, e.nb, NT, stream,
+                    (const float*)g, (const float*)yd, coefd, (float*)dyd, e.n, e.cw);
     return 0;
   }
-  if (bf16)
-    hipLaunchKernelGGL(bn_bwd_apply_ds8<__bf16>, dim3(ew_blocks(n8 / 2)), dim3(NT), 0, stream,
-                       (const __bf16*)g, (const __bf16*)y, (const __bf16*)yd, coef, coefd,
-                       (__bf16*)dy, (__bf16*)dyd, n8, c / 8);
-  else if (out16)
-    hipLaunchKernelGGL((bn_bwd_apply_ds8<float, __bf16>), dim3(ew_blocks(n8 / 2)), dim3(NT), 0, stream,
-                       (const float*)g, (const float*)y, (const float*)yd, coef, coefd,
-                       (__bf16*)dy, (__bf16*)dyd, n8, c / 8);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_ds8<float>, dim3(ew_blocks(n8 / 2)), dim3(NT), 0, stream,
-                       (const float*)g, (const float*)y, (const float*)yd, coef, coefd, (float*)dy,
-                       (float*)dyd, n8, c / 8);
-  TMR_CHECK_LAUNCH("bn_bwd_apply_ds");
-  return 0;
+  if (bf16) return apply_ds<__bf16, __bf16>(g, y, yd, coef, coefd, dy, dyd, rows, c, stream);
+  if (out16) return apply_ds<float, __bf16>(g, y, yd, coef, coefd, dy, dyd, rows, c, stream);
+  return apply_ds<float, float>(g, y, yd, coef, coefd, dy, dyd, rows, c, stream);
 }
 
 TMR_API int tmr_bn_bwd_parts_ds(const void* g, const void* y, const void* parts, int nparts,
@@ -2083,48 +1993,11 @@ TMR_API int tmr_bn_bwd_maxpool_a16(const float* dyp, const uint8_t* argmax, int 
                                    const float* save_invstd, const float* gamma, void* dy,
                                    float* dgamma, float* dbeta, int c, void* ws, size_t ws_bytes,
                                    hipStream_t stream) {
-  const long rows_l = (long)n * h * w;
-  TMR_CHECK_ARG(c % 4 == 0 && c >= 4 && rows_l > 0 && rows_l < 0x7fffffffL,
-                "tmr_bn_bwd_maxpool_a16: bad shape n=%d h=%d w=%d c=%d", n, h, w, c);
-  TMR_CHECK_ARG(ho == (h + 2 - 3) / 2 + 1 && wo == (w + 2 - 3) / 2 + 1,
-                "tmr_bn_bwd_maxpool_a16: pooled %dx%d is not MaxPool2d(3,2,1) of %dx%d", ho, wo, h, w);
-  const int rows = (int)rows_l;
-  TMR_CHECK_ARG(plan_covers(c), "tmr_bn_bwd_maxpool_a16: unsupported channel count %d", c);
-  TMR_CHECK_ARG(ws && ws_bytes >= ws_need(rows, c), "tmr_bn_bwd_maxpool_a16: workspace too small");
-  PoolGeo pg;
-  pg.dyp = dyp; pg.am = (const uchar4*)argmax;
-  pg.dHW = make_fastdiv((uint32_t)(h * w)); pg.dW = make_fastdiv((uint32_t)w);
-  pg.ho = ho; pg.wo = wo;
-  const int prows = n * ho * wo;
-  Plan p = make_plan(prows, c);
-  double* part = (double*)ws;
-  float* coef = (float*)((char*)ws + (size_t)p.nrb * c * 2 * sizeof(double));
-  const __bf16* yb = (const __bf16*)y;
-  hipLaunchKernelGGL(stem_bwd_partial_pooled<__bf16>, dim3(p.nrb, p.cblocks), dim3(NT), 0, stream, pg,
-                     h, w, yb, scale, shift, save_mean, prows, c, p.rpb, p.cthreads,
-                     make_fastdiv((uint32_t)(ho * wo)), make_fastdiv((uint32_t)wo), part);
-  TMR_CHECK_LAUNCH("stem_bwd_partial_pooled");
-  hipLaunchKernelGGL(bn_bwd_final, dim3(c), dim3(NT), 0, stream, part, p.nrb, rows, c,
-                     save_mean, save_invstd, gamma, dgamma, dbeta, coef);
-  TMR_CHECK_LAUNCH("bn_bwd_final");
-  const long n4 = rows_l * c / 4;
-  const int c8 = c / 8;
-  // 8 channels per thread, per 2x2 input quad (its candidate pooled outputs gathered once; the
-  // per-pixel form it replaced in round 4 was bound by 2.25 gathers per pixel); else 4-wide
-  if (c % 8 == 0 && (c8 & (c8 - 1)) == 0 && n4 / 2 < 0x7fffffffL &&
-      (((uintptr_t)dyp | (uintptr_t)y | (uintptr_t)dy) & 15) == 0 && ((uintptr_t)argmax & 7) == 0) {
-    const int qh = (h + 1) / 2, qw = (w + 1) / 2;
-    const int nq = n * qh * qw * c8;
-    hipLaunchKernelGGL((stem_bwd_apply8q<__bf16, __bf16>), dim3(ew_blocks(nq)), dim3(NT), 0, stream,
-                       pg, h, w, make_fastdiv((uint32_t)(qh * qw)), make_fastdiv((uint32_t)qw), yb,
-                       scale, shift, coef, (__bf16*)dy, nq, __builtin_ctz(c8));
-  } else {
-    hipLaunchKernelGGL((stem_bwd_apply<__bf16, __bf16>), dim3(ew_blocks(n4)), dim3(NT), 0, stream, pg,
-                       yb, scale, shift, coef, (__bf16*)dy, n4, c / 4);
-  }
-  TMR_CHECK_LAUNCH("stem_bwd_apply");
-  return 0;
+  return bn_bwd_maxpool_impl("tmr_bn_bwd_maxpool_a16", dyp, argmax, n, h, w, ho, wo,
+                             (const __bf16*)y, scale, shift, save_mean, save_invstd, gamma,
+                             (__bf16*)dy, dgamma, dbeta, c, ws, ws_bytes, stream);
 }
+
 
 // ---- frozen BatchNorm: a train-mode step on the running statistics (include/tmr.h
 // "tmr_bn_frozen_*") ----------------------------------------------------------------------------
@@ -2432,44 +2305,19 @@ __global__ __launch_bounds__(NT) void scale_rows4_k(float4* __restrict__ w,
   }
 }
 
-int frozen_check(const char* name, int rows, int c, const void* a, const void* b, const void* d,
-                 const void* e, const void* f, const void* h) {
+// tmr_bn_frozen_bwd (dual false: yd .. dyd, parts_d NULL) and tmr_bn_frozen_bwd_ds
+int bn_frozen_bwd_impl(bool dual, const float* g, const void* zmask, int mask, const float* y,
+                       const float* scale, const float* shift, const float* mean, float* dy,
+                       const float* yd, const float* scale_d, const float* mean_d, float* dyd,
+                       float* dres, void* parts, void* parts_d, size_t parts_bytes, int rows, int c,
+                       int want_sums, hipStream_t stream) {
+  const char* name = dual ? "tmr_bn_frozen_bwd_ds" : "tmr_bn_frozen_bwd";
   TMR_CHECK_ARG(rows > 0 && c >= 8 && c % 8 == 0,
                 "%s: bad shape rows=%d c=%d (channels must be a multiple of 8)", name, rows, c);
   TMR_CHECK_ARG(fplan_covers(c), "%s: unsupported channel count %d", name, c);
-  TMR_CHECK_ARG((((uintptr_t)a | (uintptr_t)b | (uintptr_t)d | (uintptr_t)e | (uintptr_t)f |
-                  (uintptr_t)h) & 15) == 0,
+  TMR_CHECK_ARG(aligned16(g, mask == 1 ? zmask : nullptr, y, yd, dy, dyd),
                 "%s: g / z / y / y_ds / dy / dy_ds / dres must be 16-B aligned", name);
-  return 0;
-}
-
-}  // namespace
-
-TMR_API int tmr_bn_frozen_params(const tmr_bn_frozen_entry* table_dev, int n, hipStream_t stream) {
-  TMR_CHECK_ARG(table_dev && n > 0, "tmr_bn_frozen_params: empty table");
-  hipLaunchKernelGGL(bn_frozen_params_k, dim3(n), dim3(NT), 0, stream, table_dev);
-  TMR_CHECK_LAUNCH("bn_frozen_params");
-  return 0;
-}
-
-TMR_API int tmr_bn_frozen_bwd_parts(int rows, int c) {
-  if (rows <= 0 || c < 8 || c % 8 || !fplan_covers(c)) {
-    tmr_set_error("tmr_bn_frozen_bwd_parts: bad size (rows %d, channels %d)", rows, c);
-    return -1;
-  }
-  return make_fplan(rows, c).nrb;
-}
-
-static int bn_frozen_bwd_impl(bool dual, const float* g, const void* zmask, int mask,
-                              const float* y, const float* scale, const float* shift,
-                              const float* mean, float* dy, const float* yd, const float* scale_d,
-                              const float* mean_d, float* dyd, float* dres, void* parts,
-                              void* parts_d, size_t parts_bytes, int rows, int c, int want_sums,
-                              hipStream_t stream) {
-  const char* name = dual ? "tmr_bn_frozen_bwd_ds" : "tmr_bn_frozen_bwd";
-  if (const int rc = frozen_check(name, rows, c, g, mask == 1 ? zmask : nullptr, y, yd, dy, dyd))
-    return rc;
-  TMR_CHECK_ARG(((uintptr_t)dres & 15) == 0, "%s: dres must be 16-B aligned", name);
+  TMR_CHECK_ARG(aligned16(dres), "%s: dres must be 16-B aligned", name);
   TMR_CHECK_ARG(mask >= 0 && mask <= 3, "%s: bad mask %d", name, mask);
   TMR_CHECK_ARG(g && scale && mean, "%s: null operand", name);
   TMR_CHECK_ARG(mask == 0 || mask == 2 || zmask, "%s: mask %d needs z (1) or the mask bits (3)", name, mask);
@@ -2485,21 +2333,26 @@ static int bn_frozen_bwd_impl(bool dual, const float* g, const void* zmask, int 
     pp = (float2*)parts;
     pd = (float2*)parts_d;
   }
-  const dim3 grid(p.nrb, p.cblocks);
-#define TMR_FROZEN(M)                                                                           \
-  if (dual)                                                                                      \
-    hipLaunchKernelGGL((bn_frozen_bwd8_k<M, true>), grid, dim3(NT), 0, stream, g, zmask, y,      \
-                       scale, shift, mean, dy, dres, yd, scale_d, mean_d, dyd, pp, pd, rows, c,  \
-                       p.rpb, p.cthreads);                                                       \
-  else                                                                                           \
-    hipLaunchKernelGGL((bn_frozen_bwd8_k<M, false>), grid, dim3(NT), 0, stream, g, zmask, y,     \
-                       scale, shift, mean, dy, dres, yd, scale_d, mean_d, dyd, pp, pd, rows, c,  \
-                       p.rpb, p.cthreads)
-  if (mask == 0) { TMR_FROZEN(0); } else if (mask == 1) { TMR_FROZEN(1); }
-  else if (mask == 2) { TMR_FROZEN(2); } else { TMR_FROZEN(3); }
-#undef TMR_FROZEN
-  TMR_CHECK_LAUNCH("bn_frozen_bwd");
-  return 0;
+  return with_int_bool<4>(mask, dual, [&](auto M, auto DUAL) {
+    return launch("bn_frozen_bwd", bn_frozen_bwd8_k<M, DUAL>, dim3(p.nrb, p.cblocks), NT, stream, g,
+                  zmask, y, scale, shift, mean, dy, dres, yd, scale_d, mean_d, dyd, pp, pd, rows, c,
+                  p.rpb, p.cthreads);
+  });
+}
+
+}  // namespace
+
+TMR_API int tmr_bn_frozen_params(const tmr_bn_frozen_entry* table_dev, int n, hipStream_t stream) {
+  TMR_CHECK_ARG(table_dev && n > 0, "tmr_bn_frozen_params: empty table");
+  return launch("bn_frozen_params", bn_frozen_params_k, n, NT, stream, table_dev);
+}
+
+TMR_API int tmr_bn_frozen_bwd_parts(int rows, int c) {
+  if (rows <= 0 || c < 8 || c % 8 || !fplan_covers(c)) {
+    tmr_set_error("tmr_bn_frozen_bwd_parts: bad size (rows %d, channels %d)", rows, c);
+    return -1;
+  }
+  return make_fplan(rows, c).nrb;
 }
 
 TMR_API int tmr_bn_frozen_bwd(const float* g, const void* zmask, int mask, const float* y,
@@ -2548,7 +2401,7 @@ TMR_API int tmr_bn_frozen_bwd_maxpool(const float* dyp, const uint8_t* argmax, i
                 "tmr_bn_frozen_bwd_maxpool: pooled %dx%d is not MaxPool2d(3,2,1) of %dx%d", ho, wo, h, w);
   TMR_CHECK_ARG(dyp && argmax && y && scale && shift && mean && dy,
                 "tmr_bn_frozen_bwd_maxpool: null operand");
-  TMR_CHECK_ARG((((uintptr_t)dyp | (uintptr_t)y | (uintptr_t)dy) & 15) == 0 && ((uintptr_t)argmax & 7) == 0,
+  TMR_CHECK_ARG(aligned16(dyp, y, dy) && ((uintptr_t)argmax & 7) == 0,
                 "tmr_bn_frozen_bwd_maxpool: dyp / y / dy must be 16-B aligned, argmax 8-B");
   const int qh = (h + 1) / 2, qw = (w + 1) / 2;
   const long nq_l = (long)n * qh * qw * c8;
@@ -2562,15 +2415,9 @@ TMR_API int tmr_bn_frozen_bwd_maxpool(const float* dyp, const uint8_t* argmax, i
                   "(tmr_bn_frozen_bwd_maxpool_parts rows of c float2)");
     pp = (float2*)parts;
   }
-  PoolGeo pg;
-  pg.dyp = dyp; pg.am = (const uchar4*)argmax;
-  pg.dHW = make_fastdiv((uint32_t)(h * w)); pg.dW = make_fastdiv((uint32_t)w);
-  pg.ho = ho; pg.wo = wo;
-  hipLaunchKernelGGL(bn_frozen_bwd_maxpool8q_k, dim3(nb), dim3(NT), 0, stream, pg, h, w,
-                     make_fastdiv((uint32_t)(qh * qw)), make_fastdiv((uint32_t)qw), y, scale, shift,
-                     mean, dy, pp, nq, __builtin_ctz(c8));
-  TMR_CHECK_LAUNCH("bn_frozen_bwd_maxpool");
-  return 0;
+  return launch("bn_frozen_bwd_maxpool", bn_frozen_bwd_maxpool8q_k, nb, NT, stream,
+                pool_geo(dyp, argmax, h, w, ho, wo), h, w, make_fastdiv((uint32_t)(qh * qw)),
+                make_fastdiv((uint32_t)qw), y, scale, shift, mean, dy, pp, nq, __builtin_ctz(c8));
 }
 
 TMR_API int tmr_bn_frozen_finalize(const void* parts, int nparts, int c, const float* inv,
@@ -2581,24 +2428,18 @@ TMR_API int tmr_bn_frozen_finalize(const void* parts, int nparts, int c, const f
   TMR_CHECK_ARG(ws && ws_bytes >= slab_ws_bytes(nparts, c),
                 "tmr_bn_frozen_finalize: workspace too small (need tmr_bn_parts_ws_bytes)");
   const SlabPlan sp = slab_plan(nparts, c);
-  hipLaunchKernelGGL(parts_slab_k<1>, dim3(sp.groups, sp.nslabs), dim3(256), 0, stream, parts,
-                     nparts, c, sp.rows, (double*)ws);
-  TMR_CHECK_LAUNCH("bn_parts_slab");
-  hipLaunchKernelGGL(frozen_final_slabs_k, dim3(sp.groups), dim3(SLAB_CH * SLAB_PH), 0, stream,
-                     (const double*)ws, sp.nslabs, c, inv, dgamma, dbeta);
-  TMR_CHECK_LAUNCH("bn_frozen_final_slabs");
-  return 0;
+  if (const int rc = parts_slabs<1>(sp, parts, nparts, c, ws, stream)) return rc;
+  return launch("bn_frozen_final_slabs", frozen_final_slabs_k, sp.groups, SLAB_CH * SLAB_PH, stream,
+                (const double*)ws, sp.nslabs, c, inv, dgamma, dbeta);
 }
 
 TMR_API int tmr_scale_rows(float* w, const float* scale, int k, long row, hipStream_t stream) {
   TMR_CHECK_ARG(w && scale && k > 0 && row > 0 && row < 0x7fffffffL,
                 "tmr_scale_rows: bad arguments (k %d, row %ld)", k, row);
   const long n = (long)k * row;
-  if (row % 4 == 0 && ((uintptr_t)w & 15) == 0)
-    hipLaunchKernelGGL(scale_rows4_k, dim3(ew_blocks(n / 4)), dim3(NT), 0, stream, (float4*)w,
-                       scale, n / 4, (int)(row / 4));
-  else
-    hipLaunchKernelGGL(scale_rows_k, dim3(ew_blocks(n)), dim3(NT), 0, stream, w, scale, n, (int)row);
-  TMR_CHECK_LAUNCH("scale_rows");
-  return 0;
+  if (row % 4 == 0 && aligned16(w))
+    return launch("scale_rows", scale_rows4_k, ew_blocks(n / 4), NT, stream, (float4*)w, scale,
+                  n / 4, (int)(row / 4));
+  return launch("scale_rows", scale_rows_k, ew_blocks(n), NT, stream, w, scale, n, (int)row);
 }
+
