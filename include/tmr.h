@@ -415,6 +415,27 @@ int tmr_bn_frozen_bwd_maxpool(const float* dyp, const uint8_t* argmax, int n, in
                               int wo, const float* y, const float* scale, const float* shift,
                               const float* mean, float* dy, void* parts, size_t parts_bytes, int c,
                               int want_sums, hipStream_t stream);
+/* The frozen step with bf16 backward convs: the same kernels with dy / dy_ds stored fp32
+ * (out_bf16 = 0) or rounded once to bf16 (RNE; 8 channels as one 16-B piece), and an optional g16:
+ * the masked g itself rounded to bf16 (the operand of a folded unit's convs).  dres and the
+ * partials are those of the fp32 entry points bit for bit -- the sums are always of the fp32
+ * masked g.  dy = NULL with g16 (mask 0, want_sums 0 or 1) is the cast pass over a block output's
+ * gradient.  The fp32 entry points above are out_bf16 = 0, g16 = NULL.  bf16 outputs are 16-B
+ * aligned too. */
+int tmr_bn_frozen_bwd_x(const float* g, const void* zmask, int mask, const float* y,
+                        const float* scale, const float* shift, const float* mean, void* dy,
+                        float* dres, void* g16, void* parts, size_t parts_bytes, int rows, int c,
+                        int want_sums, int out_bf16, hipStream_t stream);
+int tmr_bn_frozen_bwd_ds_x(const float* g, const void* zmask, int mask, const float* y,
+                           const float* scale, const float* shift, const float* mean, void* dy,
+                           const float* yd, const float* scale_d, const float* mean_d, void* dyd,
+                           float* dres, void* g16, void* parts, void* parts_d, size_t parts_bytes,
+                           int rows, int c, int want_sums, int out_bf16, hipStream_t stream);
+int tmr_bn_frozen_bwd_maxpool_x(const float* dyp, const uint8_t* argmax, int n, int h, int w,
+                                int ho, int wo, const float* y, const float* scale,
+                                const float* shift, const float* mean, void* dy, void* parts,
+                                size_t parts_bytes, int c, int want_sums, int out_bf16,
+                                hipStream_t stream);
 int tmr_bn_frozen_finalize(const void* parts, int nparts, int c, const float* inv, float* dgamma,
                            float* dbeta, void* ws, size_t ws_bytes, hipStream_t stream);
 int tmr_scale_rows(float* w, const float* scale, int k, long row, hipStream_t stream);

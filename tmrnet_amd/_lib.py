@@ -125,7 +125,10 @@ SIGNATURES = {
     "tmr_bn_frozen_bwd_ds": [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, SZ, I, I, I, P],
     "tmr_bn_frozen_bwd_maxpool_parts": [I, I, I, I],
     "tmr_bn_frozen_bwd_maxpool": [P, P, I, I, I, I, I, P, P, P, P, P, P, SZ, I, I, P],
-    "tmr_bn_frozen_finalize": [P, I, I, P, P, P, P, SZ, P],
+    "tmr_bn_frozen_bwd_x": [P, P, I, P, P, P, P, P, P, P, P, SZ, I, I, I, I, P],
+    "tmr_bn_frozen_bwd_ds_x": [P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, SZ, I, I, I, I, P],
+    "tmr_bn_frozen_bwd_maxpool_x": [P, P, I, I, I, I, I, P, P, P, P, P, P, SZ, I, I, I, P],
+    "tmr_bn_frozen_finalize":[P, I, I, P, P, P, P, SZ, P],
     "tmr_scale_rows": [P, P, I, L, P],
     "tmr_bn_bwd_parts_ds_ws_bytes": [I, I, I],
     "tmr_bn_bwd_parts_ds_coef_offset": [I, I, I, I],

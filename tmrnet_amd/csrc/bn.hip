@@ -2061,14 +2061,18 @@ FPlan make_fplan(int rows, int c) {
 // identity branch's gradient in place), dy / dy_ds (the caller folds the scale into its conv
 // operands), parts / parts_d (want_sums = 0).  Partials: float2 (sum g, sum g*(y - mean)) per row
 // block and channel, the layout of the fused dgrad's (tmr_conv2d_dgrad_bnbwd).
-template <int MASK, bool DUAL>
+// TD: the type dy / dy_ds are stored in (float, or __bf16: RNE, 8 channels as one 16-B piece);
+// g16 (NULL: skipped): the masked g rounded to bf16.  The sums are of the fp32 masked g whatever is
+// stored (the tmr_bn_frozen_bwd*_x forms).
+template <int MASK, bool DUAL, typename TD>
 __global__ __launch_bounds__(NT) void bn_frozen_bwd8_k(
     const float* g, const void* __restrict__ zm, const float* __restrict__ y,
     const float* __restrict__ scale, const float* __restrict__ shift,
-    const float* __restrict__ mean, float* __restrict__ dy, float* dres,
+    const float* __restrict__ mean, TD* __restrict__ dy, float* dres,
     const float* __restrict__ yd, const float* __restrict__ scale_d,
-    const float* __restrict__ mean_d, float* __restrict__ dyd, float2* __restrict__ parts,
-    float2* __restrict__ parts_d, int rows, int c, int rpb, int cthreads) {
+    const float* __restrict__ mean_d, TD* __restrict__ dyd, __bf16* __restrict__ g16,
+    float2* __restrict__ parts, float2* __restrict__ parts_d, int rows, int c, int rpb,
+    int cthreads) {
   constexpr int NV = DUAL ? 24 : 16;
   const int rthreads = NT / cthreads;
   const int tc = threadIdx.x % cthreads, tr = threadIdx.x / cthreads;
@@ -2103,6 +2107,7 @@ __global__ __launch_bounds__(NT) void bn_frozen_bwd8_k(
       gm[e] = on ? gv[e] : 0.f;
     }
     if (dres) st8(dres, i, gm);
+    if (g16) st8(g16, i, gm);
     if (dy) {
       float o[8];
 #pragma unroll
@@ -2177,10 +2182,12 @@ __global__ __launch_bounds__(NT) void bn_frozen_bwd8_k(
 // gather and summation order), masked by the forward's fmaf(y, scale, shift) > 0, dy = g*scale and
 // the per-channel partial sums in the same pass.  c / 8 is a power of two that divides NT, so a
 // thread's channel group is the same on every grid-stride trip and its sums stay in registers.
+// TD: dy's stored type (float, or __bf16 rounded once: tmr_bn_frozen_bwd_maxpool_x).
+template <typename TD>
 __global__ __launch_bounds__(NT) void bn_frozen_bwd_maxpool8q_k(
     const PoolGeo pg, int h, int w, FastDiv dQHW, FastDiv dQW, const float* __restrict__ y,
     const float* __restrict__ scale, const float* __restrict__ shift,
-    const float* __restrict__ mean, float* __restrict__ dy, float2* __restrict__ parts, int nq,
+    const float* __restrict__ mean, TD* __restrict__ dy, float2* __restrict__ parts, int nq,
     int lc8) {
   const int c8 = 1 << lc8, c = c8 * 8;
   const uint2* am = reinterpret_cast<const uint2*>(pg.am);
@@ -2305,19 +2312,21 @@ __global__ __launch_bounds__(NT) void scale_rows4_k(float4* __restrict__ w,
   }
 }
 
-// tmr_bn_frozen_bwd (dual false: yd .. dyd, parts_d NULL) and tmr_bn_frozen_bwd_ds
-int bn_frozen_bwd_impl(bool dual, const float* g, const void* zmask, int mask, const float* y,
-                       const float* scale, const float* shift, const float* mean, float* dy,
-                       const float* yd, const float* scale_d, const float* mean_d, float* dyd,
-                       float* dres, void* parts, void* parts_d, size_t parts_bytes, int rows, int c,
-                       int want_sums, hipStream_t stream) {
-  const char* name = dual ? "tmr_bn_frozen_bwd_ds" : "tmr_bn_frozen_bwd";
+// tmr_bn_frozen_bwd(_x) (dual false: yd .. dyd, parts_d NULL) and tmr_bn_frozen_bwd_ds(_x); the
+// fp32 entry points are out_bf16 = 0, g16 = NULL
+int bn_frozen_bwd_impl(const char* name, bool dual, const float* g, const void* zmask, int mask,
+                       const float* y, const float* scale, const float* shift, const float* mean,
+                       void* dy, const float* yd, const float* scale_d, const float* mean_d,
+                       void* dyd, float* dres, void* g16, void* parts, void* parts_d,
+                       size_t parts_bytes, int rows, int c, int want_sums, int out_bf16,
+                       hipStream_t stream) {
   TMR_CHECK_ARG(rows > 0 && c >= 8 && c % 8 == 0,
                 "%s: bad shape rows=%d c=%d (channels must be a multiple of 8)", name, rows, c);
   TMR_CHECK_ARG(fplan_covers(c), "%s: unsupported channel count %d", name, c);
   TMR_CHECK_ARG(aligned16(g, mask == 1 ? zmask : nullptr, y, yd, dy, dyd),
                 "%s: g / z / y / y_ds / dy / dy_ds / dres must be 16-B aligned", name);
   TMR_CHECK_ARG(aligned16(dres), "%s: dres must be 16-B aligned", name);
+  TMR_CHECK_ARG(aligned16(g16), "%s: g16 must be 16-B aligned", name);
   TMR_CHECK_ARG(mask >= 0 && mask <= 3, "%s: bad mask %d", name, mask);
   TMR_CHECK_ARG(g && scale && mean, "%s: null operand", name);
   TMR_CHECK_ARG(mask == 0 || mask == 2 || zmask, "%s: mask %d needs z (1) or the mask bits (3)", name, mask);
@@ -2333,10 +2342,53 @@ int bn_frozen_bwd_impl(bool dual, const float* g, const void* zmask, int mask, c
     pp = (float2*)parts;
     pd = (float2*)parts_d;
   }
-  return with_int_bool<4>(mask, dual, [&](auto M, auto DUAL) {
-    return launch("bn_frozen_bwd", bn_frozen_bwd8_k<M, DUAL>, dim3(p.nrb, p.cblocks), NT, stream, g,
-                  zmask, y, scale, shift, mean, dy, dres, yd, scale_d, mean_d, dyd, pp, pd, rows, c,
-                  p.rpb, p.cthreads);
+  return with_bool(out_bf16 != 0, [&](auto B16) {
+    using TD = std::conditional_t<B16.value, __bf16, float>;
+    return with_int_bool<4>(mask, dual, [&](auto M, auto DUAL) {
+      return launch("bn_frozen_bwd", bn_frozen_bwd8_k<M, DUAL, TD>, dim3(p.nrb, p.cblocks), NT,
+                    stream, g, zmask, y, scale, shift, mean, (TD*)dy, dres, yd, scale_d, mean_d,
+                    (TD*)dyd, (__bf16*)g16, pp, pd, rows, c, p.rpb, p.cthreads);
+    });
+  });
+}
+
+// tmr_bn_frozen_bwd_maxpool(_x)
+int bn_frozen_bwd_maxpool_impl(const char* name, const float* dyp, const uint8_t* argmax, int n,
+                               int h, int w, int ho, int wo, const float* y, const float* scale,
+                               const float* shift, const float* mean, void* dy, void* parts,
+                               size_t parts_bytes, int c, int want_sums, int out_bf16,
+                               hipStream_t stream) {
+  const long rows_l = (long)n * h * w;
+  TMR_CHECK_ARG(n > 0 && h > 0 && w > 0 && c >= 8 && c % 8 == 0 && rows_l < 0x7fffffffL,
+                "%s: bad shape n=%d h=%d w=%d c=%d (channels must be a multiple of 8)", name, n, h,
+                w, c);
+  const int c8 = c / 8;
+  TMR_CHECK_ARG((c8 & (c8 - 1)) == 0 && c8 <= NT,
+                "%s: unsupported channel count %d (c / 8 must be a power of two up to %d)", name, c,
+                NT);
+  TMR_CHECK_ARG(ho == (h + 2 - 3) / 2 + 1 && wo == (w + 2 - 3) / 2 + 1,
+                "%s: pooled %dx%d is not MaxPool2d(3,2,1) of %dx%d", name, ho, wo, h, w);
+  TMR_CHECK_ARG(dyp && argmax && y && scale && shift && mean && dy, "%s: null operand", name);
+  TMR_CHECK_ARG(aligned16(dyp, y, dy) && ((uintptr_t)argmax & 7) == 0,
+                "%s: dyp / y / dy must be 16-B aligned, argmax 8-B", name);
+  const int qh = (h + 1) / 2, qw = (w + 1) / 2;
+  const long nq_l = (long)n * qh * qw * c8;
+  TMR_CHECK_ARG(nq_l < 0x7fffffffL && (long)n * ho * wo * c8 < 0x7fffffffL, "%s: input too large",
+                name);
+  const int nq = (int)nq_l, nb = ew_blocks(nq);
+  float2* pp = nullptr;
+  if (want_sums) {
+    TMR_CHECK_ARG(parts && parts_bytes >= (size_t)nb * c * sizeof(float2),
+                  "%s: partials buffer too small (tmr_bn_frozen_bwd_maxpool_parts rows of c float2)",
+                  name);
+    pp = (float2*)parts;
+  }
+  return with_bool(out_bf16 != 0, [&](auto B16) {
+    using TD = std::conditional_t<B16.value, __bf16, float>;
+    return launch("bn_frozen_bwd_maxpool", bn_frozen_bwd_maxpool8q_k<TD>, nb, NT, stream,
+                  pool_geo(dyp, argmax, h, w, ho, wo), h, w, make_fastdiv((uint32_t)(qh * qw)),
+                  make_fastdiv((uint32_t)qw), y, scale, shift, mean, (TD*)dy, pp, nq,
+                  __builtin_ctz(c8));
   });
 }
 
@@ -2359,9 +2411,18 @@ TMR_API int tmr_bn_frozen_bwd(const float* g, const void* zmask, int mask, const
                               const float* scale, const float* shift, const float* mean,
                               float* dy, float* dres, void* parts, size_t parts_bytes, int rows,
                               int c, int want_sums, hipStream_t stream) {
-  return bn_frozen_bwd_impl(false, g, zmask, mask, y, scale, shift, mean, dy, nullptr, nullptr,
-                            nullptr, nullptr, dres, parts, nullptr, parts_bytes, rows, c, want_sums,
-                            stream);
+  return bn_frozen_bwd_impl("tmr_bn_frozen_bwd", false, g, zmask, mask, y, scale, shift, mean, dy,
+                            nullptr, nullptr, nullptr, nullptr, dres, nullptr, parts, nullptr,
+                            parts_bytes, rows, c, want_sums, 0, stream);
+}
+
+TMR_API int tmr_bn_frozen_bwd_x(const float* g, const void* zmask, int mask, const float* y,
+                                const float* scale, const float* shift, const float* mean,
+                                void* dy, float* dres, void* g16, void* parts, size_t parts_bytes,
+                                int rows, int c, int want_sums, int out_bf16, hipStream_t stream) {
+  return bn_frozen_bwd_impl("tmr_bn_frozen_bwd_x", false, g, zmask, mask, y, scale, shift, mean, dy,
+                            nullptr, nullptr, nullptr, nullptr, dres, g16, parts, nullptr,
+                            parts_bytes, rows, c, want_sums, out_bf16, stream);
 }
 
 TMR_API int tmr_bn_frozen_bwd_ds(const float* g, const void* zmask, int mask, const float* y,
@@ -2370,8 +2431,20 @@ TMR_API int tmr_bn_frozen_bwd_ds(const float* g, const void* zmask, int mask, co
                                  const float* mean_d, float* dyd, float* dres, void* parts,
                                  void* parts_d, size_t parts_bytes, int rows, int c, int want_sums,
                                  hipStream_t stream) {
-  return bn_frozen_bwd_impl(true, g, zmask, mask, y, scale, shift, mean, dy, yd, scale_d, mean_d,
-                            dyd, dres, parts, parts_d, parts_bytes, rows, c, want_sums, stream);
+  return bn_frozen_bwd_impl("tmr_bn_frozen_bwd_ds", true, g, zmask, mask, y, scale, shift, mean, dy,
+                            yd, scale_d, mean_d, dyd, dres, nullptr, parts, parts_d, parts_bytes,
+                            rows, c, want_sums, 0, stream);
+}
+
+TMR_API int tmr_bn_frozen_bwd_ds_x(const float* g, const void* zmask, int mask, const float* y,
+                                   const float* scale, const float* shift, const float* mean,
+                                   void* dy, const float* yd, const float* scale_d,
+                                   const float* mean_d, void* dyd, float* dres, void* g16,
+                                   void* parts, void* parts_d, size_t parts_bytes, int rows, int c,
+                                   int want_sums, int out_bf16, hipStream_t stream) {
+  return bn_frozen_bwd_impl("tmr_bn_frozen_bwd_ds_x", true, g, zmask, mask, y, scale, shift, mean,
+                            dy, yd, scale_d, mean_d, dyd, dres, g16, parts, parts_d, parts_bytes,
+                            rows, c, want_sums, out_bf16, stream);
 }
 
 TMR_API int tmr_bn_frozen_bwd_maxpool_parts(int n, int h, int w, int c) {
@@ -2389,35 +2462,19 @@ TMR_API int tmr_bn_frozen_bwd_maxpool(const float* dyp, const uint8_t* argmax, i
                                       const float* shift, const float* mean, float* dy,
                                       void* parts, size_t parts_bytes, int c, int want_sums,
                                       hipStream_t stream) {
-  const long rows_l = (long)n * h * w;
-  TMR_CHECK_ARG(n > 0 && h > 0 && w > 0 && c >= 8 && c % 8 == 0 && rows_l < 0x7fffffffL,
-                "tmr_bn_frozen_bwd_maxpool: bad shape n=%d h=%d w=%d c=%d (channels must be a "
-                "multiple of 8)", n, h, w, c);
-  const int c8 = c / 8;
-  TMR_CHECK_ARG((c8 & (c8 - 1)) == 0 && c8 <= NT,
-                "tmr_bn_frozen_bwd_maxpool: unsupported channel count %d (c / 8 must be a power of "
-                "two up to %d)", c, NT);
-  TMR_CHECK_ARG(ho == (h + 2 - 3) / 2 + 1 && wo == (w + 2 - 3) / 2 + 1,
-                "tmr_bn_frozen_bwd_maxpool: pooled %dx%d is not MaxPool2d(3,2,1) of %dx%d", ho, wo, h, w);
-  TMR_CHECK_ARG(dyp && argmax && y && scale && shift && mean && dy,
-                "tmr_bn_frozen_bwd_maxpool: null operand");
-  TMR_CHECK_ARG(aligned16(dyp, y, dy) && ((uintptr_t)argmax & 7) == 0,
-                "tmr_bn_frozen_bwd_maxpool: dyp / y / dy must be 16-B aligned, argmax 8-B");
-  const int qh = (h + 1) / 2, qw = (w + 1) / 2;
-  const long nq_l = (long)n * qh * qw * c8;
-  TMR_CHECK_ARG(nq_l < 0x7fffffffL && (long)n * ho * wo * c8 < 0x7fffffffL,
-                "tmr_bn_frozen_bwd_maxpool: input too large");
-  const int nq = (int)nq_l, nb = ew_blocks(nq);
-  float2* pp = nullptr;
-  if (want_sums) {
-    TMR_CHECK_ARG(parts && parts_bytes >= (size_t)nb * c * sizeof(float2),
-                  "tmr_bn_frozen_bwd_maxpool: partials buffer too small "
-                  "(tmr_bn_frozen_bwd_maxpool_parts rows of c float2)");
-    pp = (float2*)parts;
-  }
-  return launch("bn_frozen_bwd_maxpool", bn_frozen_bwd_maxpool8q_k, nb, NT, stream,
-                pool_geo(dyp, argmax, h, w, ho, wo), h, w, make_fastdiv((uint32_t)(qh * qw)),
-                make_fastdiv((uint32_t)qw), y, scale, shift, mean, dy, pp, nq, __builtin_ctz(c8));
+  return bn_frozen_bwd_maxpool_impl("tmr_bn_frozen_bwd_maxpool", dyp, argmax, n, h, w, ho, wo, y,
+                                    scale, shift, mean, dy, parts, parts_bytes, c, want_sums, 0,
+                                    stream);
+}
+
+TMR_API int tmr_bn_frozen_bwd_maxpool_x(const float* dyp, const uint8_t* argmax, int n, int h,
+                                        int w, int ho, int wo, const float* y, const float* scale,
+                                        const float* shift, const float* mean, void* dy,
+                                        void* parts, size_t parts_bytes, int c, int want_sums,
+                                        int out_bf16, hipStream_t stream) {
+  return bn_frozen_bwd_maxpool_impl("tmr_bn_frozen_bwd_maxpool_x", dyp, argmax, n, h, w, ho, wo, y,
+                                    scale, shift, mean, dy, parts, parts_bytes, c, want_sums,
+                                    out_bf16, stream);
 }
 
 TMR_API int tmr_bn_frozen_finalize(const void* parts, int nparts, int c, const float* inv,

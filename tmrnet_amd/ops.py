@@ -806,29 +806,31 @@ def weight_to_crsk(w, bf16=True):
                    lambda out: [(w.data_ptr(), out, k, c, r * s, c, 1, int(bf16))])
 
 
-def weight_to_crsk_scaled(w, scale):
+def weight_to_crsk_scaled(w, scale, bf16=False):
     """weight_to_crsk(w, bf16=False) times scale[k] per output channel -> (Cin, R, S, Cout) fp32:
     the dgrad operand of a frozen-BN unit, whose dy = g*scale is folded into the weights.  The
     session refreshes it from the current w and scale (the same `scale` tensor every step: the
-    trunk's coefficient buffer) in its one launch."""
+    trunk's coefficient buffer) in its one launch.  bf16=True: the fp32 product rounded once to
+    bf16 (RNE) -- the frozen step with bf16 backward convs (TMR_IO_WT_BF16)."""
     k, c, r, s = w.shape
     _req(w, "w"); _req(scale, "scale")
     if scale.numel() != k:
         raise RuntimeError("weight_to_crsk_scaled: %d scales for %d output channels"
                            % (scale.numel(), k))
+    b16 = int(bool(bf16))
 
     def convert():
-        out = _empty((c, r, s, k), w)
+        out = _empty((c, r, s, k), w, dtype=BF16 if b16 else f32)
         epb = int(query("tmr_weight_layouts_epb"))
         tab = np.zeros(1, dtype=_WL_DTYPE)
-        tab[0] = (w.data_ptr(), out.data_ptr(), out.numel(), 0, k, c, r * s, c, 1, 0)
+        tab[0] = (w.data_ptr(), out.data_ptr(), out.numel(), 0, k, c, r * s, c, 1, b16)
         tab = torch.from_numpy(tab.view(np.uint8).copy()).to(w.device)
         sp = torch.tensor([scale.data_ptr()], dtype=torch.int64).to(w.device)
         call("tmr_weight_layouts_multi_scaled", tab, sp, 1, (out.numel() + epb - 1) // epb,
              stream_ptr())
         return out
-    return _layout((w.data_ptr(), "crsk_s", k, c, r * s, c, scale.data_ptr()), convert,
-                   lambda out: [(w.data_ptr(), out, k, c, r * s, c, 1, 0, scale)])
+    return _layout((w.data_ptr(), "crsk_s", k, c, r * s, c, scale.data_ptr(), b16), convert,
+                   lambda out: [(w.data_ptr(), out, k, c, r * s, c, 1, b16, scale)])
 
 
 def weight_to_crsk_grouped(w, groups, bf16=True):
@@ -1134,6 +1136,10 @@ def _frozen_mask(mask, z, bits, y):
     return None
 
 
+def _frozen_out(like, want, bf16):
+    return torch.empty_like(like, dtype=BF16 if bf16 else f32) if want else None
+
+
 def bn_frozen_bwd(g, y, scale, shift, mean, mask, z=None, bits=None, want_dy=True,
                   dres_inplace=False, want_sums=True):
     """Frozen-BN backward of one unit in one pass (tmr_bn_frozen_bwd) -> (dy, parts, nparts).
@@ -1157,6 +1163,31 @@ def bn_frozen_bwd(g, y, scale, shift, mean, mask, z=None, bits=None, want_dy=Tru
          ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), rows, c, int(want_sums),
          stream_ptr())
     return dy, parts, nparts
+
+
+def bn_frozen_bwd_x(g, y, scale, shift, mean, mask, z=None, bits=None, want_dy=True,
+                    dres_inplace=False, want_sums=True, dy16=False, want_g16=False):
+    """bn_frozen_bwd with dy stored fp32 or (dy16) rounded once to bf16, and (want_g16) the masked
+    g itself as bf16 (tmr_bn_frozen_bwd_x) -> (dy, g16, parts, nparts).  dres and the partials are
+    bn_frozen_bwd's bit for bit.  want_dy=False, want_g16=True, mask 0: the cast pass over a block
+    output's gradient (with the sums of (g, y) if wanted)."""
+    _req(g, "g"); _req(y, "y")
+    if g.shape != y.shape:
+        raise RuntimeError("bn_frozen_bwd_x: g shape %s != y %s" % (tuple(g.shape), tuple(y.shape)))
+    c = y.shape[-1]
+    rows = y.numel() // c
+    zm = _frozen_mask(mask, z, bits, y)
+    dy = _frozen_out(y, want_dy, dy16)
+    g16 = _frozen_out(y, want_g16, True)
+    parts, nparts = None, 0
+    if want_sums:
+        nparts = query("tmr_bn_frozen_bwd_parts", rows, c)
+        parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
+    call("tmr_bn_frozen_bwd_x", g, zm, int(mask), y, scale, shift, mean, dy,
+         g if dres_inplace else None, g16, parts,
+         ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), rows, c, int(want_sums),
+         int(bool(dy16)), stream_ptr())
+    return dy, g16, parts, nparts
 
 
 def bn_frozen_bwd_ds(g, y, scale, shift, mean, yd, scale_d, mean_d, mask, z=None, bits=None,
@@ -1184,6 +1215,33 @@ def bn_frozen_bwd_ds(g, y, scale, shift, mean, yd, scale_d, mean_d, mask, z=None
     return dy, dyd, parts, parts_d, nparts
 
 
+def bn_frozen_bwd_ds_x(g, y, scale, shift, mean, yd, scale_d, mean_d, mask, z=None, bits=None,
+                       want_dy=True, dres_inplace=False, want_sums=True, dy16=False,
+                       want_g16=False):
+    """bn_frozen_bwd_ds with both dy's fp32 or (dy16) bf16 and (want_g16) the masked g as bf16
+    (tmr_bn_frozen_bwd_ds_x) -> (dy, dy_ds, g16, parts, parts_ds, nparts)."""
+    _req(g, "g"); _req(y, "y"); _req(yd, "y_ds")
+    if not (g.shape == y.shape == yd.shape):
+        raise RuntimeError("bn_frozen_bwd_ds_x: g, y and y_ds must have one shape")
+    c = y.shape[-1]
+    rows = y.numel() // c
+    zm = _frozen_mask(mask, z, bits, y)
+    dy = _frozen_out(y, want_dy, dy16)
+    dyd = _frozen_out(yd, want_dy, dy16)
+    g16 = _frozen_out(y, want_g16, True)
+    parts = parts_d = None
+    nparts = 0
+    if want_sums:
+        nparts = query("tmr_bn_frozen_bwd_parts", rows, c)
+        parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
+        parts_d = torch.empty_like(parts)
+    call("tmr_bn_frozen_bwd_ds_x", g, zm, int(mask), y, scale, shift, mean, dy, yd, scale_d,
+         mean_d, dyd, g if dres_inplace else None, g16, parts, parts_d,
+         ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), rows, c, int(want_sums),
+         int(bool(dy16)), stream_ptr())
+    return dy, dyd, g16, parts, parts_d, nparts
+
+
 def bn_frozen_bwd_maxpool(dyp, am, y, scale, shift, mean, want_sums=True):
     """The stem's frozen-BN backward: MaxPool2d(3,2,1) backward (gathered from the pooled gradient
     and argmax), the ReLU mask from fmaf(y, scale, shift), dy = g*scale and the partial sums in
@@ -1198,6 +1256,23 @@ def bn_frozen_bwd_maxpool(dyp, am, y, scale, shift, mean, want_sums=True):
         parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
     call("tmr_bn_frozen_bwd_maxpool", dyp, am, n, h, w, ho, wo, y, scale, shift, mean, dy, parts,
          ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), c, int(want_sums), stream_ptr())
+    return dy, parts, nparts
+
+
+def bn_frozen_bwd_maxpool_x(dyp, am, y, scale, shift, mean, want_sums=True, dy16=False):
+    """bn_frozen_bwd_maxpool with dy fp32 or (dy16) rounded once to bf16
+    (tmr_bn_frozen_bwd_maxpool_x); the same partials -> (dy, parts, nparts)."""
+    _req(dyp, "dyp"); _req(y, "y"); _req(am, "argmax", torch.uint8)
+    n, h, w, c = y.shape
+    _, ho, wo, _ = dyp.shape
+    dy = _frozen_out(y, True, dy16)
+    parts, nparts = None, 0
+    if want_sums:
+        nparts = query("tmr_bn_frozen_bwd_maxpool_parts", n, h, w, c)
+        parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
+    call("tmr_bn_frozen_bwd_maxpool_x", dyp, am, n, h, w, ho, wo, y, scale, shift, mean, dy, parts,
+         ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), c, int(want_sums),
+         int(bool(dy16)), stream_ptr())
     return dy, parts, nparts
 
 

@@ -19,6 +19,7 @@ The other step kinds, each specified by the block comment named:
   * precision "bf16": bf16 conv operands and activations (BF16_STORE, FULL16, ACT16, G16, R16);
   * precision "bf16-bwd": the fp32 forward, bf16 operands in the backward convs only (BWD16);
   * frozen BatchNorm (freeze_bn): a train step on the running statistics ("frozen BatchNorm");
+    with backward="bf16" its backward convs in bf16 math (_frozen16);
   * infer16: eval mode with bf16 activations, opt-in (_infer16, TrunkFn._forward_eval).
 How the units of a step are put together: "the conv+BN unit" below, DESIGN.md §29.
 """
@@ -320,7 +321,11 @@ def _dgrad_weights(w, x, math, groups, bwd16, scale):
     the KRSC weights; the stem's 3 input channels: no dgrad).  scale: the frozen step's fold."""
     c = w.shape[1]
     if bwd16:
-        return ops.weight_to_crsk(w.detach().contiguous()) if c % 8 == 0 else None
+        if c % 8:
+            return None
+        if scale is not None:   # (the frozen16 step: the fp32 product w*scale rounded once)
+            return ops.weight_to_crsk_scaled(w.detach().contiguous(), scale, bf16=True)
+        return ops.weight_to_crsk(w.detach().contiguous())
     if scale is not None:
         return ops.weight_to_crsk_scaled(w.detach().contiguous(), scale)
     x16 = _full16(math) and x.dtype == torch.bfloat16
@@ -465,7 +470,7 @@ def _unit_dy(rec, dz, grads, parts=None, pool=None, want_dres=False, dres_inplac
 
 
 def _conv_bwd(rec, dy, grads, dw=None, dx_out=None, dx_beta=0.0, need_dx=True, fuse_prev=None,
-              g16=False, r16=False):
+              g16=False, r16=False, g16_y32=False):
     """wgrad (unless dw came with dy, _wgrad_dy) and dgrad (optionally accumulated into dx_out)
     of one unit from its conv's output gradient dy -> (dx, fused).
 
@@ -474,7 +479,9 @@ def _conv_bwd(rec, dy, grads, dw=None, dx_out=None, dx_beta=0.0, need_dx=True, f
     g16: the fused dgrad may store fuse_prev's masked gradient as bf16 (TMR_IO_G16) when that unit
     has no residual and the dgrad runs on the bf16 LDS-DMA engine (the bf16-activation step).
     r16: the same for fuse_prev a block output (R16): the dgrad adds into dx_out (bf16 in place,
-    or fp32 read and a new bf16 tensor returned)."""
+    or fp32 read and a new bf16 tensor returned).
+    g16_y32 (the frozen16 step, no knob): fuse_prev's masked gradient (mask 2) stored bf16 beside
+    its fp32 y; a unit whose dgrad cannot take that form raises -- no rounding moves silently."""
     x = rec.x
     r, s = rec.conv.weight.shape[2:]
     grp = rec.groups
@@ -502,6 +509,23 @@ def _conv_bwd(rec, dy, grads, dw=None, dx_out=None, dx_beta=0.0, need_dx=True, f
     gb = g16 and G16 and mask == 2 and dx_out is None and dx_beta == 0.0 and bf8
     rb = (r16 and R16 and mask in (1, 3) and dx_out is not None and dx_beta == 1.0 and bf8
           and grp == 1)
+    if g16_y32:
+        shape = (tuple(dy.shape), tuple(rec.conv.weight.shape), rec.stride)
+        gb = (mask == 2 and dx_out is None and dx_beta == 0.0 and wt and grp == 1
+              and wdg.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16
+              and p.y.dtype == torch.float32 and p.y.shape[-1] % 8 == 0)
+        if not gb:
+            raise RuntimeError("frozen BN, bf16 backward: the fused dgrad of dy %s, weight %s, "
+                               "stride %d cannot store its masked gradient bf16 (mask %d)"
+                               % (shape + (mask,)))
+        try:
+            dx, pp, npp = ops.conv_dgrad_bnbwd(dy, wdg, hw, rec.stride, rec.pad, p.y, p.mean, mask,
+                                               scale=p.scale, shift=p.shift, math=rec.math, wt=wt,
+                                               g16=True)
+        except RuntimeError as e:
+            raise RuntimeError("frozen BN, bf16 backward: the fused dgrad of dy %s, weight %s, "
+                               "stride %d refused the bf16 masked gradient: %s" % (shape + (e,)))
+        return dx, (pp, npp)
     old = None
     if rb and dx_out.dtype != torch.bfloat16:   # fp32 old dx -> a new bf16 dx
         old, dx_out = dx_out, None
@@ -575,9 +599,27 @@ def _bn_modes(share):
 
 
 def _frozen_step(share):
-    """The frozen-BN train step applies: bn_frozen on a train-mode fp32 ResNet-50 share."""
+    """The frozen-BN train step applies: bn_frozen on a train-mode fp32 ResNet-50 share, or -- with
+    freeze_bn(backward="bf16") -- on an "fp32" or "bf16-bwd" one (_frozen16)."""
     return bool(getattr(share, "bn_frozen", False) and share.training
-                and share.precision == "fp32")
+                and (share.precision == "fp32" or _frozen16(share)))
+
+
+# freeze_bn(backward="bf16"), "frozen16": the frozen step's fp32 forward (bit for bit, plus the
+# BWD16 step's bf16 operand copies through the dual apply forms on the eval coefficients) and
+# every trunk conv's dgrad / wgrad in bf16 math on three roundings (RNE, each once, where the
+# value is produced): the bf16 input copy x; the weights -- a folded unit's dgrad reads the bf16
+# CRSK copy of the fp32 product w[k]*scale[k], the single-pass units (the last block's bn3 /
+# downsample BN, the stem) the plain bf16 forms; the output-gradient operand -- bf16(g), the
+# masked gradient unscaled, for a folded unit (tmr_scale_rows scales the fp32 dW), bf16(g*scale)
+# for a single-pass unit.  bn1 / bn2's g is stored bf16 by the fused dgrad that produces it
+# (TMR_IO_G16 beside an fp32 y; its sums are of the rounded values); a block output's g stays
+# fp32 (the residual stream; sums of the fp32 values) and one pass per block writes its bf16
+# copy (tmr_bn_frozen_bwd_x: the downsample BN's sums-only pass, or a plain cast).  DESIGN.md §31.
+def _frozen16(share):
+    return bool(getattr(share, "bn_frozen", False) and share.training
+                and getattr(share, "bn_frozen_bwd", None) == "bf16"
+                and share.precision in ("fp32", BWD16))
 
 
 def _frozen_coefs(share):
@@ -635,7 +677,9 @@ class TrunkFn(torch.autograd.Function):
         fz = _frozen_coefs(share) if _frozen_step(share) else None
         # every conv weight layout of the step in one launch (ops.layout_session)
         key = ("resnet50", share.training, bool(keep), share.precision, _infer16(share))
-        with ops.layout_session(share, key + ("frozen",) if fz is not None else key):
+        if fz is not None:
+            key += ("frozen16" if _frozen16(share) else "frozen",)
+        with ops.layout_session(share, key):
             return TrunkFn._forward(ctx, x4, share, keep, params, fz)
 
     @staticmethod
@@ -645,11 +689,13 @@ class TrunkFn(torch.autograd.Function):
         mt = _fwd_math(share.precision)
         ctx.keep = keep
         ctx.frozen = fz is not None
+        ctx.frozen16 = f16z = bool(fz is not None and keep and _frozen16(share))
         if not share.training:
             return TrunkFn._forward_eval(x4, conv1, bn1, layers, mt, _infer16(share))
         # the BWD16 step: the fp32 forward plus the bf16 copies its bf16-math backward reads
         # (without a backward to record -- no grad -- it is the fp32 path itself)
-        bw = bool(keep and share.precision == BWD16)
+        # (frozen16: the same copies under the frozen step, whichever precision the share has)
+        bw = bool(keep and share.precision == BWD16) if fz is None else f16z
         a16 = _act16(mt)                    # every activation bf16: no fp32 copies
         f16 = _full16(mt) and not a16
         st = _TrainUnits(mt, keep, bwd16=bw, frozen=fz)
@@ -696,6 +742,8 @@ class TrunkFn(torch.autograd.Function):
                         blocks[-1][1][-1].z = None
                     del z1, z2, idn   # (their fp32 z's were only this block's forward operands)
                 blocks.append((blk, [r1, r2, rd, r3]))
+        if f16z and blocks[-1][1][-1].zbits is not None:
+            blocks[-1][1][-1].z = None   # (the last block's mask is in the bits too)
         feat = ops.avgpool_fwd(h)
         if st.nbt:   # (none under frozen BN: no counter moves)
             ops.counters_add_one(st.nbt)
@@ -798,8 +846,11 @@ class TrunkFn(torch.autograd.Function):
         tmr_bn_frozen_bwd / _maxpool; every other unit's g comes masked, with its partial sums,
         from the fused dgrad that produced it, and its dy = g*scale lives in the conv operands
         (_frozen_unit_bwd).  A downsample BN needs sum g*(y_ds - mean_ds) of its own: one
-        sums-only pass over (g, y_ds), skipped with affine=False."""
+        sums-only pass over (g, y_ds), skipped with affine=False.  ctx.frozen16: the same walk on
+        the bf16 operands of freeze_bn(backward="bf16")."""
         grads = {}
+        f16 = ctx.frozen16   # bf16 backward convs: the operand dtypes of "_frozen16" above
+        mid = dict(g16_y32=True) if f16 else {}   # bn1 / bn2's g: stored bf16 by the fused dgrad
         g = _backward_head(ctx, dfeat)   # grad at the last block output
         pending = None     # the fused dgrad's partial sums of g (None: g is unmasked)
         for blk, brec, prev3 in _backward_blocks(ctx, grads, lambda recs: recs[-1]):
@@ -813,40 +864,66 @@ class TrunkFn(torch.autograd.Function):
                     dict(mask=1, z=r3.z)
                 if has_ds:
                     sums = s3 or _bn_wants_grad(rd.bn)
-                    dy3, dyd, p3, pd, npp = ops.bn_frozen_bwd_ds(
-                        g, r3.y, r3.scale, r3.shift, r3.mean, rd.y, rd.scale, rd.mean,
-                        dres_inplace=True, want_sums=sums, **mk)
+                    if f16:
+                        dy3, dyd, _, p3, pd, npp = ops.bn_frozen_bwd_ds_x(
+                            g, r3.y, r3.scale, r3.shift, r3.mean, rd.y, rd.scale, rd.mean,
+                            dres_inplace=True, want_sums=sums, dy16=True, **mk)
+                    else:
+                        dy3, dyd, p3, pd, npp = ops.bn_frozen_bwd_ds(
+                            g, r3.y, r3.scale, r3.shift, r3.mean, rd.y, rd.scale, rd.mean,
+                            dres_inplace=True, want_sums=sums, **mk)
                     _frozen_affine(r3, (p3, npp) if sums else None, grads)
                     _frozen_affine(rd, (pd, npp) if sums else None, grads)
+                elif f16:
+                    dy3, _, p3, npp = ops.bn_frozen_bwd_x(g, r3.y, r3.scale, r3.shift, r3.mean,
+                                                          dres_inplace=True, want_sums=s3,
+                                                          dy16=True, **mk)
+                    _frozen_affine(r3, (p3, npp) if s3 else None, grads)
                 else:
                     dy3, p3, npp = ops.bn_frozen_bwd(g, r3.y, r3.scale, r3.shift, r3.mean,
                                                      dres_inplace=True, want_sums=s3, **mk)
                     _frozen_affine(r3, (p3, npp) if s3 else None, grads)
-                dz2, fz2 = _frozen_dy_bwd(r3, dy3, grads, fuse_prev=r2)
+                dz2, fz2 = _frozen_dy_bwd(r3, dy3, grads, fuse_prev=r2, **mid)
                 del dy3
+                gop = None
             else:
-                if has_ds and _bn_wants_grad(rd.bn):
+                dsum = has_ds and _bn_wants_grad(rd.bn)
+                gop = g    # the folded units' conv operand: g, or (f16) its bf16 copy
+                if f16:
+                    # one pass over the block output's fp32 g writes bf16(g): the downsample
+                    # BN's sums-only pass with one more store, else a plain cast
+                    u = rd if dsum else r3
+                    _, gop, pd, npp = ops.bn_frozen_bwd_x(g, u.y, u.scale, u.shift, u.mean,
+                                                          mask=0, want_dy=False, want_sums=dsum,
+                                                          want_g16=True)
+                elif dsum:
                     _, pd, npp = ops.bn_frozen_bwd(g, rd.y, rd.scale, rd.shift, rd.mean, mask=0,
                                                    want_dy=False)
+                if dsum:
                     _frozen_affine(rd, (pd, npp), grads)
-                dz2, fz2 = _frozen_unit_bwd(r3, g, grads, parts=pending, fuse_prev=r2)
+                dz2, fz2 = _frozen_unit_bwd(r3, gop, grads, parts=pending, fuse_prev=r2, **mid)
             dres = g   # masked: the identity branch's gradient
-            dz1, fz1 = _frozen_unit_bwd(r2, dz2, grads, parts=fz2, fuse_prev=r1)
+            dz1, fz1 = _frozen_unit_bwd(r2, dz2, grads, parts=fz2, fuse_prev=r1, **mid)
             del dz2
             if has_ds:
                 if dyd is not None:
                     dres, _ = _frozen_dy_bwd(rd, dyd, grads)
                     del dyd
                 else:
-                    dres, _ = _frozen_unit_bwd(rd, dres, grads)
+                    dres, _ = _frozen_unit_bwd(rd, gop, grads)
+            del gop
             g, pending = _frozen_unit_bwd(r1, dz1, grads, parts=fz1, dx_out=dres, dx_beta=1.0,
                                           fuse_prev=prev3)
             del dz1, brec, dres
         am, _ = ctx.pool
         st = ctx.stem[0]
         ss = _bn_wants_grad(st.bn)
-        dy0, p0, np0 = ops.bn_frozen_bwd_maxpool(g, am, st.y, st.scale, st.shift, st.mean,
-                                                 want_sums=ss)
+        if f16:
+            dy0, p0, np0 = ops.bn_frozen_bwd_maxpool_x(g, am, st.y, st.scale, st.shift, st.mean,
+                                                       want_sums=ss, dy16=True)
+        else:
+            dy0, p0, np0 = ops.bn_frozen_bwd_maxpool(g, am, st.y, st.scale, st.shift, st.mean,
+                                                     want_sums=ss)
         _frozen_affine(st, (p0, np0) if ss else None, grads)
         _frozen_dy_bwd(st, dy0, grads, need_dx=False)
         return _backward_tail(ctx, grads)
@@ -877,6 +954,7 @@ class ResNet50Share(nn.Sequential):
         # frozen BatchNorm (tmrnet_amd.freeze_bn): the BN modules stay in eval mode whatever
         # train(mode) says, and a train-mode step runs on the running statistics
         self.bn_frozen = False
+        self.bn_frozen_bwd = None   # "bf16": the frozen step's backward convs in bf16 math
         mods = (nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False), nn.BatchNorm2d(64),
                 nn.ReLU(inplace=True), nn.MaxPool2d(3, stride=2, padding=1),
                 _make_layer(64, 64, 3, 1), _make_layer(256, 128, 4, 2),
@@ -936,22 +1014,38 @@ def _share_of(model):
                     "one as .share or .res, got %s" % type(model).__name__)
 
 
-def freeze_bn(model_or_share, affine=True):
+def freeze_bn(model_or_share, affine=True, backward=None):
     """Freeze the trunk's BatchNorm: every BatchNorm2d of the share goes to eval mode and stays
     there through train() / eval() (share.bn_frozen = True); a train-mode step then normalises
     with the running statistics, writes none of them, and back-propagates dy = g*scale.
     affine=False also stops training the BN weights and biases (requires_grad=False;
-    torchvision's FrozenBatchNorm2d).  ResNet-50 shares of precision "fp32" only.  Call it after
-    load_checkpoint and before the optimizer is built.  Returns its argument."""
+    torchvision's FrozenBatchNorm2d).  ResNet-50 shares of precision "fp32" only.
+    backward="bf16" (share.bn_frozen_bwd): the same fp32 forward -- logits and loss bit for bit --
+    with every trunk conv's dgrad and wgrad in bf16 math on fp32 accumulation, the backward of
+    precision "bf16-bwd" under frozen BatchNorm; ResNet-50 shares of precision "fp32" or
+    "bf16-bwd".  backward=None or "fp32": the fp32 backward.  Call it after load_checkpoint and
+    before the optimizer is built.  Returns its argument."""
     from .resnest import ResNeSt50Share
+    if backward not in (None, "fp32", "bf16"):
+        raise ValueError("freeze_bn: backward must be None, 'fp32' or 'bf16', got %r" % (backward,))
     share = _share_of(model_or_share)
-    if isinstance(share, ResNeSt50Share):
-        raise ValueError("freeze_bn: frozen BatchNorm exists for the ResNet-50 trunk "
-                         "(precision 'fp32') only, not for a ResNeSt-50 share")
-    if share.precision != "fp32":
-        raise ValueError("freeze_bn: frozen BatchNorm exists for precision 'fp32' only, not for "
-                         "%r" % (share.precision,))
+    if backward == "bf16":
+        if isinstance(share, ResNeSt50Share):
+            raise ValueError("freeze_bn: backward=\"bf16\" exists for the ResNet-50 trunk only, "
+                             "not for a ResNeSt-50 share")
+        if share.precision not in ("fp32", BWD16):
+            raise ValueError("freeze_bn: backward=\"bf16\" exists for precision 'fp32' and "
+                             "'bf16-bwd' (both run the fp32 forward), not for %r"
+                             % (share.precision,))
+    else:
+        if isinstance(share, ResNeSt50Share):
+            raise ValueError("freeze_bn: frozen BatchNorm exists for the ResNet-50 trunk "
+                             "(precision 'fp32') only, not for a ResNeSt-50 share")
+        if share.precision != "fp32":
+            raise ValueError("freeze_bn: frozen BatchNorm exists for precision 'fp32' only, not for "
+                             "%r" % (share.precision,))
     share.bn_frozen = True
+    share.bn_frozen_bwd = "bf16" if backward == "bf16" else None
     for m in _share_bns(share):
         m.training = False
         if not affine:
@@ -961,10 +1055,12 @@ def freeze_bn(model_or_share, affine=True):
 
 
 def unfreeze_bn(model_or_share):
-    """Undo freeze_bn: clear share.bn_frozen, put the BatchNorm modules back to share.training
-    and their weights and biases back to requires_grad=True.  Returns its argument."""
+    """Undo freeze_bn: clear share.bn_frozen (and bn_frozen_bwd), put the BatchNorm modules back to
+    share.training and their weights and biases back to requires_grad=True.  Returns its
+    argument."""
     share = _share_of(model_or_share)
     share.bn_frozen = False
+    share.bn_frozen_bwd = None
     for m in _share_bns(share):
         m.training = share.training
         m.weight.requires_grad_(True)
