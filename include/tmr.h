@@ -124,6 +124,17 @@ int tmr_conv2d_fwd(const tmr_conv_desc* d, const float* x, const float* w_krsc,
 int tmr_conv2d_fwd_fused(const tmr_conv_desc* d, const float* x, const float* w_krsc,
                          const float* scale, const float* shift, const float* residual, float* y,
                          int relu, hipStream_t stream);
+/* tmr_conv2d_fwd_fused on fp32 operands in fp32 math that also writes a bf16 copy of its output:
+ * z = [relu](fmaf(conv(x, w_krsc), scale[k], shift[k]) + residual) stored fp32 as above, and the
+ * same value rounded once to bf16 (RNE) into z16, a dense (n, ho, wo, k) bf16 tensor (the operand
+ * copy the bf16 backward convs of the frozen-BatchNorm step read).  The residual stays fp32.
+ * LDS-DMA engine only, and no fall-back: TMR_MATH_F32 without bf16-stored operands, no groups,
+ * dense z (y_ld == k), even k, z16 non-null, 16-B aligned and overlapping neither z nor the
+ * residual, a shape the fp32 LDS-DMA forward serves (16-B aligned x / w, 4-channel pieces) -- any
+ * other call is refused before anything is launched.  Frame chunks advance z16 with z. */
+int tmr_conv2d_fwd_fused_dual(const tmr_conv_desc* d, const float* x, const float* w_krsc,
+                              const float* scale, const float* shift, const float* residual,
+                              float* z, void* z16, int relu, hipStream_t stream);
 /* Forward conv whose epilogue also emits BatchNorm batch-statistic partials of y:
  * stats = float4 [tmr_conv2d_fwd_stats_parts(d)][k] of (count, mean, M2, 0) per output-row
  * tile, consumed by tmr_bn_finalize (fuses the separate statistics pass of nn.BatchNorm2d). */

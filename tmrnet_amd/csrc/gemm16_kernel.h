@@ -1158,6 +1158,16 @@ int launch16_cfg(const GemmArgs& a, bool tapv, dim3 grid, hipStream_t st) {
   if constexpr (MODE == MODE_FWD && F32 == 0) {
     if (a.c16 && a.scale) return launch16_inf16<BM, BN, WM, WN>(a, tapv, grid, st);
   }
+  // the fp32 inference epilogue that also writes the bf16 copy GemmArgs::Cbf: its own kernels too
+  if constexpr (MODE == MODE_FWD && F32 != 0) {
+    if (a.Cbf) {
+      if constexpr (dual32_cfg<BM, BN, WM, WN>()) {
+        return launch16_dual32<BM, BN, WM, WN>(a, tapv, grid, st);
+      } else {
+        TMR_CHECK_ARG(false, "gemm16: the fp32 forward with a bf16 copy has no %dx%d tile", BM, BN);
+      }
+    }
+  }
   // one-k-tile bf16 FWD launches on the 4-wave 128x128 / 256x64 tiles: the one-stage form
   // (bit-identical to the two-stage form, which it replaced in round 4).  56x56 64->64: 0.427 ->
   // 0.378 ms; the DGRAD view measured slower in it (its 233-VGPR LDS-staged epilogue caps the

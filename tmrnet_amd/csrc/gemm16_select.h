@@ -178,4 +178,22 @@ extern template int launch16_inf16<64, 64, 2, 2>(const GemmArgs&, bool, dim3, hi
 extern template int launch16_inf16<256, 256, 2, 4>(const GemmArgs&, bool, dim3, hipStream_t);
 extern template int launch16_inf16<256, 256, 4, 4>(const GemmArgs&, bool, dim3, hipStream_t);
 
+// the fp32 inference forwards that also write a bf16 copy of their output
+// (tmr_conv2d_fwd_fused_dual: GemmArgs::Cbf, epilogue_batched's INF16 = 2 form), in the launch
+// form (two-stage, TAPV) the same tile's other fp32 forwards take.  Kernels of their own
+// (gemm16_fwd_dual32.hip), for the tile configs pick_cfg16 gives an fp32 forward; a forced config
+// outside them (TMR_GEMM16_CFG 0 / 4) is refused.
+template <int BM, int BN, int WM, int WN>
+constexpr bool dual32_cfg() {
+  return !((BM == 256 && BN == 256 && WM * WN == 8) || (BM == 64 && BN == 256));
+}
+template <int BM, int BN, int WM, int WN>
+int launch16_dual32(const GemmArgs& a, bool tapv, dim3 grid, hipStream_t st);
+extern template int launch16_dual32<256, 128, 4, 2>(const GemmArgs&, bool, dim3, hipStream_t);
+extern template int launch16_dual32<128, 128, 2, 2>(const GemmArgs&, bool, dim3, hipStream_t);
+extern template int launch16_dual32<256, 64, 4, 1>(const GemmArgs&, bool, dim3, hipStream_t);
+extern template int launch16_dual32<128, 128, 4, 2>(const GemmArgs&, bool, dim3, hipStream_t);
+extern template int launch16_dual32<64, 64, 2, 2>(const GemmArgs&, bool, dim3, hipStream_t);
+extern template int launch16_dual32<256, 256, 4, 4>(const GemmArgs&, bool, dim3, hipStream_t);
+
 }  // namespace tmrg

@@ -287,6 +287,58 @@ TMR_API int tmr_conv2d_fwd_fused(const tmr_conv_desc* d, const float* x, const f
   });
 }
 
+// The fp32 fused forward that also writes the bf16 copy z16 of its output (GemmArgs::Cbf; the
+// LDS-DMA engine's kernels of gemm16_fwd_dual32.hip).  Every slice is checked before the first one
+// is launched: a refusal launches nothing, and there is no two-pass fall-back.
+TMR_API int tmr_conv2d_fwd_fused_dual(const tmr_conv_desc* d, const float* x, const float* w_krsc,
+                                      const float* scale, const float* shift,
+                                      const float* residual, float* z, void* z16, int relu,
+                                      hipStream_t stream) {
+  TMR_CHECK_ARG(d, "tmr_conv2d_fwd_fused_dual: null descriptor");
+  TMR_CHECK_ARG(x && w_krsc && z, "tmr_conv2d_fwd_fused_dual: null x / w / z");
+  TMR_CHECK_ARG(scale && shift, "tmr_conv2d_fwd_fused_dual: null BatchNorm scale/shift");
+  TMR_CHECK_ARG(d->math == TMR_MATH_F32 && (d->io & ~(TMR_IO_ENGINE | TMR_IO_CLASSES | TMR_IO_TILES)) == 0,
+                "tmr_conv2d_fwd_fused_dual: fp32 operands in fp32 math only (math %d, io %d)",
+                d->math, d->io);
+  TMR_CHECK_ARG(ngroups(d) == 1, "tmr_conv2d_fwd_fused_dual: no grouped conv (groups %d)", d->groups);
+  TMR_CHECK_ARG(d->n > 0 && d->k > 0 && d->ho > 0 && d->wo > 0, "tmr_conv2d_fwd_fused_dual: empty output");
+  TMR_CHECK_ARG(yld_of(d) == d->k, "tmr_conv2d_fwd_fused_dual: z and z16 must be dense (y_ld == k)");
+  TMR_CHECK_ARG(d->k % 2 == 0, "tmr_conv2d_fwd_fused_dual: output channels %d must be even "
+                "(z16 is stored as dwords of two columns)", d->k);
+  TMR_CHECK_ARG(z16, "tmr_conv2d_fwd_fused_dual: null z16");
+  TMR_CHECK_ARG(!residual || residual != z, "tmr_conv2d_fwd_fused_dual: residual must not alias z");
+  const size_t elems = (size_t)d->n * d->ho * d->wo * d->k;
+  const auto apart = [&](const void* p) {   // the fp32 tensor at p against z16's bytes
+    return !p || (const char*)p + elems * 4 <= (const char*)z16 ||
+           (const char*)z16 + elems * 2 <= (const char*)p;
+  };
+  TMR_CHECK_ARG(apart(z) && apart(residual), "tmr_conv2d_fwd_fused_dual: z16 overlaps z or the residual");
+  TMR_CHECK_ARG(aligned16(z16) && aligned16(z),
+                "tmr_conv2d_fwd_fused_dual: z and z16 must be 16-B aligned (whole-line stores)");
+  for (int pass = 0; pass < 2; ++pass) {   // 0: check every slice, 1: launch
+    const int rc = for_slices(d, [&](const tmr_conv_desc& c, int g, int f0) -> int {
+      GemmArgs a;
+      bool al;
+      const int rc = conv_fwd_args(&c, adv(x, x_off(c, g, f0), 4), w_krsc, shift,
+                                   adv(z, y_off(c, g, f0), 4), 0.f, a, al);
+      if (rc) return rc;
+      a.scale = scale;
+      a.res = adv(residual, y_off(c, g, f0), 4);
+      a.relu = relu;
+      a.Cbf = adv(z16, y_off(c, g, f0), 2);
+      TMR_CHECK_ARG(use16(a, MODE_FWD),
+                    "tmr_conv2d_fwd_fused_dual: not a shape of the fp32 LDS-DMA forward (16-B "
+                    "aligned x / w, stored channels and row strides multiples of 4; c %d, x_ld %d, "
+                    "r %d, s %d) -- run tmr_conv2d_fwd_fused and a cast instead",
+                    c.c, xld_of(&c), c.r, c.s);
+      TMR_CHECK_ARG(((uintptr_t)a.Cbf & 3) == 0, "tmr_conv2d_fwd_fused_dual: z16 chunk not 4-B aligned");
+      return pass == 0 ? 0 : launch_gemm<MODE_FWD>(a, al, 1, stream);
+    });
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 TMR_API int tmr_conv2d_fwd_stats_parts(const tmr_conv_desc* d) {
   if (!d || d->n <= 0) {
     tmr_set_error("tmr_conv2d_fwd_stats_parts: null or empty descriptor");

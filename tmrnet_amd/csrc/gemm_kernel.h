@@ -120,6 +120,10 @@ struct GemmArgs {
   // DGRAD: keep the one-tile-per-workgroup launch where the wave-specialised persistent dgrad
   // (gemm16_ws.h) would serve the shape (TMR_IO_TILES; tests)
   int io_tiles;
+  // fp32 FWD inference epilogue (tmr_conv2d_fwd_fused_dual): besides the fp32 C, the same values
+  // rounded once (RNE) into a dense bf16 tensor laid out like C (element offsets as C's, half the
+  // bytes).  Kernels of their own (epilogue_batched INF16 = 2, gemm16_fwd_dual32.hip).
+  void* Cbf;
 };
 
 __device__ __forceinline__ float bf16_rne(float v) { return (float)(__bf16)v; }
@@ -491,6 +495,67 @@ __device__ __forceinline__ void epilogue_batched(const GemmArgs& a, floatx16 (&a
     if (a.relu) v = fmaxf(v, 0.f);
     return v;
   };
+  // INF16 = 2 (gemm16_fwd_dual32.hip): the fp32 inference epilogue -- fp32 residual in, fp32 C
+  // out, inf_val's arithmetic -- and the same values rounded once (RNE) into the bf16 copy
+  // a.Cbf, stored in the whole-line form (TN even) or the pair form (TN odd) of the bf16 outputs
+  // above: same lanes, same dwords, against a descriptor of half C's extent.
+  if constexpr (INF16 == 2) {
+    const __amdgpu_buffer_rsrc_t rH = make_rsrc(reinterpret_cast<const float*>(a.Cbf), a.Cbytes >> 1);
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int r0 = 0; r0 < 16; r0 += ER) {
+        uint32_t rob[ER], off[ER][TN];
+        float v[ER][TN];
+#pragma unroll
+        for (int r = 0; r < ER; ++r) {
+          rob[r] = row_off(i, r0 + r);
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            off[r][j] = eoff(rob[r], j);
+            v[r][j] = has_res ? bld1(rR, off[r][j]) : 0.f;
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < ER; ++r)
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            v[r][j] = inf_val(acc[i][j][r0 + r], j, v[r][j]);
+            st1(v[r][j], off[r][j]);
+          }
+        if constexpr (TN % 2 == 0) {
+#pragma unroll
+          for (int r = 0; r < ER; ++r)
+#pragma unroll
+            for (int jp = 0; jp < TN / 2; ++jp) {
+              const float mine = odd ? v[r][2 * jp + 1] : v[r][2 * jp];
+              const float send = odd ? v[r][2 * jp] : v[r][2 * jp + 1];
+              const uint32_t got = swap1((uint32_t)bf16_bits(send));
+              const uint32_t mb = (uint32_t)bf16_bits(mine);
+              const uint32_t w = odd ? ((mb << 16) | got) : ((got << 16) | mb);
+              const int scol = odd ? col0 - 1 + 32 * (2 * jp + 1) : col0 + 64 * jp;
+              const uint32_t o =
+                  (rob[r] >= OOB || scol >= a.N) ? OOB : (rob[r] >> 1) + (uint32_t)scol * 2u;
+              __builtin_amdgcn_raw_buffer_store_b32(w, rH, o, 0, 0);
+            }
+        } else {
+#pragma unroll
+          for (int rp = 0; rp < ER / 2; ++rp)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+              const float vr = v[2 * rp][j], vr1 = v[2 * rp + 1][j];
+              const uint32_t mine = odd ? (uint32_t)bf16_bits(vr1) : (uint32_t)bf16_bits(vr);
+              const uint32_t other = odd ? (uint32_t)bf16_bits(vr) : (uint32_t)bf16_bits(vr1);
+              const uint32_t got = swap1(other);   // the neighbour's value of my pair's row
+              const uint32_t w = odd ? ((mine << 16) | got) : ((got << 16) | mine);
+              __builtin_amdgcn_raw_buffer_store_b32(w, rH, poff(off[2 * rp][j], off[2 * rp + 1][j]),
+                                                    0, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    return;
+  }
   if constexpr (INF16 != 0) {
     constexpr int JP = TN / 2 > 0 ? TN / 2 : 1;
     if (c16w) {

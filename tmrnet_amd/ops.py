@@ -271,6 +271,44 @@ def conv_fwd_fused(x, w_krsc, stride, pad, scale, shift, residual=None, relu=Tru
     return out
 
 
+def conv_fwd_fused_dual(x, w_krsc, stride, pad, scale, shift, residual=None, relu=True, c_real=None):
+    """conv_fwd_fused on fp32 operands in fp32 math that also writes a bf16 copy of its output
+    (tmr_conv2d_fwd_fused_dual) -> (z, z16): z = [relu](conv(x, w_krsc) * scale + shift + residual)
+    as conv_fwd_fused stores it, z16 = bf16(z) rounded once (RNE).  The residual is fp32.  The
+    LDS-DMA engine only (conv_tile(..., "fwd") plans engine 2): anything else is refused, here
+    before any library call where the operands show it."""
+    for t, name in ((x, "x"), (w_krsc, "w"), (scale, "scale"), (shift, "shift")):
+        if t.dtype != f32:
+            raise RuntimeError("conv_fwd_fused_dual: fp32 operands in fp32 math only, %s is %s"
+                               % (name, t.dtype))
+    _req(x, "x"); _req(w_krsc, "w"); _req(scale, "scale"); _req(shift, "shift")
+    n, h, w, c = x.shape
+    k, r, s, c2 = w_krsc.shape
+    if c != c2:
+        raise RuntimeError("conv_fwd_fused_dual: no grouped conv (x has %d channels, w %d)" % (c, c2))
+    if k % 2:
+        raise RuntimeError("conv_fwd_fused_dual: output channels %d must be even" % k)
+    if scale.numel() != k or shift.numel() != k:
+        raise RuntimeError("conv_fwd_fused_dual: scale / shift must have %d elements" % k)
+    d = conv_desc(n, h, w, c, k, r, s, stride, pad, math="fp32")
+    z = _empty((n, d.ho, d.wo, k), x)
+    z16 = _empty((n, d.ho, d.wo, k), x, dtype=BF16)
+    if residual is not None:
+        if residual.dtype != f32:
+            raise RuntimeError("conv_fwd_fused_dual: the residual stays fp32, got %s" % residual.dtype)
+        _req(residual, "residual")
+        if residual.shape != z.shape:
+            raise RuntimeError("conv_fwd_fused_dual: residual %s != output %s"
+                               % (tuple(residual.shape), tuple(z.shape)))
+    ysz = n * d.ho * d.wo * k
+    with _prof("conv_fwd", 2.0 * ysz * r * s * (c_real or c), (n, h, w, c, k, r, stride),
+               4 * (n * h * w * c + k * r * s * c + ysz * (2 if residual is not None else 1))
+               + 2 * ysz):
+        call("tmr_conv2d_fwd_fused_dual", ctypes.byref(d), x, w_krsc, scale, shift, residual, z,
+             z16, int(relu), stream_ptr())
+    return z, z16
+
+
 def conv_fwd_bnstats(x, w_krsc, stride, pad, c_real=None, pad_w=None, math="fp32", y16=False,
                      groups=1):
     """conv_fwd whose epilogue also emits BatchNorm partials; returns (y, stats, nparts).
@@ -332,13 +370,14 @@ def conv_dgrad(dy, w_krsc, in_hw, stride, pad, out=None, beta=0.0, pad_w=None, m
 
 def conv_dgrad_bnbwd(dy, w_krsc, in_hw, stride, pad, y, mean, mask, z=None, scale=None,
                      shift=None, out=None, beta=0.0, math="fp32", wt=False, groups=1,
-                     g16=False, old=None):
+                     g16=False, old=None, engine=False):
     """conv_dgrad whose epilogue masks dx by the previous unit's ReLU (mask 1: z > 0, 2:
     y*scale+shift > 0) and emits that unit's BN-backward partials -> (dx_masked, parts, nparts).
     wt: as conv_dgrad.  y / z may be bf16 (the bf16-activation step, TMR_IO_BN_BF16).
     g16: dx_masked stored bf16, the partials those of the rounded values (TMR_IO_G16); with beta
     the old dx is `out` itself (bf16, in place) or `old` (fp32 or bf16; tmr_conv2d_dgrad_bnbwd_acc,
-    a new bf16 dx is returned)."""
+    a new bf16 dx is returned).  engine: the implicit-GEMM engine also where a direct kernel serves
+    the operands (TMR_IO_ENGINE)."""
     if old is not None:
         if not (g16 and beta != 0.0 and out is None and groups == 1):
             raise RuntimeError("conv_dgrad_bnbwd: a separate old dx needs g16, beta, no out / "
@@ -359,7 +398,7 @@ def conv_dgrad_bnbwd(dy, w_krsc, in_hw, stride, pad, y, mean, mask, z=None, scal
     h, w = in_hw
     d = conv_desc(n, h, w, c, k, r, s, stride, pad, math=math,
                   io=_io(None, w_krsc, dy, wt) | (IO_BN if y.dtype == BF16 else 0)
-                  | (IO_G16 if g16 else 0), groups=groups)
+                  | (IO_G16 if g16 else 0) | (IO_ENGINE if engine else 0), groups=groups)
     assert (d.ho, d.wo) == (ho, wo), ((d.ho, d.wo), (ho, wo))
     if out is None:
         out = _empty((n, h, w, c), dy, dtype=BF16 if g16 else f32)
@@ -392,6 +431,31 @@ def conv_dgrad_bnbwd(dy, w_krsc, in_hw, stride, pad, y, mean, mask, z=None, scal
                  scale, shift, mean, int(mask), parts, ctypes.c_size_t(parts.numel() * 4),
                  stream_ptr())
     return out, parts, nparts
+
+
+_IDENTITY_COEFS = {}   # (device, channels) -> (ones, zeros): conv_dgrad_relu's coefficient tables
+
+
+def conv_dgrad_relu(dy, w, in_hw, stride, pad, z, out=None, beta=0.0, math="fp32", wt=False,
+                    g16=False):
+    """conv_dgrad whose epilogue masks dx by a stored ReLU output: dx = z > 0 ? dx : 0 -> dx.
+    z (dx's shape; fp32, or bf16 with bf16 math) is the output the forward kept.  This is
+    tmr_conv2d_dgrad_bnbwd with y := z, mask 2 on identity coefficients (scale 1, shift 0: fmaf(z, 1,
+    0) > 0 is z > 0 exactly) and a zero mean; the partial sums it returns are discarded.  out /
+    beta / math / wt / g16 as conv_dgrad_bnbwd.  A bf16 z keeps the dgrad on the implicit-GEMM
+    engine (the direct bf16 3x3 dgrad would take layer1's conv2 otherwise): the summation order,
+    and so every bit of dx, is that of the same dgrad beside an fp32 mask source."""
+    c = z.shape[-1]
+    key = (z.device, c)
+    coefs = _IDENTITY_COEFS.get(key)
+    if coefs is None:
+        coefs = _IDENTITY_COEFS[key] = (torch.ones(c, dtype=f32, device=z.device),
+                                        torch.zeros(c, dtype=f32, device=z.device))
+    ones, zeros_ = coefs
+    dx, _, _ = conv_dgrad_bnbwd(dy, w, in_hw, stride, pad, z, zeros_, 2, scale=ones, shift=zeros_,
+                                out=out, beta=beta, math=math, wt=wt, g16=g16,
+                                engine=z.dtype == BF16)
+    return dx
 
 
 def bn_bwd_maxpool(dyp, am, y, scale, shift, mean, inv, gamma, bf16=False):
@@ -1136,6 +1200,20 @@ def _frozen_mask(mask, z, bits, y):
     return None
 
 
+def _frozen_y(g, y, mask, want_sums, name):
+    """g and y checked; y may be None only where the kernel reads none: no sums and no mask 2 (a
+    unit whose forward stored no conv output, freeze_bn(forward="fused"))."""
+    if y is None and (want_sums or mask == 2):
+        raise RuntimeError("%s: y=None needs want_sums=False and a mask other than 2" % name)
+    _req(g, "g")
+    if y is None:
+        return None
+    _req(y, "y")
+    if g.shape != y.shape:
+        raise RuntimeError("%s: g shape %s != y %s" % (name, tuple(g.shape), tuple(y.shape)))
+    return y
+
+
 def _frozen_out(like, want, bf16):
     return torch.empty_like(like, dtype=BF16 if bf16 else f32) if want else None
 
@@ -1147,13 +1225,11 @@ def bn_frozen_bwd(g, y, scale, shift, mean, mask, z=None, bits=None, want_dy=Tru
     dres_inplace: the masked gradient overwrites g (the identity branch's gradient).
     want_dy=False: no dy (the caller folds the scale into its conv operands); want_sums=False:
     no partials (affine=False), parts is None.  bn_frozen_finalize turns parts into dgamma, dbeta."""
-    _req(g, "g"); _req(y, "y")
-    if g.shape != y.shape:
-        raise RuntimeError("bn_frozen_bwd: g shape %s != y %s" % (tuple(g.shape), tuple(y.shape)))
-    c = y.shape[-1]
-    rows = y.numel() // c
-    zm = _frozen_mask(mask, z, bits, y)
-    dy = torch.empty_like(y) if want_dy else None
+    y = _frozen_y(g, y, mask, want_sums, "bn_frozen_bwd")
+    c = g.shape[-1]
+    rows = g.numel() // c
+    zm = _frozen_mask(mask, z, bits, g)
+    dy = torch.empty_like(g) if want_dy else None
     parts, nparts = None, 0
     if want_sums:
         nparts = query("tmr_bn_frozen_bwd_parts", rows, c)
@@ -1171,14 +1247,12 @@ def bn_frozen_bwd_x(g, y, scale, shift, mean, mask, z=None, bits=None, want_dy=T
     g itself as bf16 (tmr_bn_frozen_bwd_x) -> (dy, g16, parts, nparts).  dres and the partials are
     bn_frozen_bwd's bit for bit.  want_dy=False, want_g16=True, mask 0: the cast pass over a block
     output's gradient (with the sums of (g, y) if wanted)."""
-    _req(g, "g"); _req(y, "y")
-    if g.shape != y.shape:
-        raise RuntimeError("bn_frozen_bwd_x: g shape %s != y %s" % (tuple(g.shape), tuple(y.shape)))
-    c = y.shape[-1]
-    rows = y.numel() // c
-    zm = _frozen_mask(mask, z, bits, y)
-    dy = _frozen_out(y, want_dy, dy16)
-    g16 = _frozen_out(y, want_g16, True)
+    y = _frozen_y(g, y, mask, want_sums, "bn_frozen_bwd_x")
+    c = g.shape[-1]
+    rows = g.numel() // c
+    zm = _frozen_mask(mask, z, bits, g)
+    dy = _frozen_out(g, want_dy, dy16)
+    g16 = _frozen_out(g, want_g16, True)
     parts, nparts = None, 0
     if want_sums:
         nparts = query("tmr_bn_frozen_bwd_parts", rows, c)

@@ -19,7 +19,8 @@ The other step kinds, each specified by the block comment named:
   * precision "bf16": bf16 conv operands and activations (BF16_STORE, FULL16, ACT16, G16, R16);
   * precision "bf16-bwd": the fp32 forward, bf16 operands in the backward convs only (BWD16);
   * frozen BatchNorm (freeze_bn): a train step on the running statistics ("frozen BatchNorm");
-    with backward="bf16" its backward convs in bf16 math (_frozen16);
+    with backward="bf16" its backward convs in bf16 math (_frozen16); with forward="fused" BN
+    folded into the conv forward, no conv output stored (_frozen_fused);
   * infer16: eval mode with bf16 activations, opt-in (_infer16, TrunkFn._forward_eval).
 How the units of a step are put together: "the conv+BN unit" below, DESIGN.md §29.
 """
@@ -247,9 +248,10 @@ class Unit:
                    # stem's NHWC4 fp32 input)
         "wk",      # KRSC weights (_krsc)
         "wt",      # the dgrad's transposed CRSK copy (_dgrad_weights); None: the dgrad reads wk
-        "y",       # the conv output
+        "y",       # the conv output (None: the fused frozen step never stores it)
         "z",       # the BN output of a residual unit (the ReLU mask); None without a residual,
-                   # for a deferred unit, and in the bf16-bwd step once the bits replace it
+                   # for a deferred unit, and in the bf16-bwd step once the bits replace it.  The
+                   # fused frozen step: every ReLU unit's own output (fp32 z, or its bf16 copy)
         "zbits",   # the ReLU mask as bits: fp32 block outputs of a recorded step, else None
         "scale", "shift", "mean", "inv",   # BN coefficients and statistics (frozen: running)
         "stride", "pad", "relu",
@@ -363,6 +365,35 @@ class _TrainUnits:
         inside the maxpool, ResNeSt's bn0 inside the split attention)."""
         branch, _, _, rec = self._run(x, conv, bn, stride, pad, relu, True, **kw)
         return branch, rec
+
+    def fused(self, x, conv, bn, stride, pad, relu, residual=None, x16=None, fold=True,
+              copy16=True):
+        """A non-stem unit of the frozen step with BN folded into the conv forward
+        (freeze_bn(forward="fused")): ONE launch z = [relu](fmaf(acc, scale, shift) [+ residual]),
+        no y stored -> (z, z16, record).  With a bf16 backward (``bwd16``) and ``copy16`` the launch
+        is the dual form, which also writes z16 = bf16(z), the next conv's wgrad operand.  The
+        record's ReLU-mask source is the unit's own output (z16 where it exists, else z) -- the
+        tensor the next unit keeps as its x; y and zbits are None."""
+        w = conv.weight
+        c = w.shape[1]
+        math, bwd16 = self.math, self.bwd16
+        wk = _krsc(w, x.shape[3], False)
+        scale, shift, inv = self.frozen[bn]
+        z16 = None
+        if bwd16 and copy16:
+            z, z16 = ops.conv_fwd_fused_dual(x, wk, stride, pad, scale, shift, residual, relu,
+                                             c_real=c)
+        else:
+            z = ops.conv_fwd_fused(x, wk, stride, pad, scale, shift, residual, relu, c_real=c,
+                                   math=math)
+        zm = (z16 if z16 is not None else z) if relu else None
+        rec = Unit(conv=conv, bn=bn, x=x16 if (bwd16 and x16 is not None) else x, wk=wk,
+                   wt=_dgrad_weights(w, x, math, 1, bwd16, scale if fold else None),
+                   y=None, z=zm, zbits=None, scale=scale, shift=shift, mean=bn.running_mean,
+                   inv=inv, stride=stride, pad=pad, relu=relu, c_real=c,
+                   math="bf16" if bwd16 else math, groups=1, res=residual is not None,
+                   dy16=bwd16, fold=bool(fold))
+        return z, z16, rec
 
     def _run(self, x, conv, bn, stride, pad, relu, defer, residual=None, branch=None, dual=False,
              groups=1, x16=None, fold=True):
@@ -622,6 +653,20 @@ def _frozen16(share):
                 and share.precision in ("fp32", BWD16))
 
 
+# freeze_bn(affine=False, forward="fused"), DESIGN.md §32: the frozen step with BatchNorm folded
+# into the conv forward.  Every non-stem unit is ONE launch z = [relu](fmaf(acc, scale, shift)
+# [+ residual]) (ops.conv_fwd_fused; with a bf16 backward ops.conv_fwd_fused_dual, which also
+# writes z16 = bf16(z), rounded once) -- the values of conv_fwd + bn_apply bit for bit, but y is
+# never stored and no apply pass runs.  A unit's ReLU mask is its own stored output (z > 0 is the
+# predicate fmaf(y, scale, shift) > 0), the tensor the next unit keeps as x anyway; with a bf16
+# backward the mask is z16 > 0, which differs from z > 0 only where a positive fp32 z rounds to
+# bf16 zero (below the bf16 subnormal range).  No BN gradient exists (affine=False), so nothing in
+# the backward needs y.  The stem keeps conv_fwd + maxpool_fwd_bn[_dual] and its y.
+def _frozen_fused(share):
+    return bool(getattr(share, "bn_frozen", False) and share.training
+                and getattr(share, "bn_frozen_fwd", None) == "fused")
+
+
 def _frozen_coefs(share):
     """{bn: (scale, shift, inv)} of every BN of the share, computed by ONE launch from the current
     weight / bias / running statistics (ops.bn_frozen_params)."""
@@ -666,6 +711,37 @@ def _frozen_dy_bwd(rec, dy, grads, **conv):
     return _conv_bwd(rec, dy, grads, **conv)
 
 
+def _fused_unit_bwd(rec, gy, grads, f16, prev=None, dx_out=None, dx_beta=0.0):
+    """wgrad and dgrad of a unit of the fused frozen step (no y anywhere, no BN gradient) -> dx.
+    gy: the unit's masked gradient g for a folded unit (dW's rows take scale[k], the dgrad reads the
+    pre-scaled CRSK weights), or its real dy = g*scale for the last block's bn3.  prev: the unit
+    whose output gradient this dgrad produces -- masked by that unit's stored output
+    (ops.conv_dgrad_relu), stored bf16 under ``f16`` unless it is a block output (the residual
+    stream's gradient stays fp32).  A dgrad that refuses the operand mix raises with its shape."""
+    r, s = rec.conv.weight.shape[2:]
+    grads[rec.conv.weight] = ops.conv_wgrad(rec.x, gy, r, s, rec.stride, rec.pad,
+                                            c_real=rec.c_real, math=rec.math)
+    if rec.fold:
+        ops.scale_rows(grads[rec.conv.weight], rec.scale)
+    hw = (rec.x.shape[1], rec.x.shape[2])
+    wt = rec.wt is not None
+    wdg = rec.wt if wt else rec.wk
+    if prev is None:
+        return ops.conv_dgrad(gy, wdg, hw, rec.stride, rec.pad, out=dx_out, beta=dx_beta,
+                              math=rec.math, wt=wt)
+    if not prev.relu or prev.z is None:
+        raise RuntimeError("frozen BN, fused forward: the masked dgrad needs the previous unit's "
+                           "stored ReLU output")
+    try:
+        return ops.conv_dgrad_relu(gy, wdg, hw, rec.stride, rec.pad, prev.z, out=dx_out,
+                                   beta=dx_beta, math=rec.math, wt=wt, g16=f16 and not prev.res)
+    except RuntimeError as e:
+        raise RuntimeError("frozen BN, fused forward: the masked dgrad of dy %s, weight %s, stride "
+                           "%d refused its operands (mask source %s, beta %g): %s"
+                           % (tuple(gy.shape), tuple(rec.conv.weight.shape), rec.stride,
+                              prev.z.dtype, dx_beta, e))
+
+
 class TrunkFn(torch.autograd.Function):
     """Whole ResNet-50 trunk as one autograd node: x NHWC4 (F,224,224,4) -> (F,2048)."""
 
@@ -679,6 +755,8 @@ class TrunkFn(torch.autograd.Function):
         key = ("resnet50", share.training, bool(keep), share.precision, _infer16(share))
         if fz is not None:
             key += ("frozen16" if _frozen16(share) else "frozen",)
+            if keep and _frozen_fused(share):
+                key += ("fused",)
         with ops.layout_session(share, key):
             return TrunkFn._forward(ctx, x4, share, keep, params, fz)
 
@@ -690,6 +768,7 @@ class TrunkFn(torch.autograd.Function):
         ctx.keep = keep
         ctx.frozen = fz is not None
         ctx.frozen16 = f16z = bool(fz is not None and keep and _frozen16(share))
+        ctx.frozen_fused = False
         if not share.training:
             return TrunkFn._forward_eval(x4, conv1, bn1, layers, mt, _infer16(share))
         # the BWD16 step: the fp32 forward plus the bf16 copies its bf16-math backward reads
@@ -699,6 +778,13 @@ class TrunkFn(torch.autograd.Function):
         a16 = _act16(mt)                    # every activation bf16: no fp32 copies
         f16 = _full16(mt) and not a16
         st = _TrainUnits(mt, keep, bwd16=bw, frozen=fz)
+        # freeze_bn(forward="fused"): a recorded frozen step whose non-stem units never store y
+        # (without a backward to record the forward is the unfused one: the same bits)
+        ctx.frozen_fused = fu = bool(fz is not None and keep and _frozen_fused(share))
+        if fu and any(_bn_wants_grad(bn) for bn in _share_bns(share)):
+            raise RuntimeError("frozen BN, forward=\"fused\": a BatchNorm weight or bias requires "
+                               "grad, but dgamma needs the conv output, which this step does not "
+                               "store: call tmrnet_amd.freeze_bn(..., affine=False) again")
         # bf16 activations: the stem reads an NHWC8 bf16 copy of its input (8-channel pieces: the
         # LDS-DMA engine; exact, the bf16 math rounds x anyway)
         xs = ops.nhwc4_to_bf16x8(x4) if (a16 and ops.engine_forced()) else x4
@@ -717,6 +803,25 @@ class TrunkFn(torch.autograd.Function):
         last = layers[-1][-1]
         for layer in layers:
             for blk in layer:
+                if fu:
+                    # BN folded into the conv forward: one launch per unit, no y, no apply pass;
+                    # the downsample branch is a fused unit without ReLU whose fp32 output (no
+                    # conv operand: no bf16 copy) is conv3's residual
+                    fold = blk is not last
+                    z1, z1h, r1 = st.fused(hx, blk.conv1, blk.bn1, 1, 0, True, x16=h16)
+                    z2, z2h, r2 = st.fused(z1, blk.conv2, blk.bn2, blk.stride, 1, True, x16=z1h)
+                    rd, idn = None, h
+                    if blk.downsample is not None:
+                        idn, _, rd = st.fused(hx, blk.downsample[0], blk.downsample[1], blk.stride,
+                                              0, False, x16=h16, fold=fold, copy16=False)
+                    # (the last block's output is no conv operand: fp32 only, which is also the
+                    # mask-1 source of its bn3's single pass)
+                    h, h16, r3 = st.fused(z2, blk.conv3, blk.bn3, 1, 0, True, residual=idn,
+                                          x16=z2h, fold=fold, copy16=fold)
+                    hx = h
+                    del z1, z2, idn   # (bf16 backward: the records hold the bf16 copies only)
+                    blocks.append((blk, [r1, r2, rd, r3]))
+                    continue
                 z1, z1h, r1 = st.unit(hx, blk.conv1, blk.bn1, 1, 0, True, x16=h16)
                 z2, z2h, r2 = st.unit(z1, blk.conv2, blk.bn2, blk.stride, 1, True, x16=z1h)
                 # the frozen step: every unit but the last block's bn3 / downsample BN (whose g
@@ -784,6 +889,8 @@ class TrunkFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dfeat):
+        if ctx.frozen and ctx.frozen_fused:
+            return TrunkFn._backward_frozen_fused(ctx, dfeat)
         if ctx.frozen:
             return TrunkFn._backward_frozen(ctx, dfeat)
         grads = {}
@@ -929,6 +1036,65 @@ class TrunkFn(torch.autograd.Function):
         return _backward_tail(ctx, grads)
 
 
+    @staticmethod
+    def _backward_frozen_fused(ctx, dfeat):
+        """The backward of the frozen step with BN folded into the conv forward ("_frozen_fused"):
+        _backward_frozen's affine=False walk without a y anywhere.  No BN gradient and no
+        sums-only pass; every dgrad that produces a previous unit's g masks by that unit's stored
+        output (_fused_unit_bwd); the last block's bn3 (g unmasked from the avgpool) takes one pass
+        of tmr_bn_frozen_bwd[_x] with mask 1 on its stored fp32 output, no sums, dres in place.
+        The stem is the unfused step's.  ctx.frozen16: the same operands, roundings and cast
+        passes as _backward_frozen's bf16 walk."""
+        grads = {}
+        f16 = ctx.frozen16
+        g = _backward_head(ctx, dfeat)   # grad at the last block output
+        masked = False     # g came masked from the next block's conv1 dgrad
+        for blk, brec, prev3 in _backward_blocks(ctx, grads, lambda recs: recs[-1]):
+            r1, r2, rd, r3 = brec   # (rd: None without a downsample)
+            if not masked:
+                if rd is not None:
+                    raise RuntimeError("frozen BN, fused forward: a last block with a downsample "
+                                       "branch has no single-pass form")
+                if f16:
+                    dy3, _, _, _ = ops.bn_frozen_bwd_x(g, None, r3.scale, r3.shift, r3.mean,
+                                                       mask=1, z=r3.z, dres_inplace=True,
+                                                       want_sums=False, dy16=True)
+                else:
+                    dy3, _, _ = ops.bn_frozen_bwd(g, None, r3.scale, r3.shift, r3.mean, mask=1,
+                                                  z=r3.z, dres_inplace=True, want_sums=False)
+                if r3.fold:
+                    raise RuntimeError("frozen BN: a real dy meets pre-scaled dgrad weights")
+                dz2 = _fused_unit_bwd(r3, dy3, grads, f16, prev=r2)
+                del dy3
+                gop = None
+            else:
+                gop = g    # the folded units' conv operand: g, or (f16) its bf16 copy
+                if f16:    # one cast pass per block output's fp32 g
+                    _, gop, _, _ = ops.bn_frozen_bwd_x(g, None, r3.scale, r3.shift, r3.mean,
+                                                       mask=0, want_dy=False, want_sums=False,
+                                                       want_g16=True)
+                dz2 = _fused_unit_bwd(r3, gop, grads, f16, prev=r2)
+            dres = g   # masked: the identity branch's gradient
+            dz1 = _fused_unit_bwd(r2, dz2, grads, f16, prev=r1)
+            del dz2
+            if rd is not None:
+                dres = _fused_unit_bwd(rd, gop, grads, f16)
+            del gop
+            g = _fused_unit_bwd(r1, dz1, grads, f16, prev=prev3, dx_out=dres, dx_beta=1.0)
+            masked = True
+            del dz1, brec, dres
+        am, _ = ctx.pool
+        st = ctx.stem[0]
+        if f16:
+            dy0, _, _ = ops.bn_frozen_bwd_maxpool_x(g, am, st.y, st.scale, st.shift, st.mean,
+                                                    want_sums=False, dy16=True)
+        else:
+            dy0, _, _ = ops.bn_frozen_bwd_maxpool(g, am, st.y, st.scale, st.shift, st.mean,
+                                                  want_sums=False)
+        _frozen_dy_bwd(st, dy0, grads, need_dx=False)
+        return _backward_tail(ctx, grads)
+
+
 _CHILD_NAMES = ("conv1", "bn1", "relu", "maxpool", "layer1", "layer2", "layer3", "layer4",
                 "avgpool")
 
@@ -955,6 +1121,7 @@ class ResNet50Share(nn.Sequential):
         # train(mode) says, and a train-mode step runs on the running statistics
         self.bn_frozen = False
         self.bn_frozen_bwd = None   # "bf16": the frozen step's backward convs in bf16 math
+        self.bn_frozen_fwd = None   # "fused": BN folded into the conv forward, no y stored
         mods = (nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False), nn.BatchNorm2d(64),
                 nn.ReLU(inplace=True), nn.MaxPool2d(3, stride=2, padding=1),
                 _make_layer(64, 64, 3, 1), _make_layer(256, 128, 4, 2),
@@ -1014,7 +1181,7 @@ def _share_of(model):
                     "one as .share or .res, got %s" % type(model).__name__)
 
 
-def freeze_bn(model_or_share, affine=True, backward=None):
+def freeze_bn(model_or_share, affine=True, backward=None, forward=None):
     """Freeze the trunk's BatchNorm: every BatchNorm2d of the share goes to eval mode and stays
     there through train() / eval() (share.bn_frozen = True); a train-mode step then normalises
     with the running statistics, writes none of them, and back-propagates dy = g*scale.
@@ -1023,11 +1190,19 @@ def freeze_bn(model_or_share, affine=True, backward=None):
     backward="bf16" (share.bn_frozen_bwd): the same fp32 forward -- logits and loss bit for bit --
     with every trunk conv's dgrad and wgrad in bf16 math on fp32 accumulation, the backward of
     precision "bf16-bwd" under frozen BatchNorm; ResNet-50 shares of precision "fp32" or
-    "bf16-bwd".  backward=None or "fp32": the fp32 backward.  Call it after load_checkpoint and
-    before the optimizer is built.  Returns its argument."""
+    "bf16-bwd".  backward=None or "fp32": the fp32 backward.
+    forward="fused" (share.bn_frozen_fwd; needs affine=False, combines with every backward): each
+    non-stem conv + BN (+ residual) (+ ReLU) unit is one launch that never stores the conv output
+    and runs no BatchNorm apply pass; logits, loss and every gradient are those of the unfused
+    affine=False step bit for bit (with backward="bf16" the ReLU masks are read from the bf16
+    copies: they differ only where a positive output rounds to bf16 zero), with less memory.
+    forward=None or "apply": conv, then the BatchNorm apply pass.  Call it after load_checkpoint
+    and before the optimizer is built.  Returns its argument."""
     from .resnest import ResNeSt50Share
     if backward not in (None, "fp32", "bf16"):
         raise ValueError("freeze_bn: backward must be None, 'fp32' or 'bf16', got %r" % (backward,))
+    if forward not in (None, "apply", "fused"):
+        raise ValueError("freeze_bn: forward must be None, 'apply' or 'fused', got %r" % (forward,))
     share = _share_of(model_or_share)
     if backward == "bf16":
         if isinstance(share, ResNeSt50Share):
@@ -1044,8 +1219,12 @@ def freeze_bn(model_or_share, affine=True, backward=None):
         if share.precision != "fp32":
             raise ValueError("freeze_bn: frozen BatchNorm exists for precision 'fp32' only, not for "
                              "%r" % (share.precision,))
+    if forward == "fused" and affine:
+        raise ValueError("freeze_bn: forward=\"fused\" needs affine=False: dgamma needs the conv "
+                         "output, which this step does not store")
     share.bn_frozen = True
     share.bn_frozen_bwd = "bf16" if backward == "bf16" else None
+    share.bn_frozen_fwd = "fused" if forward == "fused" else None
     for m in _share_bns(share):
         m.training = False
         if not affine:
@@ -1055,12 +1234,13 @@ def freeze_bn(model_or_share, affine=True, backward=None):
 
 
 def unfreeze_bn(model_or_share):
-    """Undo freeze_bn: clear share.bn_frozen (and bn_frozen_bwd), put the BatchNorm modules back to
+    """Undo freeze_bn: clear share.bn_frozen (and bn_frozen_bwd, bn_frozen_fwd), put the BatchNorm modules back to
     share.training and their weights and biases back to requires_grad=True.  Returns its
     argument."""
     share = _share_of(model_or_share)
     share.bn_frozen = False
     share.bn_frozen_bwd = None
+    share.bn_frozen_fwd = None
     for m in _share_bns(share):
         m.training = share.training
         m.weight.requires_grad_(True)
