@@ -122,7 +122,7 @@ def main():
 def run_legs(args, specs):
     """The protocol above over `specs` = [(leg name, trunk precision, prepare)]: prepare(model),
     when given, runs on the leg's fresh train-mode model before its optimizer is built (other
-    benchmarks' legs: scripts/frozen_bn_bench.py).  One JSON line per leg, its name under
+    benchmarks' legs: scripts/frozen_bench.py).  One JSON line per leg, its name under
     "precision"."""
     clips, T, L = CONFIGS[args.config]
     import torch

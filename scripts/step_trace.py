@@ -3,7 +3,8 @@
 A tool for changes to the host logic of the trunk steps (tmrnet_amd/trunk.py, resnest.py) that
 must leave the launches and the bits alone.  For each kind below it builds a fresh seeded share,
 wraps `ops.call` and `resnest.call` by a recorder, runs one step (4 frames of 64x64, seeded as
-tests/test_wgrad_bnbwd_gpu.py::test_wgrad_bnbwd_step_bit_identical does) and prints one JSON line:
+tests/test_wgrad_bnbwd_gpu.py::test_wgrad_bnbwd_step_bit_identical does; a kind whose extras carry
+"input": (frames, side) runs that size instead) and prints one JSON line:
 
   kind      the kind's name
   calls     the number of library calls
@@ -42,8 +43,23 @@ sys.path.insert(0, ROOT)
 # ---------------------------------------------------------------- the kinds
 # (name, backbone, precision, mode, {trunk switch: value}, extras)
 # mode: "train" (forward + backward), "nograd" (train-mode forward under no_grad), "eval"
+# extras: "freeze": the keywords of tmrnet_amd.freeze_bn; "input": (frames, side) where the kind
+# refuses the default 4 frames of 64x64
+def _frozen(precision, affine, backward=None, forward=None, mode="train"):
+    fz = {"affine": affine}
+    if backward:
+        fz["backward"] = backward
+    if forward:
+        fz["forward"] = forward
+    name = "r50 %s frozen %s" % (precision, " ".join("%s=%s" % kv for kv in fz.items()))
+    if mode == "nograd":
+        name += " no_grad"
+    return (name, "resnet50", precision, mode, {}, {"freeze": fz})
+
+
 def _kinds():
     R, S = "resnet50", "resnest50"
+    B, F = "bf16", "fused"
     return [
         ("r50 fp32 train", R, "fp32", "train", {}, {}),
         ("r50 fp32 train WGRAD_BNBWD_DS_MIN=0", R, "fp32", "train", {"WGRAD_BNBWD_DS_MIN": 0}, {}),
@@ -58,8 +74,17 @@ def _kinds():
         ("r50 bf16 train FULL16=False G16=False BF16_STORE=False", R, "bf16", "train",
          {"FULL16": False, "G16": False, "BF16_STORE": False}, {}),
         ("r50 bf16-bwd train", R, "bf16-bwd", "train", {}, {}),
-        ("r50 fp32 frozen affine=True", R, "fp32", "train", {}, {"freeze": True}),
-        ("r50 fp32 frozen affine=False", R, "fp32", "train", {}, {"freeze": False}),
+        _frozen("fp32", True),
+        _frozen("fp32", False),
+        _frozen("fp32", True, B),
+        _frozen("fp32", False, B),
+        _frozen("bf16-bwd", True, B),
+        _frozen("fp32", False, None, F),
+        _frozen("fp32", False, B, F),
+        _frozen("bf16-bwd", False, B, F),
+        _frozen("fp32", True, mode="nograd"),
+        # (without a backward to record the forward is the unfused one)
+        _frozen("fp32", False, None, F, mode="nograd"),
         ("r50 fp32 eval", R, "fp32", "eval", {}, {}),
         ("r50 bf16 eval", R, "bf16", "eval", {}, {}),
         ("r50 bf16 eval infer_act16", R, "bf16", "eval", {}, {"infer_act16": True}),
@@ -144,9 +169,10 @@ def run_kind(spec, dev, full=False, dump=None):
     from tmrnet_amd import ops, trunk
     name, backbone, precision, mode, switches, extra = spec
     gen = torch.Generator().manual_seed(3)
-    x4 = torch.randn(4, 64, 64, 4, generator=gen).to(dev)
+    frames, side = extra.get("input", (4, 64))
+    x4 = torch.randn(frames, side, side, 4, generator=gen).to(dev)
     x4[..., 3] = 0
-    w = torch.randn(4, 2048, generator=gen).to(dev)
+    w = torch.randn(frames, 2048, generator=gen).to(dev)
     saved = {k: getattr(trunk, k) for k in switches}
     log = []
     try:
@@ -155,7 +181,7 @@ def run_kind(spec, dev, full=False, dump=None):
         share = _make_share(backbone, precision, dev)
         share.train(mode != "eval")
         if "freeze" in extra:
-            tmrnet_amd.freeze_bn(share, affine=extra["freeze"])
+            tmrnet_amd.freeze_bn(share, **extra["freeze"])
         if extra.get("infer_act16"):
             share.infer_act16 = True
         torch.cuda.synchronize()
@@ -260,6 +286,9 @@ def main():
     ap.add_argument("--kinds", default=None, help="comma separated kind names (default: all)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--full", action="store_true", help="every tensor's own digest")
+    ap.add_argument("--input", default=None, metavar="FRAMES,SIDE",
+                    help="run the chosen kinds at this input size (to find the smallest a kind "
+                         "takes); a kind that raises prints its error instead")
     ap.add_argument("--dump", default=None, metavar="KIND",
                     help="write this kind's full call list to --out (one call per line)")
     ap.add_argument("--host-bench", action="store_true")
@@ -291,7 +320,15 @@ def main():
                 raise SystemExit("unknown kind %r (have: %s)" % (k, "; ".join(sorted(known))))
         kinds = [k for k in kinds if k[0] in want]
     for spec in kinds:
-        _emit(run_kind(spec, dev, full=args.full), args.out)
+        if args.input:
+            size = tuple(int(v) for v in args.input.split(","))
+            spec = spec[:5] + (dict(spec[5], input=size),)
+        try:
+            _emit(run_kind(spec, dev, full=args.full), args.out)
+        except RuntimeError as e:
+            if not args.input:
+                raise
+            _emit({"kind": spec[0], "input": args.input, "error": str(e)}, args.out)
 
 
 if __name__ == "__main__":

@@ -1,4 +1,5 @@
-"""Shared pieces of the frozen-BatchNorm tests (tests/test_frozen_bn_cpu.py, _gpu.py).
+"""Shared pieces of the frozen-BatchNorm tests (tests/test_frozen_bn_*.py, test_frozen_bwd16_*.py,
+test_frozen_fused_*.py).
 
 step_case(): one seeded 2-frame TMRNet step whose trunk BatchNorms are frozen -- eval mode, every
 BN's running statistics and affine parameters randomised so that a step on batch statistics, a dy
@@ -7,6 +8,7 @@ without the scale or a wrong ReLU mask cannot pass for it.  oracle_step() runs i
 cached tensors are shared between tests and never written.
 """
 import functools
+import math
 
 import torch
 import torch.nn as nn
@@ -193,14 +195,45 @@ def to_nhwc4(x):
     return out
 
 
-def hip_model(dev, frozen=True, affine=True):
+def hip_model(dev, frozen=True, affine=True, backward=None, forward=None, precision="fp32"):
     import tmrnet_amd
-    m = tmrnet_amd.resnet_lstm(seq_len=T).to(dev)
+    m = tmrnet_amd.resnet_lstm(seq_len=T, precision=precision).to(dev)
     m.load_state_dict(step_case()["sd"])
     m.train()
     if frozen:
-        tmrnet_amd.freeze_bn(m, affine=affine)
+        tmrnet_amd.freeze_bn(m, affine=affine, backward=backward, forward=forward)
     return m
+
+
+def _buffers(m):
+    return {n: b.detach().clone() for n, b in m.named_buffers()}
+
+
+def _keep(t):
+    """A hip_step result whose tensors the next step cannot overwrite."""
+    return t[0].clone(), t[1], {n: (g.detach().clone() if g is not None else None)
+                                for n, g in t[2].items()}
+
+
+PAD, SENT = 64, 12345.0
+
+
+def guarded(shape, dev, fill=None, dtype=torch.float32):
+    """A tensor between two PAD-element sentinel zones -> (whole buffer, view); the view is 16-B
+    aligned (PAD elements into an aligned allocation).  fill: a tensor copied into the view, or
+    a number (NaN) it is filled with; None leaves the sentinel value."""
+    n = math.prod(shape)
+    full = torch.full((n + 2 * PAD,), SENT, dtype=dtype, device=dev)
+    view = full[PAD:PAD + n].view(shape)
+    if isinstance(fill, torch.Tensor):
+        view.copy_(fill)
+    elif fill is not None:
+        view.fill_(fill)
+    return full, view
+
+
+def intact(full):
+    return bool((full[:PAD] == SENT).all() and (full[-PAD:] == SENT).all())
 
 
 def hip_inputs(dev, clips=(0,)):

@@ -587,7 +587,7 @@ def test_frozen_bwd_ds_mask(dev, poison, mask):
     gm, _ = _masked(k, "", mask)
     f = lambda n: up(k[n], dev)
     # (gamma_d serves as the downsample BN's scale: an arbitrary fp32 vector)
-    dy, dyd, parts, parts_d, nparts = ops.bn_frozen_bwd_ds(
+    dy, dyd, _, parts, parts_d, nparts = ops.bn_frozen_bwd_ds(
         f("dz"), f("y"), f("scale"), f("shift"), f("mean"), f("yd"), f("gamma_d"), f("mean_d"), mask=mask)
     assert no_nan(dy) and no_nan(dyd)
     assert rel_err(dy, gm * k["scale"]) < E_BWD and rel_err(dyd, gm * k["gamma_d"]) < E_BWD

@@ -23,31 +23,16 @@ import tmrnet_amd
 from tmrnet_amd import ops, _lib
 from tmrnet_amd._lib import stream_ptr
 from tests import _frozen_bn as F
+from tests._frozen_bn import SENT, guarded, intact, _buffers
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PAD, SENT = 64, 12345.0
 SZ = ctypes.c_size_t
 ROWS, CS = (1, 98, 1025), (8, 24, 256)
 
 
 # ---- helpers ----------------------------------------------------------------------------------
-def guarded(shape, dev, fill=None):
-    """A tensor between two PAD-element sentinel zones -> (whole buffer, view); the view is 16-B
-    aligned (PAD * 4 bytes into an aligned allocation)."""
-    n = int(np.prod(shape))
-    full = torch.full((n + 2 * PAD,), SENT, dtype=torch.float32, device=dev)
-    view = full[PAD:PAD + n].view(shape)
-    if fill is not None:
-        view.copy_(fill)
-    return full, view
-
-
-def intact(full):
-    return bool((full[:PAD] == SENT).all() and (full[-PAD:] == SENT).all())
-
-
 def grid(gen, shape, lim, step=16):
     return torch.randint(-lim * step, lim * step + 1, shape, generator=gen).float() / step
 
@@ -278,7 +263,7 @@ def test_frozen_bwd_maxpool(dev, shape, want_sums):
     p, am = ops.maxpool_fwd_bn(yd, sc, sh)
     dyp = grid(gen, tuple(p.shape), 2).to(dev)
     dx = ops.maxpool_bwd(dyp, am, (h, w))
-    dy_ref, parts_ref, np_ref = ops.bn_frozen_bwd(dx, yd, sc, sh, mu, mask=2)
+    dy_ref, _, parts_ref, np_ref = ops.bn_frozen_bwd(dx, yd, sc, sh, mu, mask=2)
     ho, wo = p.shape[1:3]
     dyf, dy = guarded(shape, dev)
     nparts = _lib.query("tmr_bn_frozen_bwd_maxpool_parts", n, h, w, c)
@@ -377,10 +362,6 @@ def test_scaled_weights_and_row_scale(dev):
 
 
 # ---- the step ---------------------------------------------------------------------------------
-def _buffers(m):
-    return {n: b.detach().clone() for n, b in m.named_buffers()}
-
-
 @pytest.fixture(scope="module")
 def frozen_run(dev):
     """One frozen step of the HIP model on step_case(): model, buffers before, logits, grads."""

@@ -14,6 +14,7 @@ import tmrnet_amd
 from tmrnet_amd import ops, _lib
 from tmrnet_amd._lib import stream_ptr
 from tests import _frozen_bn as F
+from tests._frozen_bn import SENT, guarded, intact, _buffers, _keep
 from tests import _frozen_bwd16 as X
 
 pytestmark = pytest.mark.gpu
@@ -22,22 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "profiles", "frozen_bwd16")
 SZ = ctypes.c_size_t
 BF16 = torch.bfloat16
-PAD, SENT = 64, 12345.0
 ROWS, CS = (1, 98, 1025), (8, 24, 256)
-
-
-def guarded(shape, dev, fill=None, dtype=torch.float32):
-    """A tensor between two PAD-element sentinel zones -> (whole buffer, view), 16-B aligned."""
-    n = int(np.prod(shape))
-    full = torch.full((n + 2 * PAD,), SENT, dtype=dtype, device=dev)
-    view = full[PAD:PAD + n].view(shape)
-    if fill is not None:
-        view.copy_(fill)
-    return full, view
-
-
-def intact(full):
-    return bool((full[:PAD] == SENT).all() and (full[-PAD:] == SENT).all())
 
 
 def _bits_of(dev, z):
@@ -85,6 +71,104 @@ def run_x(dev, k, mask, dual, want_sums, b16, want_dy=True, g16=False, inplace=T
         out[n] = X.bits16(v) if v.dtype == BF16 else v.cpu().numpy()
     out["ok"] = all(intact(b) for b in bufs)
     return out
+
+
+def _same(t, ref):
+    """A wrapper's output tensor against run_x's numpy record of it (bf16: as bits)."""
+    if t.dtype == BF16:
+        return np.array_equal(X.bits16(t), ref)
+    return torch.equal(t.cpu(), torch.from_numpy(ref))
+
+
+@pytest.fixture
+def entries(monkeypatch):
+    """The names of the library entries that ops calls, in order."""
+    names, real = [], ops.call
+    monkeypatch.setattr(ops, "call", lambda name, *a: (names.append(name), real(name, *a))[1])
+    return names
+
+
+@pytest.mark.parametrize("rows,c", [(ROWS[0], CS[0]), (ROWS[1], CS[1])])
+def test_merged_wrappers_are_the_direct_calls(dev, entries, rows, c):
+    """ops.bn_frozen_bwd / _ds for masks 0..3, dy16, want_g16 and want_sums on and off, dres in
+    place: every output torch.equal to the same call through _lib.call (run_x; bf16 as bits); with
+    neither dy16 nor want_g16 the fp32 entry is the one called, else the _x entry."""
+    k = X.x_case(rows, c, rows * 1000 + c + 7)
+    v = lambda n: torch.from_numpy(k[n]).to(dev)
+    for mask in range(4):
+        mk = dict(z=v("z")) if mask == 1 else \
+            (dict(bits=_bits_of(dev, k["z"])) if mask == 3 else {})
+        for dual in (False, True):
+            for dy16 in (False, True):
+                for g16 in (False, True):
+                    for sums in (False, True):
+                        what = (rows, c, mask, dual, dy16, g16, sums)
+                        x = dy16 or g16
+                        ref = run_x(dev, k, mask, dual, int(sums), dy16, g16=g16,
+                                    entry="x" if x else "fp32")
+                        assert ref["ok"], what
+                        g = v("g")
+                        a = (g, v("y"), v("scale"), v("shift"), v("mean"))
+                        kw = dict(mask=mask, dres_inplace=True, want_sums=sums, dy16=dy16,
+                                  want_g16=g16, **mk)
+                        del entries[:]
+                        if dual:
+                            dy, dyd, gb, parts, parts_d, nparts = ops.bn_frozen_bwd_ds(
+                                *a, v("yd"), v("scale_d"), v("mean_d"), **kw)
+                            assert _same(dyd, ref["dyd"]), what
+                            assert dyd.dtype == (BF16 if dy16 else torch.float32), what
+                        else:
+                            dy, gb, parts, nparts = ops.bn_frozen_bwd(*a, **kw)
+                            parts_d = None
+                        torch.cuda.synchronize()
+                        name = "tmr_bn_frozen_bwd" + ("_ds" if dual else "") + ("_x" if x else "")
+                        assert [n for n in entries if "frozen" in n] == [name], (what, entries)
+                        assert dy.dtype == (BF16 if dy16 else torch.float32), what
+                        assert _same(dy, ref["dy"]) and _same(g, ref["dres"]), what
+                        assert (gb is None) == (not g16), what
+                        assert gb is None or _same(gb, ref["g16"]), what
+                        if sums:
+                            assert nparts == _lib.query("tmr_bn_frozen_bwd_parts", rows, c)
+                            assert _same(parts, ref["parts"]), what
+                            assert parts_d is None or _same(parts_d, ref["parts_d"]), what
+                            assert (parts_d is not None) == dual, what
+                        else:
+                            assert parts is None and parts_d is None and nparts == 0, what
+
+
+@pytest.mark.parametrize("dy16", [False, True])
+@pytest.mark.parametrize("want_sums", [True, False])
+def test_merged_maxpool_wrapper_is_the_direct_call(dev, entries, dy16, want_sums):
+    """ops.bn_frozen_bwd_maxpool at (1, 9, 7, 64): dy and the partials torch.equal to the direct
+    call of the entry it must take -- the fp32 one without dy16."""
+    shape = n, h, w, c = (1, 9, 7, 64)
+    gen = torch.Generator().manual_seed(97)
+    yd = torch.randn(shape, generator=gen).to(dev)
+    sc = (0.5 + torch.rand(c, generator=gen)).to(dev)
+    sh = (0.1 * torch.randn(c, generator=gen)).to(dev)
+    mu = (0.2 * torch.randn(c, generator=gen)).to(dev)
+    p, am = ops.maxpool_fwd_bn(yd, sc, sh)
+    dyp = torch.randn(tuple(p.shape), generator=gen).to(dev)
+    name = "tmr_bn_frozen_bwd_maxpool" + ("_x" if dy16 else "")
+    nparts = _lib.query("tmr_bn_frozen_bwd_maxpool_parts", n, h, w, c)
+    dyf, dy_ref = guarded(shape, dev, dtype=BF16 if dy16 else torch.float32)
+    pf, parts_ref = guarded((nparts, c, 2), dev)
+    _lib.call(name, dyp, am, n, h, w, p.shape[1], p.shape[2], yd, sc, sh, mu, dy_ref, parts_ref,
+              SZ(nparts * c * 2 * 4), c, int(want_sums), *((1,) if dy16 else ()), stream_ptr())
+    torch.cuda.synchronize()
+    assert intact(dyf) and intact(pf)
+    del entries[:]
+    dy, parts, npp = ops.bn_frozen_bwd_maxpool(dyp, am, yd, sc, sh, mu, want_sums=want_sums,
+                                               dy16=dy16)
+    torch.cuda.synchronize()
+    assert [e for e in entries if "frozen" in e and not e.endswith("_parts")] == [name], entries
+    assert dy.dtype == dy_ref.dtype
+    assert torch.equal(dy.view(torch.int16) if dy16 else dy,
+                       dy_ref.view(torch.int16) if dy16 else dy_ref)
+    if want_sums:
+        assert npp == nparts and torch.equal(parts, parts_ref)
+    else:
+        assert parts is None and npp == 0
 
 
 @pytest.mark.parametrize("c", CS)
@@ -145,8 +229,8 @@ def test_block_output_pass(dev, rows, c):
             assert (got["parts"] == SENT).all()
     g = torch.from_numpy(k["g"]).to(dev)
     v = lambda n: torch.from_numpy(k[n]).to(dev)
-    _, g16, parts, nparts = ops.bn_frozen_bwd_x(g, v("y"), v("scale"), v("shift"), v("mean"),
-                                                mask=0, want_dy=False, want_g16=True)
+    _, g16, parts, nparts = ops.bn_frozen_bwd(g, v("y"), v("scale"), v("shift"), v("mean"),
+                                              mask=0, want_dy=False, want_g16=True)
     assert torch.equal(g16, g.to(BF16)) and np.array_equal(X.bits32(parts.cpu().numpy()),
                                                            X.bits32(ref["parts"]))
 
@@ -188,8 +272,8 @@ def test_frozen_bwd_maxpool_x(dev, shape, want_sums):
         assert torch.equal(res[key][1], res["f32"][1]), key
     if not want_sums:
         assert (res["x16"][1] == SENT).all()
-    dy, parts, npp = ops.bn_frozen_bwd_maxpool_x(dyp, am, yd, sc, sh, mu, want_sums=bool(want_sums),
-                                                 dy16=True)
+    dy, parts, npp = ops.bn_frozen_bwd_maxpool(dyp, am, yd, sc, sh, mu, want_sums=bool(want_sums),
+                                               dy16=True)
     assert dy.dtype == BF16 and torch.equal(dy, res["x16"][0])
     assert (parts is None) == (not want_sums)
 
@@ -318,30 +402,12 @@ def test_fused_dgrad_g16_beside_fp32_y(dev, kind):
 
 
 # ---- the step ---------------------------------------------------------------------------------
-def _buffers(m):
-    return {n: b.detach().clone() for n, b in m.named_buffers()}
-
-
-def hip_model16(dev, precision="fp32", affine=True, frozen=True):
-    m = tmrnet_amd.resnet_lstm(seq_len=F.T, precision=precision).to(dev)
-    m.load_state_dict(F.step_case()["sd"])
-    m.train()
-    if frozen:
-        tmrnet_amd.freeze_bn(m, affine=affine, backward="bf16")
-    return m
-
-
-def _keep(t):
-    return t[0].clone(), t[1], {n: (g.detach().clone() if g is not None else None)
-                                for n, g in t[2].items()}
-
-
 @pytest.fixture(scope="module")
 def runs(dev):
     """One step of the fp32 frozen model and of the frozen16 model (share kind "fp32")."""
     m32 = F.hip_model(dev)
     l32, loss32, g32 = _keep(F.hip_step(m32, dev))
-    m = hip_model16(dev)
+    m = F.hip_model(dev, backward="bf16")
     before = _buffers(m)
     torch.cuda.reset_peak_memory_stats()
     l16, loss16, g16 = _keep(F.hip_step(m, dev))
@@ -447,7 +513,7 @@ def test_step_runs_without_the_batch_statistics_ops(runs, dev, monkeypatch):
 
 
 def test_affine_false_step(dev, runs):
-    m = hip_model16(dev, affine=False)
+    m = F.hip_model(dev, affine=False, backward="bf16")
     logits, loss, grads = F.hip_step(m, dev)
     bn = {n for n, _ in m.named_parameters()
           if n.startswith("share.") and (".bn" in n or ".downsample.1." in n)}
@@ -464,12 +530,12 @@ def test_affine_false_step(dev, runs):
 def test_both_share_kinds_and_unfreeze(dev, runs, precision):
     """The frozen16 step is the same on an "fp32" and a "bf16-bwd" share; unfreeze_bn gives back
     the share's own step, torch.equal to a never-frozen model's."""
-    m = hip_model16(dev, precision)
+    m = F.hip_model(dev, backward="bf16", precision=precision)
     logits, _, grads = F.hip_step(m, dev)
     assert torch.equal(logits, runs["l16"])
     for n, g in grads.items():
         assert torch.equal(g, runs["g16"][n]), n
-    a = hip_model16(dev, precision, frozen=False)
+    a = F.hip_model(dev, frozen=False, precision=precision)
     b = tmrnet_amd.unfreeze_bn(m)
     la, _, ga = F.hip_step(a, dev)
     lb, _, gb = F.hip_step(b, dev)
@@ -531,7 +597,8 @@ def test_short_trajectory(dev):
     x4, lt, labels, masks = F.hip_inputs(dev)
     crit = tmrnet_amd.CrossEntropyLoss(size_average=False)
     traj = {}
-    for key, m in (("frozen32", F.hip_model(dev)), ("frozen16", hip_model16(dev, "bf16-bwd"))):
+    for key, m in (("frozen32", F.hip_model(dev)),
+                   ("frozen16", F.hip_model(dev, backward="bf16", precision="bf16-bwd"))):
         m.nl_block.forced_mask, m.forced_head_mask = masks["nl"], masks["head"]
         opt = tmrnet_amd.SGD(ref.sgd_param_groups(m, F.LR), lr=F.LR / 10, momentum=0.9,
                              weight_decay=5e-4)

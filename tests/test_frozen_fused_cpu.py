@@ -114,8 +114,8 @@ def test_pinned_refusals_keep_their_messages(forward):
 
 
 def test_ops_wrappers_refuse_before_any_library_call(monkeypatch):
-    """conv_fwd_fused_dual's Python-side checks and the y=None rule of bn_frozen_bwd[_x] raise
-    without calling the library (CPU tensors would be refused there anyway)."""
+    """conv_fwd_fused_dual's Python-side checks and the y=None rule of bn_frozen_bwd (fp32 and
+    dy16 forms) raise without calling the library (CPU tensors would be refused there anyway)."""
     def no_call(*a, **k):
         raise AssertionError("library call")
     monkeypatch.setattr(ops, "call", no_call)
@@ -127,11 +127,11 @@ def test_ops_wrappers_refuse_before_any_library_call(monkeypatch):
     with pytest.raises(RuntimeError, match="fp32 operands in fp32 math only, w is torch.bfloat16"):
         ops.conv_fwd_fused_dual(x, w.bfloat16(), 1, 0, sc, sc)
     g = torch.zeros(4, 8)
-    for fn in (ops.bn_frozen_bwd, ops.bn_frozen_bwd_x):
+    for dy16 in (False, True):
         with pytest.raises(RuntimeError, match="y=None needs want_sums=False"):
-            fn(g, None, sc, sc, sc, mask=1, z=g, want_sums=True)
+            ops.bn_frozen_bwd(g, None, sc, sc, sc, mask=1, z=g, want_sums=True, dy16=dy16)
         with pytest.raises(RuntimeError, match="y=None needs want_sums=False"):
-            fn(g, None, sc, sc, sc, mask=2, want_sums=False)
+            ops.bn_frozen_bwd(g, None, sc, sc, sc, mask=2, want_sums=False, dy16=dy16)
 
 
 # ------------------------------------------------------------------ 2. routing

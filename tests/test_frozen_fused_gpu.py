@@ -17,6 +17,7 @@ from tmrnet_amd import ops, trunk, _lib
 from tmrnet_amd._lib import stream_ptr
 from tests import _conv_engine_cases as T
 from tests import _frozen_bn as F
+from tests._frozen_bn import SENT, intact, _buffers, _keep
 from tests import _frozen_bwd16 as X
 from tests import _frozen_fused as Z
 
@@ -27,7 +28,6 @@ OUT = os.path.join(ROOT, "profiles", "frozen_fused")
 BF16 = torch.bfloat16
 F64 = torch.float64
 EPS = 2.0 ** -24
-PAD, SENT = 64, 12345.0
 BY_NAME = {c.name: c for c in T.CASES}
 
 
@@ -49,16 +49,8 @@ def record(key, value):
 
 
 def guarded(shape, dev, dtype=torch.float32):
-    """A NaN-filled tensor between two PAD-element sentinel zones -> (whole buffer, view)."""
-    n = int(np.prod(shape))
-    full = torch.full((n + 2 * PAD,), SENT, dtype=dtype, device=dev)
-    view = full[PAD:PAD + n].view(shape)
-    view.fill_(float("nan"))
-    return full, view
-
-
-def intact(full):
-    return bool((full[:PAD] == SENT).all() and (full[-PAD:] == SENT).all())
+    """A NaN-filled tensor between two sentinel zones -> (whole buffer, view)."""
+    return F.guarded(shape, dev, float("nan"), dtype)
 
 
 # ------------------------------------------------------------------ the dual forward
@@ -337,23 +329,8 @@ MODES = [None, "bf16"]
 IDS = ["bwd-fp32", "bwd-bf16"]
 
 
-def _buffers(m):
-    return {n: b.detach().clone() for n, b in m.named_buffers()}
-
-
-def hip_model(dev, backward=None, fused=True, precision="fp32", frozen=True):
-    m = tmrnet_amd.resnet_lstm(seq_len=F.T, precision=precision).to(dev)
-    m.load_state_dict(F.step_case()["sd"])
-    m.train()
-    if frozen:
-        tmrnet_amd.freeze_bn(m, affine=False, backward=backward,
-                             forward="fused" if fused else None)
-    return m
-
-
-def _keep(t):
-    return t[0].clone(), t[1], {n: (g.detach().clone() if g is not None else None)
-                                for n, g in t[2].items()}
+NOAFF = dict(affine=False)                      # the unfused partner's freeze_bn keywords
+FUSED = dict(affine=False, forward="fused")     # the fused step's
 
 
 _RUNS = {}
@@ -365,8 +342,8 @@ def runs(dev):
     once, never written) -> {backward: dict}."""
     def get(backward):
         if backward not in _RUNS:
-            ref = _keep(F.hip_step(hip_model(dev, backward, fused=False), dev))
-            m = hip_model(dev, backward)
+            ref = _keep(F.hip_step(F.hip_model(dev, backward=backward, **NOAFF), dev))
+            m = F.hip_model(dev, backward=backward, **FUSED)
             before = _buffers(m)
             got = _keep(F.hip_step(m, dev))
             _RUNS[backward] = {"m": m, "before": before, "ref": ref, "got": got}
@@ -495,13 +472,13 @@ def test_both_share_kinds_and_unfreeze(dev, runs):
     """backward="bf16": the "fp32" and the "bf16-bwd" share give the same bits; unfreeze_bn gives
     back the share's own step, torch.equal to a never-frozen model's."""
     want = runs("bf16")["got"]
-    m = hip_model(dev, "bf16", precision="bf16-bwd")
+    m = F.hip_model(dev, backward="bf16", precision="bf16-bwd", **FUSED)
     logits, _, grads = F.hip_step(m, dev)
     assert torch.equal(logits, want[0])
     for n, g in grads.items():
         assert (g is None and want[2][n] is None) or torch.equal(g, want[2][n]), n
-    for precision, mm in (("bf16-bwd", m), ("fp32", hip_model(dev, None))):
-        a = hip_model(dev, precision=precision, frozen=False)
+    for precision, mm in (("bf16-bwd", m), ("fp32", F.hip_model(dev, **FUSED))):
+        a = F.hip_model(dev, frozen=False, precision=precision)
         b = tmrnet_amd.unfreeze_bn(mm)
         assert b.share.bn_frozen_fwd is None
         la, _, ga = F.hip_step(a, dev)
@@ -566,7 +543,7 @@ def test_short_trajectory(dev, backward):
     crit = tmrnet_amd.CrossEntropyLoss(size_average=False)
     traj = {}
     for key in ("unfused", "fused"):
-        m = hip_model(dev, backward, fused=key == "fused")
+        m = F.hip_model(dev, backward=backward, **(FUSED if key == "fused" else NOAFF))
         m.nl_block.forced_mask, m.forced_head_mask = masks["nl"], masks["head"]
         opt = tmrnet_amd.SGD(ref.sgd_param_groups(m, F.LR), lr=F.LR / 10, momentum=0.9,
                              weight_decay=5e-4)
@@ -600,7 +577,7 @@ def test_peak_memory_is_below_the_unfused_step(dev, backward):
     crit = tmrnet_amd.CrossEntropyLoss(size_average=False)
     peak = {}
     for key in ("unfused", "fused"):
-        m = hip_model(dev, backward, fused=key == "fused")
+        m = F.hip_model(dev, backward=backward, **(FUSED if key == "fused" else NOAFF))
         for it in range(2):
             for p in m.parameters():
                 p.grad = None

@@ -1218,135 +1218,89 @@ def _frozen_out(like, want, bf16):
     return torch.empty_like(like, dtype=BF16 if bf16 else f32) if want else None
 
 
+def _frozen_parts(want, entry, dims, c, dev, n=1):
+    """The partial-sum buffers of a frozen-BN backward pass -> (n tensors or Nones, nparts, the
+    byte count of one)."""
+    if not want:
+        return (None,) * n, 0, ctypes.c_size_t(0)
+    nparts = query(entry, *dims)
+    parts = tuple(torch.empty((nparts, c, 2), dtype=f32, device=dev) for _ in range(n))
+    return parts, nparts, ctypes.c_size_t(parts[0].numel() * 4)
+
+
 def bn_frozen_bwd(g, y, scale, shift, mean, mask, z=None, bits=None, want_dy=True,
-                  dres_inplace=False, want_sums=True):
-    """Frozen-BN backward of one unit in one pass (tmr_bn_frozen_bwd) -> (dy, parts, nparts).
+                  dres_inplace=False, want_sums=True, dy16=False, want_g16=False):
+    """Frozen-BN backward of one unit in one pass -> (dy, g16, parts, nparts).
     mask 0: g already masked; 1: z > 0; 2: fmaf(y, scale, shift) > 0; 3: the ReLU-mask bits.
     dres_inplace: the masked gradient overwrites g (the identity branch's gradient).
     want_dy=False: no dy (the caller folds the scale into its conv operands); want_sums=False:
-    no partials (affine=False), parts is None.  bn_frozen_finalize turns parts into dgamma, dbeta."""
+    no partials (affine=False), parts is None.  bn_frozen_finalize turns parts into dgamma, dbeta.
+    dy16: dy rounded once to bf16; want_g16: also the masked g itself as bf16 (else None).  Either
+    takes tmr_bn_frozen_bwd_x, neither tmr_bn_frozen_bwd: dres and the partials are the same bit
+    for bit.  want_dy=False, want_g16=True, mask 0: the cast pass over a block output's gradient
+    (with the sums of (g, y) if wanted)."""
     y = _frozen_y(g, y, mask, want_sums, "bn_frozen_bwd")
-    c = g.shape[-1]
-    rows = g.numel() // c
-    zm = _frozen_mask(mask, z, bits, g)
-    dy = torch.empty_like(g) if want_dy else None
-    parts, nparts = None, 0
-    if want_sums:
-        nparts = query("tmr_bn_frozen_bwd_parts", rows, c)
-        parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
-    call("tmr_bn_frozen_bwd", g, zm, int(mask), y, scale, shift, mean, dy,
-         g if dres_inplace else None, parts,
-         ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), rows, c, int(want_sums),
-         stream_ptr())
-    return dy, parts, nparts
-
-
-def bn_frozen_bwd_x(g, y, scale, shift, mean, mask, z=None, bits=None, want_dy=True,
-                    dres_inplace=False, want_sums=True, dy16=False, want_g16=False):
-    """bn_frozen_bwd with dy stored fp32 or (dy16) rounded once to bf16, and (want_g16) the masked
-    g itself as bf16 (tmr_bn_frozen_bwd_x) -> (dy, g16, parts, nparts).  dres and the partials are
-    bn_frozen_bwd's bit for bit.  want_dy=False, want_g16=True, mask 0: the cast pass over a block
-    output's gradient (with the sums of (g, y) if wanted)."""
-    y = _frozen_y(g, y, mask, want_sums, "bn_frozen_bwd_x")
     c = g.shape[-1]
     rows = g.numel() // c
     zm = _frozen_mask(mask, z, bits, g)
     dy = _frozen_out(g, want_dy, dy16)
     g16 = _frozen_out(g, want_g16, True)
-    parts, nparts = None, 0
-    if want_sums:
-        nparts = query("tmr_bn_frozen_bwd_parts", rows, c)
-        parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
-    call("tmr_bn_frozen_bwd_x", g, zm, int(mask), y, scale, shift, mean, dy,
-         g if dres_inplace else None, g16, parts,
-         ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), rows, c, int(want_sums),
-         int(bool(dy16)), stream_ptr())
+    (parts,), nparts, nbytes = _frozen_parts(want_sums, "tmr_bn_frozen_bwd_parts", (rows, c), c,
+                                             g.device)
+    dres = g if dres_inplace else None
+    if dy16 or want_g16:
+        call("tmr_bn_frozen_bwd_x", g, zm, int(mask), y, scale, shift, mean, dy, dres, g16, parts,
+             nbytes, rows, c, int(want_sums), int(bool(dy16)), stream_ptr())
+    else:
+        call("tmr_bn_frozen_bwd", g, zm, int(mask), y, scale, shift, mean, dy, dres, parts,
+             nbytes, rows, c, int(want_sums), stream_ptr())
     return dy, g16, parts, nparts
 
 
 def bn_frozen_bwd_ds(g, y, scale, shift, mean, yd, scale_d, mean_d, mask, z=None, bits=None,
-                     want_dy=True, dres_inplace=False, want_sums=True):
+                     want_dy=True, dres_inplace=False, want_sums=True, dy16=False,
+                     want_g16=False):
     """bn_frozen_bwd for a downsample block's bn3 (y) and downsample BN (y_ds), which share g, in
-    one read of g (tmr_bn_frozen_bwd_ds) -> (dy, dy_ds, parts, parts_ds, nparts)."""
+    one read of g (tmr_bn_frozen_bwd_ds; with dy16 or want_g16 tmr_bn_frozen_bwd_ds_x)
+    -> (dy, dy_ds, g16, parts, parts_ds, nparts)."""
     _req(g, "g"); _req(y, "y"); _req(yd, "y_ds")
     if not (g.shape == y.shape == yd.shape):
         raise RuntimeError("bn_frozen_bwd_ds: g, y and y_ds must have one shape")
     c = y.shape[-1]
     rows = y.numel() // c
     zm = _frozen_mask(mask, z, bits, y)
-    dy = torch.empty_like(y) if want_dy else None
-    dyd = torch.empty_like(yd) if want_dy else None
-    parts = parts_d = None
-    nparts = 0
-    if want_sums:
-        nparts = query("tmr_bn_frozen_bwd_parts", rows, c)
-        parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
-        parts_d = torch.empty_like(parts)
-    call("tmr_bn_frozen_bwd_ds", g, zm, int(mask), y, scale, shift, mean, dy, yd, scale_d, mean_d,
-         dyd, g if dres_inplace else None, parts, parts_d,
-         ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), rows, c, int(want_sums),
-         stream_ptr())
-    return dy, dyd, parts, parts_d, nparts
-
-
-def bn_frozen_bwd_ds_x(g, y, scale, shift, mean, yd, scale_d, mean_d, mask, z=None, bits=None,
-                       want_dy=True, dres_inplace=False, want_sums=True, dy16=False,
-                       want_g16=False):
-    """bn_frozen_bwd_ds with both dy's fp32 or (dy16) bf16 and (want_g16) the masked g as bf16
-    (tmr_bn_frozen_bwd_ds_x) -> (dy, dy_ds, g16, parts, parts_ds, nparts)."""
-    _req(g, "g"); _req(y, "y"); _req(yd, "y_ds")
-    if not (g.shape == y.shape == yd.shape):
-        raise RuntimeError("bn_frozen_bwd_ds_x: g, y and y_ds must have one shape")
-    c = y.shape[-1]
-    rows = y.numel() // c
-    zm = _frozen_mask(mask, z, bits, y)
     dy = _frozen_out(y, want_dy, dy16)
     dyd = _frozen_out(yd, want_dy, dy16)
     g16 = _frozen_out(y, want_g16, True)
-    parts = parts_d = None
-    nparts = 0
-    if want_sums:
-        nparts = query("tmr_bn_frozen_bwd_parts", rows, c)
-        parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
-        parts_d = torch.empty_like(parts)
-    call("tmr_bn_frozen_bwd_ds_x", g, zm, int(mask), y, scale, shift, mean, dy, yd, scale_d,
-         mean_d, dyd, g if dres_inplace else None, g16, parts, parts_d,
-         ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), rows, c, int(want_sums),
-         int(bool(dy16)), stream_ptr())
+    (parts, parts_d), nparts, nbytes = _frozen_parts(want_sums, "tmr_bn_frozen_bwd_parts",
+                                                     (rows, c), c, y.device, n=2)
+    dres = g if dres_inplace else None
+    if dy16 or want_g16:
+        call("tmr_bn_frozen_bwd_ds_x", g, zm, int(mask), y, scale, shift, mean, dy, yd, scale_d,
+             mean_d, dyd, dres, g16, parts, parts_d, nbytes, rows, c, int(want_sums),
+             int(bool(dy16)), stream_ptr())
+    else:
+        call("tmr_bn_frozen_bwd_ds", g, zm, int(mask), y, scale, shift, mean, dy, yd, scale_d,
+             mean_d, dyd, dres, parts, parts_d, nbytes, rows, c, int(want_sums), stream_ptr())
     return dy, dyd, g16, parts, parts_d, nparts
 
 
-def bn_frozen_bwd_maxpool(dyp, am, y, scale, shift, mean, want_sums=True):
+def bn_frozen_bwd_maxpool(dyp, am, y, scale, shift, mean, want_sums=True, dy16=False):
     """The stem's frozen-BN backward: MaxPool2d(3,2,1) backward (gathered from the pooled gradient
-    and argmax), the ReLU mask from fmaf(y, scale, shift), dy = g*scale and the partial sums in
-    one pass (tmr_bn_frozen_bwd_maxpool) -> (dy, parts, nparts)."""
-    _req(dyp, "dyp"); _req(y, "y"); _req(am, "argmax", torch.uint8)
-    n, h, w, c = y.shape
-    _, ho, wo, _ = dyp.shape
-    dy = torch.empty_like(y)
-    parts, nparts = None, 0
-    if want_sums:
-        nparts = query("tmr_bn_frozen_bwd_maxpool_parts", n, h, w, c)
-        parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
-    call("tmr_bn_frozen_bwd_maxpool", dyp, am, n, h, w, ho, wo, y, scale, shift, mean, dy, parts,
-         ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), c, int(want_sums), stream_ptr())
-    return dy, parts, nparts
-
-
-def bn_frozen_bwd_maxpool_x(dyp, am, y, scale, shift, mean, want_sums=True, dy16=False):
-    """bn_frozen_bwd_maxpool with dy fp32 or (dy16) rounded once to bf16
-    (tmr_bn_frozen_bwd_maxpool_x); the same partials -> (dy, parts, nparts)."""
+    and argmax), the ReLU mask from fmaf(y, scale, shift), dy = g*scale (dy16: rounded once to
+    bf16) and the partial sums in one pass (tmr_bn_frozen_bwd_maxpool; with dy16
+    tmr_bn_frozen_bwd_maxpool_x, the same partials) -> (dy, parts, nparts)."""
     _req(dyp, "dyp"); _req(y, "y"); _req(am, "argmax", torch.uint8)
     n, h, w, c = y.shape
     _, ho, wo, _ = dyp.shape
     dy = _frozen_out(y, True, dy16)
-    parts, nparts = None, 0
-    if want_sums:
-        nparts = query("tmr_bn_frozen_bwd_maxpool_parts", n, h, w, c)
-        parts = torch.empty((nparts, c, 2), dtype=f32, device=y.device)
-    call("tmr_bn_frozen_bwd_maxpool_x", dyp, am, n, h, w, ho, wo, y, scale, shift, mean, dy, parts,
-         ctypes.c_size_t(parts.numel() * 4 if want_sums else 0), c, int(want_sums),
-         int(bool(dy16)), stream_ptr())
+    (parts,), nparts, nbytes = _frozen_parts(want_sums, "tmr_bn_frozen_bwd_maxpool_parts",
+                                             (n, h, w, c), c, y.device)
+    args = (dyp, am, n, h, w, ho, wo, y, scale, shift, mean, dy, parts, nbytes, c, int(want_sums))
+    if dy16:
+        call("tmr_bn_frozen_bwd_maxpool_x", *args, 1, stream_ptr())
+    else:
+        call("tmr_bn_frozen_bwd_maxpool", *args, stream_ptr())
     return dy, parts, nparts
 
 

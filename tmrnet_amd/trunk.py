@@ -20,7 +20,9 @@ The other step kinds, each specified by the block comment named:
   * precision "bf16-bwd": the fp32 forward, bf16 operands in the backward convs only (BWD16);
   * frozen BatchNorm (freeze_bn): a train step on the running statistics ("frozen BatchNorm");
     with backward="bf16" its backward convs in bf16 math (_frozen16); with forward="fused" BN
-    folded into the conv forward, no conv output stored (_frozen_fused);
+    folded into the conv forward, no conv output stored (_frozen_fused).  One backward walk
+    (TrunkFn._backward_frozen) and one per-unit helper (_frozen_unit_bwd) serve them all: the
+    units' records say which forward ran (DESIGN.md §33);
   * infer16: eval mode with bf16 activations, opt-in (_infer16, TrunkFn._forward_eval).
 How the units of a step are put together: "the conv+BN unit" below, DESIGN.md §29.
 """
@@ -240,8 +242,9 @@ def _infer16(share):
 
 # ------------------------------------------------------------------ the conv+BN unit
 class Unit:
-    """What the forward of one conv+BN unit leaves for its backward.  Built by _TrainUnits._run
-    only; every field is set for every unit, None where the step kind has no such tensor."""
+    """What the forward of one conv+BN unit leaves for its backward.  Built by
+    _TrainUnits._record only; every field is set for every unit, None where the step kind has no
+    such tensor."""
     __slots__ = (
         "conv", "bn",      # the parameter containers
         "x",       # the conv's input as the wgrad reads it (bf16-bwd: its bf16 copy x16, but the
@@ -387,13 +390,23 @@ class _TrainUnits:
             z = ops.conv_fwd_fused(x, wk, stride, pad, scale, shift, residual, relu, c_real=c,
                                    math=math)
         zm = (z16 if z16 is not None else z) if relu else None
-        rec = Unit(conv=conv, bn=bn, x=x16 if (bwd16 and x16 is not None) else x, wk=wk,
-                   wt=_dgrad_weights(w, x, math, 1, bwd16, scale if fold else None),
-                   y=None, z=zm, zbits=None, scale=scale, shift=shift, mean=bn.running_mean,
-                   inv=inv, stride=stride, pad=pad, relu=relu, c_real=c,
-                   math="bf16" if bwd16 else math, groups=1, res=residual is not None,
-                   dy16=bwd16, fold=bool(fold))
+        rec = self._record(conv, bn, x, x16, wk, None, zm, None, (scale, shift, bn.running_mean,
+                           inv), stride, pad, relu, 1, residual is not None, bool(fold))
         return z, z16, rec
+
+    def _record(self, conv, bn, x, x16, wk, y, z, zbits, coefs, stride, pad, relu, groups, res,
+                fold):
+        """The Unit of one forward unit.  coefs: (scale, shift, mean, inv).  bwd16: the backward's
+        conv views read the bf16 copies (x16, a bf16 wt) in bf16 math, dy stored bf16."""
+        w = conv.weight
+        bwd16 = self.bwd16
+        scale, shift, mean, inv = coefs
+        return Unit(conv=conv, bn=bn, x=x16 if (bwd16 and x16 is not None) else x, wk=wk,
+                    wt=_dgrad_weights(w, x, self.math, groups, bwd16, scale if fold else None),
+                    y=y, z=z, zbits=zbits, scale=scale, shift=shift, mean=mean, inv=inv,
+                    stride=stride, pad=pad, relu=relu, c_real=w.shape[1],
+                    math="bf16" if bwd16 else self.math, groups=groups, res=res, dy16=bwd16,
+                    fold=fold)
 
     def _run(self, x, conv, bn, stride, pad, relu, defer, residual=None, branch=None, dual=False,
              groups=1, x16=None, fold=True):
@@ -434,14 +447,9 @@ class _TrainUnits:
                                            dual or bwd16, s16)
         rec = None
         if self.keep:
-            folded = bool(frozen is not None and fold)
-            # bwd16: the backward's conv views read the bf16 copies in bf16 math, dy stored bf16
-            rec = Unit(conv=conv, bn=bn, x=x16 if (bwd16 and x16 is not None) else x, wk=wk,
-                       wt=_dgrad_weights(w, x, math, groups, bwd16, scale if folded else None),
-                       y=y, z=z if has_res else None, zbits=zbits, scale=scale, shift=shift,
-                       mean=mean, inv=inv, stride=stride, pad=pad, relu=relu, c_real=c,
-                       math="bf16" if bwd16 else math, groups=groups, res=has_res, dy16=bwd16,
-                       fold=folded)
+            rec = self._record(conv, bn, x, x16, wk, y, z if has_res else None, zbits,
+                               (scale, shift, mean, inv), stride, pad, relu, groups, has_res,
+                               bool(frozen is not None and fold))
         return (y, scale, shift), z, z16, rec
 
 
@@ -646,7 +654,9 @@ def _frozen_step(share):
 # for a single-pass unit.  bn1 / bn2's g is stored bf16 by the fused dgrad that produces it
 # (TMR_IO_G16 beside an fp32 y; its sums are of the rounded values); a block output's g stays
 # fp32 (the residual stream; sums of the fp32 values) and one pass per block writes its bf16
-# copy (tmr_bn_frozen_bwd_x: the downsample BN's sums-only pass, or a plain cast).  DESIGN.md §31.
+# copy (ops.bn_frozen_bwd(want_g16=True): the downsample BN's sums-only pass, or a plain cast).
+# In the walk (TrunkFn._backward_frozen) all of this is `f16`: dy16 / want_g16 of the frozen-BN
+# passes, and the bf16 store of bn1 / bn2's g in _frozen_unit_bwd.  DESIGN.md §31.
 def _frozen16(share):
     return bool(getattr(share, "bn_frozen", False) and share.training
                 and getattr(share, "bn_frozen_bwd", None) == "bf16"
@@ -661,7 +671,9 @@ def _frozen16(share):
 # predicate fmaf(y, scale, shift) > 0), the tensor the next unit keeps as x anyway; with a bf16
 # backward the mask is z16 > 0, which differs from z > 0 only where a positive fp32 z rounds to
 # bf16 zero (below the bf16 subnormal range).  No BN gradient exists (affine=False), so nothing in
-# the backward needs y.  The stem keeps conv_fwd + maxpool_fwd_bn[_dual] and its y.
+# the backward needs y.  The stem keeps conv_fwd + maxpool_fwd_bn[_dual] and its y.  The backward
+# is the frozen step's one walk: a record without y sends the dgrad that produces its unit's
+# gradient to ops.conv_dgrad_relu on the stored output (_frozen_unit_bwd).
 def _frozen_fused(share):
     return bool(getattr(share, "bn_frozen", False) and share.training
                 and getattr(share, "bn_frozen_fwd", None) == "fused")
@@ -692,54 +704,50 @@ def _frozen_affine(rec, parts, grads):
             parts[0], parts[1], rec.inv)
 
 
-def _frozen_unit_bwd(rec, g, grads, parts=None, **conv):
-    """wgrad and dgrad (_conv_bwd's keywords) of a frozen-BN unit whose g came masked from a fused
-    dgrad (`parts` -> the BN gradients): the wgrad runs on g and dW's rows take scale[k], the
-    dgrad reads the pre-scaled CRSK weights (rec.fold) -- no pass forms dy = g*scale."""
+def _frozen_unit_bwd(rec, gy, grads, f16, real_dy=False, parts=None, prev=None, dx_out=None,
+                     dx_beta=0.0, need_dx=True):
+    """wgrad and dgrad of one unit of the frozen step -> (dx, the partial sums that came with it).
+    gy: the unit's masked gradient g, from a fused dgrad (`parts` -> the BN gradients) -- the wgrad
+    runs on g and dW's rows take scale[k], the dgrad reads the pre-scaled CRSK weights (rec.fold),
+    no pass forms dy = g*scale; or (real_dy) the dy = g*scale a single-pass kernel wrote.
+    prev: the unit whose output gradient this dgrad produces, masked by what that unit stored: its
+    ReLU output where the forward kept no y (ops.conv_dgrad_relu; no sums), else y / z / bits with
+    the partial sums (_conv_bwd).  f16 (the bf16 backward): that gradient is stored bf16 unless
+    prev is a block output (the residual stream's gradient stays fp32); a dgrad that cannot
+    raises with its shape."""
     _frozen_affine(rec, parts, grads)
-    if not rec.fold:
-        raise RuntimeError("frozen BN: a folded unit needs its pre-scaled dgrad weights")
-    out = _conv_bwd(rec, g, grads, **conv)
-    ops.scale_rows(grads[rec.conv.weight], rec.scale)
-    return out
-
-
-def _frozen_dy_bwd(rec, dy, grads, **conv):
-    """The same for a unit of the single-pass kernels, which wrote its real dy = g*scale."""
-    if rec.fold:
+    if real_dy and rec.fold:
         raise RuntimeError("frozen BN: a real dy meets pre-scaled dgrad weights")
-    return _conv_bwd(rec, dy, grads, **conv)
-
-
-def _fused_unit_bwd(rec, gy, grads, f16, prev=None, dx_out=None, dx_beta=0.0):
-    """wgrad and dgrad of a unit of the fused frozen step (no y anywhere, no BN gradient) -> dx.
-    gy: the unit's masked gradient g for a folded unit (dW's rows take scale[k], the dgrad reads the
-    pre-scaled CRSK weights), or its real dy = g*scale for the last block's bn3.  prev: the unit
-    whose output gradient this dgrad produces -- masked by that unit's stored output
-    (ops.conv_dgrad_relu), stored bf16 under ``f16`` unless it is a block output (the residual
-    stream's gradient stays fp32).  A dgrad that refuses the operand mix raises with its shape."""
+    if not (real_dy or rec.fold):
+        raise RuntimeError("frozen BN: a folded unit needs its pre-scaled dgrad weights")
     r, s = rec.conv.weight.shape[2:]
-    grads[rec.conv.weight] = ops.conv_wgrad(rec.x, gy, r, s, rec.stride, rec.pad,
-                                            c_real=rec.c_real, math=rec.math)
-    if rec.fold:
-        ops.scale_rows(grads[rec.conv.weight], rec.scale)
-    hw = (rec.x.shape[1], rec.x.shape[2])
-    wt = rec.wt is not None
-    wdg = rec.wt if wt else rec.wk
-    if prev is None:
-        return ops.conv_dgrad(gy, wdg, hw, rec.stride, rec.pad, out=dx_out, beta=dx_beta,
-                              math=rec.math, wt=wt)
-    if not prev.relu or prev.z is None:
-        raise RuntimeError("frozen BN, fused forward: the masked dgrad needs the previous unit's "
-                           "stored ReLU output")
-    try:
-        return ops.conv_dgrad_relu(gy, wdg, hw, rec.stride, rec.pad, prev.z, out=dx_out,
-                                   beta=dx_beta, math=rec.math, wt=wt, g16=f16 and not prev.res)
-    except RuntimeError as e:
-        raise RuntimeError("frozen BN, fused forward: the masked dgrad of dy %s, weight %s, stride "
-                           "%d refused its operands (mask source %s, beta %g): %s"
-                           % (tuple(gy.shape), tuple(rec.conv.weight.shape), rec.stride,
-                              prev.z.dtype, dx_beta, e))
+    dw = ops.conv_wgrad(rec.x, gy, r, s, rec.stride, rec.pad, c_real=rec.c_real, math=rec.math)
+    # (dW's rows are scaled before the dgrad for a unit without y, after it otherwise: the launch
+    # order scripts/step_trace.py pins)
+    if rec.fold and rec.y is None:
+        ops.scale_rows(dw, rec.scale)
+    g16 = bool(f16 and prev is not None and not prev.res)
+    if need_dx and prev is not None and prev.y is None:
+        if not prev.relu or prev.z is None:
+            raise RuntimeError("frozen BN, fused forward: the masked dgrad needs the previous "
+                               "unit's stored ReLU output")
+        grads[rec.conv.weight] = dw
+        wt = rec.wt is not None
+        try:
+            dx, fused = ops.conv_dgrad_relu(
+                gy, rec.wt if wt else rec.wk, (rec.x.shape[1], rec.x.shape[2]), rec.stride,
+                rec.pad, prev.z, out=dx_out, beta=dx_beta, math=rec.math, wt=wt, g16=g16), None
+        except RuntimeError as e:
+            raise RuntimeError("frozen BN, fused forward: the masked dgrad of dy %s, weight %s, "
+                               "stride %d refused its operands (mask source %s, beta %g): %s"
+                               % (tuple(gy.shape), tuple(rec.conv.weight.shape), rec.stride,
+                                  prev.z.dtype, dx_beta, e))
+    else:
+        dx, fused = _conv_bwd(rec, gy, grads, dw=dw, dx_out=dx_out, dx_beta=dx_beta,
+                              need_dx=need_dx, fuse_prev=prev, g16_y32=g16)
+    if rec.fold and rec.y is not None:
+        ops.scale_rows(dw, rec.scale)
+    return dx, fused
 
 
 class TrunkFn(torch.autograd.Function):
@@ -801,51 +809,40 @@ class TrunkFn(torch.autograd.Function):
         h, hx = (None, p) if f16 else (p, p)
         blocks = []
         last = layers[-1][-1]
+        unit = st.fused if fu else st.unit
         for layer in layers:
             for blk in layer:
-                if fu:
-                    # BN folded into the conv forward: one launch per unit, no y, no apply pass;
-                    # the downsample branch is a fused unit without ReLU whose fp32 output (no
-                    # conv operand: no bf16 copy) is conv3's residual
-                    fold = blk is not last
-                    z1, z1h, r1 = st.fused(hx, blk.conv1, blk.bn1, 1, 0, True, x16=h16)
-                    z2, z2h, r2 = st.fused(z1, blk.conv2, blk.bn2, blk.stride, 1, True, x16=z1h)
-                    rd, idn = None, h
-                    if blk.downsample is not None:
-                        idn, _, rd = st.fused(hx, blk.downsample[0], blk.downsample[1], blk.stride,
-                                              0, False, x16=h16, fold=fold, copy16=False)
-                    # (the last block's output is no conv operand: fp32 only, which is also the
-                    # mask-1 source of its bn3's single pass)
-                    h, h16, r3 = st.fused(z2, blk.conv3, blk.bn3, 1, 0, True, residual=idn,
-                                          x16=z2h, fold=fold, copy16=fold)
-                    hx = h
-                    del z1, z2, idn   # (bf16 backward: the records hold the bf16 copies only)
-                    blocks.append((blk, [r1, r2, rd, r3]))
-                    continue
-                z1, z1h, r1 = st.unit(hx, blk.conv1, blk.bn1, 1, 0, True, x16=h16)
-                z2, z2h, r2 = st.unit(z1, blk.conv2, blk.bn2, blk.stride, 1, True, x16=z1h)
+                # fu: BN folded into the conv forward -- one launch per unit, no y, no apply pass
+                z1, z1h, r1 = unit(hx, blk.conv1, blk.bn1, 1, 0, True, x16=h16)
+                z2, z2h, r2 = unit(z1, blk.conv2, blk.bn2, blk.stride, 1, True, x16=z1h)
                 # the frozen step: every unit but the last block's bn3 / downsample BN (whose g
                 # arrives unmasked) folds its dy scale into its dgrad weights
                 fold = blk is not last
-                rd = None
-                if blk.downsample is not None:
+                rd, idn, how = None, h, "residual"
+                if blk.downsample is not None and fu:
+                    # a fused unit without ReLU whose fp32 output (no conv operand: no bf16 copy)
+                    # is conv3's residual
+                    idn, _, rd = st.fused(hx, blk.downsample[0], blk.downsample[1], blk.stride, 0,
+                                          False, x16=h16, fold=fold, copy16=False)
+                elif blk.downsample is not None:
                     # the branch's BN is applied inside the BN3 pass (bn_apply2)
+                    how = "branch"
                     idn, rd = st.deferred(hx, blk.downsample[0], blk.downsample[1], blk.stride, 0,
                                           False, x16=h16, fold=fold)
-                    h, hc, r3 = st.unit(z2, blk.conv3, blk.bn3, 1, 0, True, branch=idn, dual=f16,
-                                        x16=z2h, fold=fold)
-                else:
-                    if h is None:
-                        raise RuntimeError("identity residual of the stem output (no downsample)")
-                    idn = h
-                    h, hc, r3 = st.unit(z2, blk.conv3, blk.bn3, 1, 0, True, residual=idn,
-                                        dual=f16, x16=z2h, fold=fold)
+                elif h is None:
+                    raise RuntimeError("identity residual of the stem output (no downsample)")
+                # (fu: the last block's output is no conv operand -- fp32 only, which is also the
+                # mask-1 source of its bn3's single pass)
+                out = dict(copy16=fold) if fu else dict(dual=f16)
+                h, hc, r3 = unit(z2, blk.conv3, blk.bn3, 1, 0, True, x16=z2h, fold=fold,
+                                 **{how: idn}, **out)
                 hx = hc if f16 else h
                 if bw:
                     h16 = hc
-                    if blocks:   # the previous block output's fp32 z: its mask is in the bits
-                        blocks[-1][1][-1].z = None
-                    del z1, z2, idn   # (their fp32 z's were only this block's forward operands)
+                    if blocks and not fu:   # the previous block output's fp32 z: its mask is in
+                        blocks[-1][1][-1].z = None   # the bits (fu: z is the mask)
+                if bw or fu:   # (their fp32 z's were only this block's forward operands; with a
+                    del z1, z2, idn   # bf16 backward the records hold the bf16 copies only)
                 blocks.append((blk, [r1, r2, rd, r3]))
         if f16z and blocks[-1][1][-1].zbits is not None:
             blocks[-1][1][-1].z = None   # (the last block's mask is in the bits too)
@@ -889,8 +886,6 @@ class TrunkFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dfeat):
-        if ctx.frozen and ctx.frozen_fused:
-            return TrunkFn._backward_frozen_fused(ctx, dfeat)
         if ctx.frozen:
             return TrunkFn._backward_frozen(ctx, dfeat)
         grads = {}
@@ -948,150 +943,85 @@ class TrunkFn(torch.autograd.Function):
 
     @staticmethod
     def _backward_frozen(ctx, dfeat):
-        """The frozen-BN step's backward: no BN-backward projection anywhere.  The last block's
-        bn3 (g unmasked from the avgpool) and the stem (g through the maxpool) take one pass of
-        tmr_bn_frozen_bwd / _maxpool; every other unit's g comes masked, with its partial sums,
-        from the fused dgrad that produced it, and its dy = g*scale lives in the conv operands
-        (_frozen_unit_bwd).  A downsample BN needs sum g*(y_ds - mean_ds) of its own: one
-        sums-only pass over (g, y_ds), skipped with affine=False.  ctx.frozen16: the same walk on
-        the bf16 operands of freeze_bn(backward="bf16")."""
-        grads = {}
-        f16 = ctx.frozen16   # bf16 backward convs: the operand dtypes of "_frozen16" above
-        mid = dict(g16_y32=True) if f16 else {}   # bn1 / bn2's g: stored bf16 by the fused dgrad
-        g = _backward_head(ctx, dfeat)   # grad at the last block output
-        pending = None     # the fused dgrad's partial sums of g (None: g is unmasked)
-        for blk, brec, prev3 in _backward_blocks(ctx, grads, lambda recs: recs[-1]):
-            r1, r2, rd, r3 = brec   # (rd: None without a downsample)
-            has_ds = rd is not None
-            dyd = None
-            if pending is None:
-                # g unmasked: mask (the block output's bits), dres in place, dy's and sums at once
-                s3 = _bn_wants_grad(r3.bn)
-                mk = dict(mask=3, bits=r3.zbits) if r3.zbits is not None else \
-                    dict(mask=1, z=r3.z)
-                if has_ds:
-                    sums = s3 or _bn_wants_grad(rd.bn)
-                    if f16:
-                        dy3, dyd, _, p3, pd, npp = ops.bn_frozen_bwd_ds_x(
-                            g, r3.y, r3.scale, r3.shift, r3.mean, rd.y, rd.scale, rd.mean,
-                            dres_inplace=True, want_sums=sums, dy16=True, **mk)
-                    else:
-                        dy3, dyd, p3, pd, npp = ops.bn_frozen_bwd_ds(
-                            g, r3.y, r3.scale, r3.shift, r3.mean, rd.y, rd.scale, rd.mean,
-                            dres_inplace=True, want_sums=sums, **mk)
-                    _frozen_affine(r3, (p3, npp) if sums else None, grads)
-                    _frozen_affine(rd, (pd, npp) if sums else None, grads)
-                elif f16:
-                    dy3, _, p3, npp = ops.bn_frozen_bwd_x(g, r3.y, r3.scale, r3.shift, r3.mean,
-                                                          dres_inplace=True, want_sums=s3,
-                                                          dy16=True, **mk)
-                    _frozen_affine(r3, (p3, npp) if s3 else None, grads)
-                else:
-                    dy3, p3, npp = ops.bn_frozen_bwd(g, r3.y, r3.scale, r3.shift, r3.mean,
-                                                     dres_inplace=True, want_sums=s3, **mk)
-                    _frozen_affine(r3, (p3, npp) if s3 else None, grads)
-                dz2, fz2 = _frozen_dy_bwd(r3, dy3, grads, fuse_prev=r2, **mid)
-                del dy3
-                gop = None
-            else:
-                dsum = has_ds and _bn_wants_grad(rd.bn)
-                gop = g    # the folded units' conv operand: g, or (f16) its bf16 copy
-                if f16:
-                    # one pass over the block output's fp32 g writes bf16(g): the downsample
-                    # BN's sums-only pass with one more store, else a plain cast
-                    u = rd if dsum else r3
-                    _, gop, pd, npp = ops.bn_frozen_bwd_x(g, u.y, u.scale, u.shift, u.mean,
-                                                          mask=0, want_dy=False, want_sums=dsum,
-                                                          want_g16=True)
-                elif dsum:
-                    _, pd, npp = ops.bn_frozen_bwd(g, rd.y, rd.scale, rd.shift, rd.mean, mask=0,
-                                                   want_dy=False)
-                if dsum:
-                    _frozen_affine(rd, (pd, npp), grads)
-                dz2, fz2 = _frozen_unit_bwd(r3, gop, grads, parts=pending, fuse_prev=r2, **mid)
-            dres = g   # masked: the identity branch's gradient
-            dz1, fz1 = _frozen_unit_bwd(r2, dz2, grads, parts=fz2, fuse_prev=r1, **mid)
-            del dz2
-            if has_ds:
-                if dyd is not None:
-                    dres, _ = _frozen_dy_bwd(rd, dyd, grads)
-                    del dyd
-                else:
-                    dres, _ = _frozen_unit_bwd(rd, gop, grads)
-            del gop
-            g, pending = _frozen_unit_bwd(r1, dz1, grads, parts=fz1, dx_out=dres, dx_beta=1.0,
-                                          fuse_prev=prev3)
-            del dz1, brec, dres
-        am, _ = ctx.pool
-        st = ctx.stem[0]
-        ss = _bn_wants_grad(st.bn)
-        if f16:
-            dy0, p0, np0 = ops.bn_frozen_bwd_maxpool_x(g, am, st.y, st.scale, st.shift, st.mean,
-                                                       want_sums=ss, dy16=True)
-        else:
-            dy0, p0, np0 = ops.bn_frozen_bwd_maxpool(g, am, st.y, st.scale, st.shift, st.mean,
-                                                     want_sums=ss)
-        _frozen_affine(st, (p0, np0) if ss else None, grads)
-        _frozen_dy_bwd(st, dy0, grads, need_dx=False)
-        return _backward_tail(ctx, grads)
-
-
-    @staticmethod
-    def _backward_frozen_fused(ctx, dfeat):
-        """The backward of the frozen step with BN folded into the conv forward ("_frozen_fused"):
-        _backward_frozen's affine=False walk without a y anywhere.  No BN gradient and no
-        sums-only pass; every dgrad that produces a previous unit's g masks by that unit's stored
-        output (_fused_unit_bwd); the last block's bn3 (g unmasked from the avgpool) takes one pass
-        of tmr_bn_frozen_bwd[_x] with mask 1 on its stored fp32 output, no sums, dres in place.
-        The stem is the unfused step's.  ctx.frozen16: the same operands, roundings and cast
-        passes as _backward_frozen's bf16 walk."""
+        """The frozen-BN step's backward, for every forward and backward of freeze_bn: no
+        BN-backward projection anywhere.  The last block's bn3 (g unmasked from the avgpool) and the
+        stem (g through the maxpool) take one pass of tmr_bn_frozen_bwd / _maxpool; every other
+        unit's g comes masked from the dgrad that produced it (with its partial sums where the
+        forward stored y), and its dy = g*scale lives in the conv operands (_frozen_unit_bwd).  A
+        downsample BN that trains needs sum g*(y_ds - mean_ds) of its own: one sums-only pass over
+        (g, y_ds).  The records say what the forward was: a unit of forward="fused" has no y, its
+        mask source is z, and no BN of that step wants a gradient, so no sums are ever asked for.
+        ctx.frozen16: the same walk on the bf16 operands of freeze_bn(backward="bf16")
+        ("_frozen16" above)."""
         grads = {}
         f16 = ctx.frozen16
         g = _backward_head(ctx, dfeat)   # grad at the last block output
         masked = False     # g came masked from the next block's conv1 dgrad
+        pending = None     # that dgrad's partial sums of g, where it emits them
         for blk, brec, prev3 in _backward_blocks(ctx, grads, lambda recs: recs[-1]):
             r1, r2, rd, r3 = brec   # (rd: None without a downsample)
+            has_ds = rd is not None
+            dyd = gop = None
             if not masked:
-                if rd is not None:
-                    raise RuntimeError("frozen BN, fused forward: a last block with a downsample "
-                                       "branch has no single-pass form")
-                if f16:
-                    dy3, _, _, _ = ops.bn_frozen_bwd_x(g, None, r3.scale, r3.shift, r3.mean,
-                                                       mask=1, z=r3.z, dres_inplace=True,
-                                                       want_sums=False, dy16=True)
+                # g unmasked: mask (the block output's bits, or z), dres in place, dy's and sums
+                # at once
+                s3 = _bn_wants_grad(r3.bn)
+                bits = r3.zbits   # (without bits -- forward="fused" -- the mask is z > 0)
+                mask = 1 if bits is None else 3
+                if has_ds:
+                    if r3.y is None:
+                        raise RuntimeError("frozen BN, fused forward: a last block with a "
+                                           "downsample branch has no single-pass form")
+                    sums = s3 or _bn_wants_grad(rd.bn)
+                    dy3, dyd, _, p3, pd, npp = ops.bn_frozen_bwd_ds(
+                        g, r3.y, r3.scale, r3.shift, r3.mean, rd.y, rd.scale, rd.mean,
+                        mask=mask, z=r3.z if bits is None else None, bits=bits,
+                        dres_inplace=True, want_sums=sums, dy16=f16)
                 else:
-                    dy3, _, _ = ops.bn_frozen_bwd(g, None, r3.scale, r3.shift, r3.mean, mask=1,
-                                                  z=r3.z, dres_inplace=True, want_sums=False)
-                if r3.fold:
-                    raise RuntimeError("frozen BN: a real dy meets pre-scaled dgrad weights")
-                dz2 = _fused_unit_bwd(r3, dy3, grads, f16, prev=r2)
+                    sums = s3
+                    dy3, _, p3, npp = ops.bn_frozen_bwd(
+                        g, r3.y, r3.scale, r3.shift, r3.mean,
+                        mask=mask, z=r3.z if bits is None else None, bits=bits,
+                        dres_inplace=True, want_sums=sums, dy16=f16)
+                _frozen_affine(r3, (p3, npp) if sums else None, grads)
+                if has_ds:
+                    _frozen_affine(rd, (pd, npp) if sums else None, grads)
+                dz2, fz2 = _frozen_unit_bwd(r3, dy3, grads, f16, real_dy=True, prev=r2)
                 del dy3
-                gop = None
             else:
+                dsum = has_ds and _bn_wants_grad(rd.bn)
                 gop = g    # the folded units' conv operand: g, or (f16) its bf16 copy
-                if f16:    # one cast pass per block output's fp32 g
-                    _, gop, _, _ = ops.bn_frozen_bwd_x(g, None, r3.scale, r3.shift, r3.mean,
-                                                       mask=0, want_dy=False, want_sums=False,
-                                                       want_g16=True)
-                dz2 = _fused_unit_bwd(r3, gop, grads, f16, prev=r2)
+                if f16 or dsum:
+                    # one pass over the block output's fp32 g: the downsample BN's sums of
+                    # (g, y_ds), and / or (f16) the store of bf16(g) -- alone, a plain cast
+                    u = rd if dsum else r3
+                    _, g16, pd, npp = ops.bn_frozen_bwd(g, u.y, u.scale, u.shift, u.mean, mask=0,
+                                                        want_dy=False, want_sums=dsum,
+                                                        want_g16=f16)
+                    if f16:
+                        gop = g16
+                    del g16, u
+                    if dsum:
+                        _frozen_affine(rd, (pd, npp), grads)
+                dz2, fz2 = _frozen_unit_bwd(r3, gop, grads, f16, parts=pending, prev=r2)
             dres = g   # masked: the identity branch's gradient
-            dz1 = _fused_unit_bwd(r2, dz2, grads, f16, prev=r1)
+            dz1, fz1 = _frozen_unit_bwd(r2, dz2, grads, f16, parts=fz2, prev=r1)
             del dz2
-            if rd is not None:
-                dres = _fused_unit_bwd(rd, gop, grads, f16)
-            del gop
-            g = _fused_unit_bwd(r1, dz1, grads, f16, prev=prev3, dx_out=dres, dx_beta=1.0)
+            if has_ds:
+                dres, _ = _frozen_unit_bwd(rd, gop if dyd is None else dyd, grads, f16,
+                                           real_dy=dyd is not None)
+            del gop, dyd
+            g, pending = _frozen_unit_bwd(r1, dz1, grads, f16, parts=fz1, prev=prev3, dx_out=dres,
+                                          dx_beta=1.0)
             masked = True
             del dz1, brec, dres
         am, _ = ctx.pool
         st = ctx.stem[0]
-        if f16:
-            dy0, _, _ = ops.bn_frozen_bwd_maxpool_x(g, am, st.y, st.scale, st.shift, st.mean,
-                                                    want_sums=False, dy16=True)
-        else:
-            dy0, _, _ = ops.bn_frozen_bwd_maxpool(g, am, st.y, st.scale, st.shift, st.mean,
-                                                  want_sums=False)
-        _frozen_dy_bwd(st, dy0, grads, need_dx=False)
+        ss = _bn_wants_grad(st.bn)
+        dy0, p0, np0 = ops.bn_frozen_bwd_maxpool(g, am, st.y, st.scale, st.shift, st.mean,
+                                                 want_sums=ss, dy16=f16)
+        _frozen_unit_bwd(st, dy0, grads, f16, real_dy=True, parts=(p0, np0) if ss else None,
+                         need_dx=False)
         return _backward_tail(ctx, grads)
 
 
